@@ -8,9 +8,16 @@ synthetic RecBole-shaped batches already resident in HBM; weights are the
 reference init.  Multi-GPU: one process per GPU (torchrun), batch-DP with
 DDP gradient all-reduce over RCCL, weak scaling (2048 per GPU).
 
-Prints ONE JSON line on rank 0 with the throughput, the HBM roofline of the
-dominant HIP kernel (HIP-event timed inside the timed region) and the CPU
-oracle baseline (rank 0, N=1 only).
+Prints ONE JSON line on rank 0 with the throughput and the HBM roofline of the
+dominant HIP kernel (HIP-event timed inside the timed region).  A plain run
+does no more: set up, --warmup steps, a short settle, --steps timed steps.
+--dump-outputs DIR then writes what the last timed step computed (loss,
+gradients, updated parameters) as DIR/<name>.npy; the timed steps start from
+the state the warmup left, so the same arguments give the same arrays.
+--full adds every other measurement to the line: the per-kernel and per-GEMM
+breakdown, the access-pattern ceilings, the A/B legs, the dense and
+fixed-length variants, configs[4], the DDP overhead and the CPU oracle
+baseline (rank 0, N=1 only).
 """
 from __future__ import annotations
 
@@ -694,15 +701,76 @@ def per_rank_ms(ms: float, env, dev) -> list:
     return [round(float(x.item()), 3) for x in got]
 
 
+def _snapshot(model, opt):
+    """Copies of everything a train step reads and updates: the parameters,
+    the optimizer's per-parameter state and torch's default generator (the
+    dropout seeds are drawn from it, blocks.draw_seed)."""
+    params = [p.detach().clone() for p in model.parameters()]
+    state = [{k: v.clone() if torch.is_tensor(v) else v for k, v in opt.state.get(p, {}).items()}
+             for p in model.parameters()]
+    return params, state, torch.get_rng_state()
+
+
+@torch.no_grad()
+def _restore(snap, model, opt):
+    """Put a _snapshot back in place (no tensor is re-allocated, so the timed
+    steps allocate nothing new); optimizer state created after the snapshot
+    goes back to its initial zeros."""
+    params, state, rng = snap
+    for p, saved, st_saved in zip(model.parameters(), params, state):
+        p.copy_(saved)
+        st = opt.state.get(p, {})
+        for k, v in st.items():
+            if torch.is_tensor(v) and k in st_saved:
+                v.copy_(st_saved[k])
+            elif torch.is_tensor(v):
+                v.zero_()
+            else:
+                st[k] = st_saved.get(k, 0)
+    torch.set_rng_state(rng)
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  Over
+    DUMP_LIMIT_BYTES in all, each array is cut to its share of the limit: a
+    sample of its flattened elements at sorted indices drawn with a fixed
+    seed (the same indices for the same shapes)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(4 * a.numel() for a in arrays.values())
+    for name, a in arrays.items():
+        x = a.detach().to(torch.float32).cpu().numpy()
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, int(x.size * DUMP_LIMIT_BYTES / total * 0.99))
+            idx = np.sort(np.random.default_rng(0).choice(x.size, size=keep, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--settle-seconds", type=float, default=15.0,
+    ap.add_argument("--settle-seconds", type=float, default=None,
                     help="after the warmup, keep running untimed steps for about this long "
                          "so the device clocks reach their sustained state (0: off); a fresh "
-                         "box runs the GEMMs ~15%% slower for its first seconds under load")
+                         "box runs the GEMMs ~15%% slower for its first seconds under load.  "
+                         "Default: 8 (the settle time of tools/ab_*.sh), 15 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other measurement (per-kernel and "
+                         "per-GEMM breakdown, access-pattern ceilings, A/B legs, dense and "
+                         "fixed-length variants, configs[4], DDP overhead, CPU baselines; the "
+                         "--no-* options below trim it).  Without it the run warms up, times "
+                         "--steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as "
+                         "DIR/<name>.npy (float32): loss, grad.<parameter> and "
+                         "param.<parameter> (after the update); rank 0 writes")
     ap.add_argument("--batch", type=int, default=2048, help="sequences per GPU")
     ap.add_argument("--seq-len", type=int, default=200)
     ap.add_argument("--hidden", type=int, default=128)
@@ -724,6 +792,8 @@ def main():
                     help="launch and rendezvous only: every rank joins a gloo group and rank 0 "
                          "prints the ranks' (rank, local_rank, world_size); no GPU is touched")
     args = ap.parse_args()
+    if args.settle_seconds is None:
+        args.settle_seconds = 15.0 if args.full else 8.0
 
     if args.dry_run:
         dry_run_ranks(args)
@@ -775,6 +845,11 @@ def main():
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
+    # the settle below runs a number of steps that depends on the clock: the
+    # timed steps start from the state the warmup left (parameters, optimizer
+    # state, dropout seeds), so the same arguments time the same arithmetic
+    # and --dump-outputs writes the same arrays from run to run
+    after_warmup = _snapshot(model, opt) if args.settle_seconds > 0 else None
     # settle: untimed steps, sized from three timed ones (the same count on every rank)
     settle_steps = 0
     if args.settle_seconds > 0:
@@ -788,6 +863,8 @@ def main():
             step(i)
         settle_steps += 3
         torch.cuda.synchronize()
+        _restore(after_warmup, model, opt)
+        del after_warmup
     barrier(env)
     torch.cuda.synchronize()
 
@@ -805,23 +882,40 @@ def main():
     if timing:
         timing.__exit__(None, None, None)
     rank_ms = per_rank_ms(1000.0 * elapsed / args.steps, env, dev)
+    if not torch.isfinite(loss):
+        raise RuntimeError(f"non-finite loss {loss}")
+    if args.dump_outputs and env.rank == 0:
+        # what the last timed step handed its caller: the loss, every
+        # parameter's gradient and the parameters after the Adam update
+        arrays = {"loss": loss}
+        for name, p in model.named_parameters():
+            if p.grad is not None:
+                arrays["grad." + name] = p.grad
+            arrays["param." + name] = p
+        dump_outputs(args.dump_outputs, arrays)
     # host side of a step: the time to queue one step's launches from an idle
     # device (median of 5) — close to ms_per_step means the host paces the step
-    host_ms = []
-    for i in range(5):
-        torch.cuda.synchronize()
-        t5 = time.perf_counter()
-        step(i)
-        host_ms.append(1000.0 * (time.perf_counter() - t5))
-        torch.cuda.synchronize()
-    host_enqueue_ms = sorted(host_ms)[2]
+    host_enqueue_ms = None
+    if args.full:
+        host_ms = []
+        for i in range(5):
+            torch.cuda.synchronize()
+            t5 = time.perf_counter()
+            step(i)
+            host_ms.append(1000.0 * (time.perf_counter() - t5))
+            torch.cuda.synchronize()
+        host_enqueue_ms = sorted(host_ms)[2]
     elapsed = max_over_ranks(elapsed, env, dev)
+
+    # everything past the headline runs with --full only; the --no-* options trim it
+    kernel_passes = args.full and not args.no_kernel_timing
+    variants = args.full and not args.no_full_tail
 
     # N > 1: the exchange on its own, and the same step without DDP on every
     # rank at once (no collective: what each GPU does alone while its
     # neighbours run) — the in-job reference for the scaling efficiency
-    multi = None
-    if env.world_size > 1:
+    multi = {"per_rank_ms_per_step": rank_ms} if env.world_size > 1 else None
+    if env.world_size > 1 and args.full:
         from datamining_recblr_amd.distributed import LossModule
         plain = LossModule(model)
         for i in range(2):
@@ -852,7 +946,7 @@ def main():
     # per-kernel / per-GEMM breakdown: a second pass with every launch timed
     timer = breakdown_ms = None
     opt_events = []
-    if not args.no_kernel_timing:
+    if kernel_passes:
         with kernels.kernel_timing() as timer:
             t2 = time.perf_counter()
             for i in range(args.steps):
@@ -869,8 +963,6 @@ def main():
                              "step, timed on its own in the breakdown pass"}
     ms = 1000.0 * elapsed / args.steps
     value = env.world_size * args.batch * args.steps / elapsed
-    if not torch.isfinite(loss):
-        raise RuntimeError(f"non-finite loss {loss}")
 
     # The same step in the reference's shapes, for comparison (results identical,
     # tests/test_gpu_eval.py): the dense [B, L] batch with the gathered tail,
@@ -895,7 +987,7 @@ def main():
                 "ms_per_step": round(1000.0 * el / args.steps, 3)}
 
     fixed = None
-    if not args.no_full_tail:
+    if variants:
         full_len = [synthetic_interaction(args.batch, args.seq_len, args.n_items, dev,
                                           seed=1000 * env.rank + 50 + i, fixed_len=True)
                     for i in range(4)]
@@ -906,7 +998,7 @@ def main():
                          "rows), the same step otherwise: a length-independent companion to "
                          "the headline, whose lengths are ~U{1..L}")
     devlen = None
-    if not args.no_full_tail:
+    if variants:
         # run.py's path: RecBole hands item_length as a bare device tensor
         # (RecBLR.py:86, run.py:84) — no host copy attached, so the packed
         # forward reads the token count from the device (one sync per step)
@@ -928,7 +1020,7 @@ def main():
                                 "keeps the host lengths (recbole_compat.install_interaction_hook)")
         devlen["recbole_interaction_path"] = recbole_path
     fused_ab = None
-    if not args.no_full_tail:
+    if variants:
         # the fused GatedRecurrentLayer kernels (experimental/grl_fused.hip, opt-in):
         # A/B against the headline's three-launch path on the same batches
         from datamining_recblr_amd import recurrence
@@ -946,7 +1038,7 @@ def main():
                             "batches: rb_grl_fwd (conv + gates GEMM + scan in one launch) "
                             "alone and with rb_grl_bwd, against the three-launch path")
     ffn_act_ab = None
-    if not args.no_full_tail:
+    if variants:
         # the FeedForward's activation in w_1's GEMM epilogue (rb_gemm_nt_h_act)
         # against the GEMM + rb_silu_dropout_fwd, alternated 3x on the lease
         from datamining_recblr_amd import linear as _lin
@@ -963,7 +1055,7 @@ def main():
                               "dropout(silu(.)) in its epilogue vs the GEMM and "
                               "rb_silu_dropout_fwd, best of 3 alternated runs each")
     nt_ab = None
-    if not args.no_full_tail:
+    if variants:
         # rb_gemm_nt_h's kernel for the encoder's projections: the weight-
         # stationary kernel (round 6, csrc/gemm_ws.hip) against round 5's
         # persistent tiles, alternated 3x on the lease
@@ -981,7 +1073,7 @@ def main():
                          "/ input-gradient GEMMs from 16,384 rows on the weight-stationary "
                          "kernel vs the persistent 256-row tiles; best of 3 alternated runs")
     order_ab = None
-    if not args.no_full_tail:
+    if variants:
         # the gate backward's consumers: the conv backward right behind the
         # dX GEMM that wrote its second input (default) vs the weight gradient
         # first (round 3), alternated 3x on the lease
@@ -999,7 +1091,7 @@ def main():
                             "GatedRecurrentLayer backward, the conv backward before the gates "
                             "weight gradient (its inputs just written) or after it; best of 3")
     adam_ab = None
-    if not args.no_full_tail:
+    if variants:
         # the optimizer update: rb_adam_step (one launch over every parameter)
         # against torch's fused Adam, alternated 3x on the lease (each with its
         # own state; the step's other work is the same)
@@ -1018,7 +1110,7 @@ def main():
         adam_ab["note"] = ("RECBLR_ADAM A/B on the headline's batches: rb_adam_step (native, one "
                            "launch) vs torch.optim.Adam(fused=True), best of 3 alternated runs")
     dense = full_tail = None
-    if not args.no_full_tail:
+    if variants:
         dense = timed_variant(False, True)
         dense["note"] = ("dense [B, L] batch (right padding computed, RECBLR_PACKED=0), "
                          "last layer's tail at the gathered positions")
@@ -1064,28 +1156,30 @@ def main():
         ntok_step = sum(int(batches[i % len(batches)]["item_length"].sum())
                         for i in range(args.steps)) / args.steps
         kernels_report = kernel_report(summ, args.steps, ntok_step, 2 * args.hidden, args.layers)
-        dsumm = dom_timer.summary() if dom_timer is not None else {}
-        if DOMINANT in dsumm:
-            d = dsumm[DOMINANT]
-            ach = d["avg_bytes"] / (d["avg_ms"] * 1e-3) / 1e9
-            traffic, src = pmc_traffic(args, "k_gate_scan_bwd")
-            roofline = {"kernel": DOMINANT, "bound": "hbm", "achieved": round(ach, 1),
-                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
-                        "traffic": traffic, "traffic_source": src,
-                        "algo_bytes_per_launch": int(d["avg_bytes"]),
-                        "avg_launch_us": round(d["avg_ms"] * 1e3, 2),
-                        "timed": "HIP events on the launch stream, inside the timed region"}
-    if roofline is not None and env.rank == 0 and args.hidden * 2 % 4 == 0:
+    # the dominant kernel's launches were timed inside the timed region: its
+    # roofline needs no run of its own and is part of every result line
+    dsumm = dom_timer.summary() if dom_timer is not None else {}
+    if DOMINANT in dsumm:
+        d = dsumm[DOMINANT]
+        ach = d["avg_bytes"] / (d["avg_ms"] * 1e-3) / 1e9
+        traffic, src = pmc_traffic(args, "k_gate_scan_bwd")
+        roofline = {"kernel": DOMINANT, "bound": "hbm", "achieved": round(ach, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
+                    "traffic": traffic, "traffic_source": src,
+                    "algo_bytes_per_launch": int(d["avg_bytes"]),
+                    "avg_launch_us": round(d["avg_ms"] * 1e3, 2),
+                    "timed": "HIP events on the launch stream, inside the timed region"}
+    if args.full and roofline is not None and env.rank == 0 and args.hidden * 2 % 4 == 0:
         roofline["pattern"] = gate_bwd_pattern(args, batches[0], dev)
     if gemm is not None and env.rank == 0 and fmt == "f16x3":
         gemm["pattern"] = gemm_pattern(args, batches[0], dev)
     ddp_ab = None
-    if env.world_size == 1 and not args.no_ddp_ab:
+    if args.full and env.world_size == 1 and not args.no_ddp_ab:
         ddp_ab = ddp_overhead(args, model, batches, dev)
-    scan = scan_microbench(args, dev) if env.rank == 0 else None
-    c5 = None if args.no_c5 else long_seq_c5(args, env, dev)   # every rank (weak scaling)
+    scan = scan_microbench(args, dev) if args.full and env.rank == 0 else None
+    c5 = long_seq_c5(args, env, dev) if args.full and not args.no_c5 else None   # every rank
     cpu = None
-    if env.rank == 0 and env.world_size == 1 and not args.no_cpu_baseline:
+    if args.full and env.rank == 0 and env.world_size == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, model.state_dict())
 
     from datamining_recblr_amd.linear import gemm_format
@@ -1114,7 +1208,9 @@ def main():
                        "seq_len": args.seq_len, "hidden_size": args.hidden, "inner_H": H,
                        "num_layers": args.layers, "n_items": args.n_items,
                        "dropout": args.dropout, "parallelism": f"dp{env.world_size}"},
-            "host_enqueue_ms_per_step": round(host_enqueue_ms, 3),
+            "full": args.full,
+            "host_enqueue_ms_per_step": (round(host_enqueue_ms, 3)
+                                         if host_enqueue_ms is not None else None),
             "multi_gpu": multi,
             "roofline": roofline,
             "gemm": gemm,

@@ -32,7 +32,11 @@ def pytest_collection_modifyitems(config, items):
 def load_golden(name):
     import torch
 
-    return torch.load(os.path.join(GOLDEN, name), weights_only=True)["cases"]
+    cases = torch.load(os.path.join(GOLDEN, name), weights_only=True)["cases"]
+    # a case too large to share a committed file with the others lies in a file
+    # of its own (make_golden.save_cases): {"stored_in": file} marks its place
+    return [torch.load(os.path.join(GOLDEN, c["stored_in"]), weights_only=True)["cases"][0]
+            if isinstance(c, dict) and set(c) == {"stored_in"} else c for c in cases]
 
 
 @pytest.fixture(scope="session")

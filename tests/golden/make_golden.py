@@ -140,11 +140,37 @@ def model_cases():
     return out
 
 
+BIG_CASE_BYTES = 512 * 1024   # no committed file over 1 MiB: such a case gets its own file
+
+
+def _nbytes(o):
+    if torch.is_tensor(o):
+        return o.numel() * o.element_size()
+    if isinstance(o, dict):
+        return sum(_nbytes(v) for v in o.values())
+    return 0
+
+
+def save_cases(cases, name):
+    """<name>: {"cases": [...]}; a case of BIG_CASE_BYTES or more is stored as
+    <stem>_<index>.pt and {"stored_in": that file} takes its place in the list
+    (conftest.load_golden puts it back)."""
+    cases, written = list(cases), [name]
+    for i, c in enumerate(cases):
+        if _nbytes(c) >= BIG_CASE_BYTES:
+            part = f"{name[:-3]}_{i}.pt"
+            torch.save({"cases": [c]}, os.path.join(HERE, part))
+            cases[i] = {"stored_in": part}
+            written.append(part)
+    torch.save({"cases": cases}, os.path.join(HERE, name))
+    return written
+
+
 def main():
-    torch.save({"cases": scan_cases()}, os.path.join(HERE, "scan_golden.pt"))
-    torch.save({"cases": grl_cases()}, os.path.join(HERE, "grl_golden.pt"))
-    torch.save({"cases": model_cases()}, os.path.join(HERE, "model_golden.pt"))
-    for f in ("scan_golden.pt", "grl_golden.pt", "model_golden.pt"):
+    written = save_cases(scan_cases(), "scan_golden.pt")
+    written += save_cases(grl_cases(), "grl_golden.pt")
+    written += save_cases(model_cases(), "model_golden.pt")
+    for f in written:
         print(f, os.path.getsize(os.path.join(HERE, f)))
 
 

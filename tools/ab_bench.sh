@@ -2,11 +2,12 @@
 # ab_bench.sh LIB_A LIB_B [ROUNDS] — alternate bench.py runs between two
 # builds (RECBLR_LIB), print value / path fraction / per-kernel fractions
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out
+OUT=${OUT:-build/ab}   # the run logs (build/ is ignored)
+mkdir -p "$OUT"
 for r in $(seq 1 ${3:-2}); do
   for lib in "$1" "$2"; do
-    RECBLR_LIB=$lib timeout -k 10 300 python bench.py --no-cpu-baseline --no-c5 --no-full-tail --settle-seconds ${SETTLE:-10} > gpurun_out/ab.log 2>&1 || exit 1
-    tail -1 gpurun_out/ab.log | python -c "
+    RECBLR_LIB=$lib timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-c5 --no-full-tail --settle-seconds ${SETTLE:-10} > "$OUT/ab.log" 2>&1 || exit 1
+    tail -1 "$OUT/ab.log" | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['kernels']
 print('$(basename $lib)', d['value'], d['ms_per_step'], 'path', k['scan_conv_gate_path']['frac'], ' '.join('%s=%.3f'%(n[3:],v['frac']) for n,v in k.items() if n.startswith('rb_')))"
   done

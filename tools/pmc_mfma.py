@@ -4,7 +4,7 @@
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F32 \
         SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_VALU_MFMA_MOPS_F16 \
         --output-format csv -d gpurun_out/pmc_mfma -o run \
-        -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-full-tail
+        -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-full-tail
     python tools/pmc_mfma.py gpurun_out/pmc_mfma > profiles/rNN_pmc_mfma.json
 
 MfmaUtil follows rocprofv3's derived metric on gfx950:

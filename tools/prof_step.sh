@@ -6,7 +6,7 @@ set -o pipefail
 TAG=${1:-prof}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out
-ARGS="--steps 10 --warmup 2 --settle-seconds 0 --no-cpu-baseline --no-full-tail --no-c5 --no-ddp-ab"
+ARGS="--full --steps 10 --warmup 2 --settle-seconds 0 --no-cpu-baseline --no-full-tail --no-c5 --no-ddp-ab"
 timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_kt -o run \
   -- python3 bench.py $ARGS > $OUT/${TAG}_prof.log 2>&1 || exit $?
 KT=$(ls $OUT/${TAG}_kt/*/run_kernel_trace.csv $OUT/${TAG}_kt/run_kernel_trace.csv 2>/dev/null | head -1)
