@@ -71,7 +71,7 @@ using namespace rb;
 
 extern "C" {
 
-int rb_version(void) { return 44; }
+int rb_version(void) { return 45; }
 
 const char* rb_last_error_string(void) { return g_last_error.c_str(); }
 
@@ -461,6 +461,25 @@ int rb_item_rank(const float* seq, const float* items, const int64_t* target, in
   if (first_item < 0) return fail("rb_item_rank: first_item must be >= 0");
   return launch_item_rank(seq, items, target, B, V, d, first_item, n_greater, n_equal, workspace,
                           workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
+int64_t rb_item_topk_workspace(int64_t B, int64_t V, int64_t d, int64_t k) {
+  if (B <= 0 || V <= 0 || d <= 0 || k < 1 || k > 64) return 0;
+  return item_topk_workspace_bytes(B, V, k);
+}
+
+int rb_item_topk(const float* seq, const float* items, int64_t B, int64_t V, int64_t d, int64_t k,
+                 int64_t first_item, const int64_t* exclude, int64_t E, int64_t* ids,
+                 float* scores, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (int rc = check_items("rb_item_topk", seq, items, B, V, d)) return rc;
+  if (!ids || !scores || !workspace) return fail("rb_item_topk: null pointer");
+  if (k < 1 || k > 64) return fail("rb_item_topk: k must be in [1, 64]");
+  if (first_item < 0) return fail("rb_item_topk: first_item must be >= 0");
+  if (E < 0) return fail("rb_item_topk: E must be >= 0");
+  if (E > 0 && !exclude) return fail("rb_item_topk: null pointer (exclude with E > 0)");
+  return launch_item_topk(seq, items, B, V, d, k, first_item, E > 0 ? exclude : nullptr, E, ids,
+                          scores, workspace, workspace_bytes,
+                          reinterpret_cast<hipStream_t>(stream));
 }
 
 int rb_item_ce_probs(const float* seq, const float* items, const int64_t* target,

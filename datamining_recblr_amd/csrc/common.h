@@ -452,6 +452,10 @@ int launch_item_ce_bwd(const float* E, const float* W, const int64_t* tgt, const
 int launch_item_rank(const float* E, const float* W, const int64_t* tgt, int64_t B, int64_t V,
                      int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq, void* ws,
                      int64_t ws_bytes, hipStream_t st);
+int64_t item_topk_workspace_bytes(int64_t B, int64_t V, int64_t k);
+int launch_item_topk(const float* E, const float* W, int64_t B, int64_t V, int64_t D, int64_t k,
+                     int64_t first, const int64_t* ex, int64_t NE, int64_t* ids, float* scores,
+                     void* ws, int64_t ws_bytes, hipStream_t st);
 int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, const float* lse,
                          const float* dloss, int64_t B, int64_t V, int64_t D, int64_t v_off,
                          int64_t n_total, float* out, int64_t ld, hipStream_t st);

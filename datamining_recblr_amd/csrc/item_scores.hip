@@ -614,6 +614,200 @@ __global__ __launch_bounds__(256) void k_rank_rows(const int* __restrict__ gt_pa
   if (n_eq) n_eq[b] = bad ? -1 : e;
 }
 
+// ---- top-k: each row's k best items, no score matrix -------------------------------
+// k_item_rank's frame (a lane owns sequence row b and sees 16 items per
+// tile) with a selection epilogue.  Candidates order by (score descending,
+// id ascending): `beats` below.  Per (row, split) a list of k candidates
+// lives in LDS, unsorted, owned by the row's h = 0 lane, which keeps the
+// list's worst entry (score, id, position) in registers as the admission
+// threshold.  A score passes the cheap filter when it is >= the threshold
+// score (false for NaN); the h = 1 lane hands its passing candidates to h = 0
+// by shuffle, so one lane writes a list.  An admitted candidate replaces the
+// worst entry and the list is rescanned for the new worst (k independent LDS
+// reads, no dependent shift chain).  Empty slots are (-inf, kNoItem), which
+// every real candidate beats, a -inf score included.
+//
+// Exclusion: the row's two lanes hash the exclude entries that fall into the
+// split's item range into the row's kExBits-bit map in LDS (atomic OR: the
+// map does not depend on the order).  A candidate whose bit is clear is not
+// excluded; a set bit is confirmed by scanning the row's list unless the
+// split's range fits the map (then the map is exact: the evaluation shape's
+// 352-item splits).  Only candidates that beat the threshold pay for the
+// lookup.
+constexpr int kNoItem = 0x7fffffff;
+constexpr int kExBits = 512;   // exclusion map bits per row
+
+__device__ __forceinline__ bool beats(float s, int id, float s2, int id2) {
+  return s > s2 || (s == s2 && id < id2);
+}
+
+template <int D, int KP>
+__global__ __launch_bounds__(256) void k_item_topk(const float* __restrict__ E,
+                                                   const float* __restrict__ W, int64_t B,
+                                                   int64_t V, int64_t first, int k,
+                                                   const int64_t* __restrict__ ex, int64_t NE,
+                                                   int64_t per, int64_t RB, int64_t NS,
+                                                   float* __restrict__ c_sc,
+                                                   int* __restrict__ c_id) {
+  constexpr int KH = D / 2, NR = kWaves * kTile, XW = kExBits / 32;
+  // entry i / map word w of row r at [i * NR + r] / [w * NR + r]: lanes of a
+  // wave touching the same entry or word hit distinct banks
+  __shared__ float l_sc[KP * NR];
+  __shared__ int l_id[KP * NR];
+  __shared__ unsigned l_ex[XW * NR];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
+  Place pl;
+  if (!place(RB, NS, pl)) return;
+  const int64_t b = (pl.rb * kWaves + wave) * kTile + j;
+  const int64_t bc = min(b, B - 1);
+  float eb[KH];
+  ld_half<KH>(eb, E + bc * D, h);
+  const int row = wave * kTile + j;
+  // the split's item range [v_lo, v_hi)
+  const int64_t v_lo = pl.split * per * kTile, v_hi = min((pl.split + 1) * per * kTile, V);
+  const bool ex_exact = v_hi - v_lo <= kExBits;
+  const int64_t* exr = ex + bc * NE;
+  if (h == 0) {
+    for (int i = 0; i < k; ++i) {
+      l_sc[i * NR + row] = -INFINITY;
+      l_id[i * NR + row] = kNoItem;
+    }
+  }
+  if (NE > 0) {
+#pragma unroll
+    for (int w = 0; w < XW / 2; ++w) l_ex[(h * (XW / 2) + w) * NR + row] = 0u;
+    __syncthreads();
+    for (int64_t e = h; e < NE; e += 2) {
+      const int64_t v = exr[e];
+      if (v >= v_lo && v < v_hi) {
+        const int hb = (int)(v - v_lo) & (kExBits - 1);
+        atomicOr(&l_ex[(hb >> 5) * NR + row], 1u << (hb & 31));
+      }
+    }
+  }
+  __syncthreads();
+  float thr = -INFINITY;   // the list's worst entry (h = 0 owns it; h = 1 holds a copy of thr)
+  int thr_id = kNoItem, thr_pos = 0;
+  auto excluded = [&](int id) -> bool {
+    const int hb = (id - (int)v_lo) & (kExBits - 1);
+    const unsigned wd = l_ex[(hb >> 5) * NR + row];
+    if (!((wd >> (hb & 31)) & 1u)) return false;
+    if (ex_exact) return true;
+    for (int64_t e = 0; e < NE; ++e)
+      if (exr[e] == (int64_t)id) return true;
+    return false;
+  };
+  auto try_insert = [&](float s, int id) {   // h = 0 lanes only
+    if (!beats(s, id, thr, thr_id)) return;
+    if (NE > 0 && excluded(id)) return;
+    l_sc[thr_pos * NR + row] = s;
+    l_id[thr_pos * NR + row] = id;
+    float ws = s;
+    int wi = id, wp = thr_pos;
+    for (int i = 0; i < k; ++i) {
+      const float a = l_sc[i * NR + row];
+      const int c = l_id[i * NR + row];
+      if (beats(ws, wi, a, c)) {
+        ws = a;
+        wi = c;
+        wp = i;
+      }
+    }
+    thr = ws;
+    thr_id = wi;
+    thr_pos = wp;
+  };
+  stream_tiles<D, false>(W, V, per, pl.split, nullptr, nullptr,
+                         [&](int64_t t, const float* tile, const float*, const int64_t*) {
+    const int64_t v0 = t * kTile;
+    const f32x16 x = lds_dot<D, KH, true>(tile, j, h, eb);
+    const int lo = rel32(first, v0), hi = rel32(V, v0);
+    unsigned m = 0;   // bit r: score r passes the cheap filter
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int c = crow(r, h);
+      m |= ((c >= lo) & (c < hi) & (x[r] >= thr)) ? 1u << r : 0u;
+    }
+    // wave-uniform loop: every lane takes its lowest passing score per turn
+    while (__builtin_amdgcn_ballot_w64(m != 0) != 0) {
+      const bool p = m != 0;
+      const int r = p ? __builtin_ctz(m) : 0;
+      m &= m - 1;
+      float cs = x[0];
+#pragma unroll
+      for (int q = 1; q < 16; ++q) cs = r == q ? x[q] : cs;
+      const int cid = (int)v0 + crow(r, h);
+      const float s1 = __shfl_xor(cs, 32);
+      const int id1 = __shfl_xor(cid, 32);
+      const int p1 = __shfl_xor((int)p, 32);
+      if (h == 0) {
+        if (p) try_insert(cs, cid);
+        if (p1) try_insert(s1, id1);
+      }
+      thr = __shfl(thr, j);
+    }
+  });
+  if (h == 0 && b < B) {
+    const int64_t o = (pl.split * B + b) * k;
+    for (int i = 0; i < k; ++i) {
+      c_sc[o + i] = l_sc[i * NR + row];
+      c_id[o + i] = l_id[i * NR + row];
+    }
+  }
+}
+
+// One wave per row: the row's S lists of k candidates (all ids distinct: the
+// splits partition the items) merged into the k best in order.  Turn t takes
+// the best candidate that the previous turn's pick beats, so nothing is
+// marked; the reduction over lanes uses the full comparison, so the result
+// does not depend on which lane held which candidate.  Empty slots and turns
+// that find nothing give id -1, score -inf.
+__global__ __launch_bounds__(256) void k_topk_rows(const float* __restrict__ c_sc,
+                                                   const int* __restrict__ c_id, int64_t S,
+                                                   int64_t B, int k, int64_t* __restrict__ ids,
+                                                   float* __restrict__ scores) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int64_t n = S * k;
+  float ps = INFINITY, my_s = -INFINITY;
+  int pid = -1, my_id = kNoItem;   // previous pick: beats every candidate at first
+  for (int t = 0; t < k; ++t) {
+    float bs = -INFINITY;
+    int bid = kNoItem;
+    if (pid != kNoItem) {
+      for (int64_t c = lane; c < n; c += 64) {
+        const int64_t sp = c / k, i = c - sp * k;
+        const float s = c_sc[(sp * B + b) * k + i];
+        const int id = c_id[(sp * B + b) * k + i];
+        if (beats(ps, pid, s, id) && beats(s, id, bs, bid)) {
+          bs = s;
+          bid = id;
+        }
+      }
+#pragma unroll
+      for (int sh = 32; sh >= 1; sh >>= 1) {
+        const float os = __shfl_xor(bs, sh);
+        const int oid = __shfl_xor(bid, sh);
+        if (beats(os, oid, bs, bid)) {
+          bs = os;
+          bid = oid;
+        }
+      }
+    }
+    ps = bs;
+    pid = bid;
+    if (lane == t) {
+      my_s = bs;
+      my_id = bid;
+    }
+  }
+  if (lane < k) {
+    ids[b * k + lane] = my_id == kNoItem ? -1 : (int64_t)my_id;
+    scores[b * k + lane] = my_s;
+  }
+}
+
 // ---- score matrix (full_sort_predict) and CE gradient of the logits -------------
 // X[b][v], lane = item column v, rows b in registers, stored as 128-B row
 // segments.  kProbs: stores P[b][v] = (exp(x - lse[b]) - [v + v_off ==
@@ -1054,6 +1248,21 @@ RankWs rank_layout(int64_t B, int64_t V) {
   return o;
 }
 
+struct TopkWs {
+  size_t sc, id, total;
+};
+
+TopkWs topk_layout(int64_t B, int64_t V, int64_t k) {
+  const Grid2 f = plan(B, ntiles(V));
+  TopkWs o{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t r = off; off = al256(off + bytes); return r; };
+  o.sc = take(f.splits * B * k * 4);
+  o.id = take(f.splits * B * k * 4);
+  o.total = off;
+  return o;
+}
+
 #define RB_ITEM_DISPATCH(D, FN, ...)              \
   switch (D) {                                    \
     case 16: FN<16>(__VA_ARGS__); break;          \
@@ -1099,6 +1308,17 @@ void rank_t(const float* E, const float* W, const float* ts, const int64_t* tgt,
             int64_t V, int64_t first, const Grid2& g, int* gt, int* eq, hipStream_t st) {
   hipLaunchKernelGGL(k_item_rank<D>, dim3(g.wgs()), dim3(256), 0,
                      st, E, W, ts, tgt, B, V, first, g.per, g.blocks, g.splits, gt, eq);
+}
+
+template <int D>
+void topk_t(const float* E, const float* W, int64_t B, int64_t V, int64_t first, int k,
+            const int64_t* ex, int64_t NE, const Grid2& g, float* sc, int* id, hipStream_t st) {
+  if (k <= 32)
+    hipLaunchKernelGGL((k_item_topk<D, 32>), dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, k,
+                       ex, NE, g.per, g.blocks, g.splits, sc, id);
+  else
+    hipLaunchKernelGGL((k_item_topk<D, 64>), dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, k,
+                       ex, NE, g.per, g.blocks, g.splits, sc, id);
 }
 
 template <int D>
@@ -1217,6 +1437,25 @@ int launch_item_rank(const float* E, const float* W, const int64_t* tgt, int64_t
   hipLaunchKernelGGL(k_rank_rows, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, gt, eq,
                      g.splits, ts, B, n_gt, n_eq);
   return launch_status("rb_item_rank");
+}
+
+int64_t item_topk_workspace_bytes(int64_t B, int64_t V, int64_t k) {
+  return (int64_t)topk_layout(B, V, k).total;
+}
+
+int launch_item_topk(const float* E, const float* W, int64_t B, int64_t V, int64_t D, int64_t k,
+                     int64_t first, const int64_t* ex, int64_t NE, int64_t* ids, float* scores,
+                     void* ws, int64_t ws_bytes, hipStream_t st) {
+  const TopkWs L = topk_layout(B, V, k);
+  if (ws_bytes < (int64_t)L.total) return fail("rb_item_topk: workspace too small");
+  char* w = static_cast<char*>(ws);
+  float* sc = reinterpret_cast<float*>(w + L.sc);
+  int* id = reinterpret_cast<int*>(w + L.id);
+  const Grid2 g = plan(B, ntiles(V));
+  RB_ITEM_DISPATCH(D, topk_t, E, W, B, V, first, (int)k, ex, NE, g, sc, id, st);
+  hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, sc, id,
+                     g.splits, B, (int)k, ids, scores);
+  return launch_status("rb_item_topk");
 }
 
 int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, const float* lse,

@@ -14,14 +14,17 @@ the rank of each row's target (rb_item_rank, no score matrix):
     forward (up to fp32 reassociation in the GEMMs).  Metrics follow the
     reference: NDCG@k as sklearn.metrics.ndcg_score (tie-averaged) over
     scores[1:], Hit@k as "target among the k best of scores[1:]".
+
+``recommend`` returns what a served model returns: each user's k best items
+(rb_item_topk, again no score matrix), batched like ``evaluate_unseen``.
 """
 from __future__ import annotations
 
 import torch
 
-from .scoring import rank_metrics, target_ranks
+from .scoring import rank_metrics, target_ranks, top_items
 
-__all__ = ["unseen_inputs", "evaluate_unseen", "full_sort_metrics"]
+__all__ = ["unseen_inputs", "evaluate_unseen", "full_sort_metrics", "recommend"]
 
 
 def unseen_inputs(sequences, pad_id: int = 0):
@@ -98,3 +101,43 @@ def full_sort_metrics(model, batches, topk=(10, 20)):
         eqs.append(e.cpu())
     model.train(was_training)
     return rank_metrics(torch.cat(gts), torch.cat(eqs), topk=topk, ties="optimistic")
+
+
+@torch.no_grad()
+def recommend(model, item_id_lists, k: int = 10, batch_size: int = 1024,
+              exclude_seen: bool = True, device=None):
+    """Each user's k best items from their input id sequence.
+
+    item_id_lists: per-user id sequences (ints in [0, n_items)), batched by
+    length with ``forward(..., exact_lengths=True)`` as evaluate_unseen does,
+    so every row equals its batch-1 forward.  Item 0 (padding) is never
+    recommended; exclude_seen also drops the user's own input items.  Returns
+    (ids int64 [n, k], scores fp32 [n, k]) on the CPU in the callers' order,
+    by (score descending, id ascending), id -1 / score -inf where fewer than k
+    items are selectable (scoring.top_items).  The model's train/eval mode is
+    left as found."""
+    device = device or next(model.parameters()).device
+    was_training = model.training
+    model.eval()
+    n = len(item_id_lists)
+    lens = torch.tensor([max(1, len(x)) for x in item_id_lists], dtype=torch.int64)
+    order = torch.argsort(lens, stable=True)
+    ids = torch.full((n, k), -1, dtype=torch.int64)
+    scores = torch.full((n, k), float("-inf"), dtype=torch.float32)
+    table = model.item_embedding.weight
+    try:
+        for s in range(0, n, batch_size):
+            idx = order[s:s + batch_size]
+            L = int(lens[idx].max())
+            seq = torch.zeros((len(idx), L), dtype=torch.int64)
+            for r, u in enumerate(idx.tolist()):
+                row = item_id_lists[u] or [0]
+                seq[r, :len(row)] = torch.as_tensor(row, dtype=torch.int64)
+            seq = seq.to(device)
+            out = model.forward(seq, lens[idx].to(device), exact_lengths=True)
+            i, sc = top_items(out, table, k, first_item=1, exclude=seq if exclude_seen else None)
+            ids[idx] = i.cpu()
+            scores[idx] = sc.cpu()
+    finally:
+        model.train(was_training)
+    return ids, scores

@@ -19,7 +19,7 @@ __all__ = [
     "scan_fwd", "scan_bwd", "conv_silu_fwd", "conv_silu_bwd", "gate_scan_fwd",
     "gate_scan_bwd", "num_tiles", "RecBLRNativeError", "kernel_timing", "KernelTimer",
     "item_ce_fwd", "item_ce_bwd", "item_ce_probs", "item_rank", "item_scores",
-    "SplitRows", "item_split_h", "item_ce_fwd_h", "item_ce_probs_h",
+    "item_topk", "SplitRows", "item_split_h", "item_ce_fwd_h", "item_ce_probs_h",
     "embedding_bwd", "embedding_plan",
 ]
 
@@ -685,7 +685,7 @@ def embedding_plan(idx, num_rows, d, stream=None):
 # Launches timed in FLOPs rather than bytes (bench.py reports them against the
 # MFMA roofline).
 FLOP_KERNELS = frozenset({"rb_item_ce_fwd", "rb_item_ce_bwd", "rb_item_ce_probs", "rb_item_rank",
-                          "rb_item_scores", "rb_item_ce_fwd_h", "rb_item_ce_probs_h",
+                          "rb_item_scores", "rb_item_topk", "rb_item_ce_fwd_h", "rb_item_ce_probs_h",
                           "rb_item_ce_probs_h_t", "rb_item_ce_probs_h_both"})
 
 
@@ -924,6 +924,39 @@ def item_rank(seq, items, target, first_item=1, want_equal=True):
             B, V, d, int(first_item), gt.data_ptr(), eq.data_ptr() if eq is not None else None,
             ws.data_ptr(), ws_bytes, _stream(seq), _flops=True)
     return gt, eq
+
+
+ITEM_TOPK_MAX = 64
+
+
+def item_topk(seq, items, k, first_item=1, exclude=None):
+    """(ids int64 [B, k], scores fp32 [B, k]): each row's k best items in
+    [first_item, V) not listed in exclude [B, E] (int64; entries outside
+    [0, V) ignored), by (score descending, id ascending), scores bit-identical
+    to item_scores'; id -1 / score -inf where fewer than k are selectable.
+    No [B, V] buffer (rb_item_topk)."""
+    seq, items, _ = _item_operands(seq, items)
+    B, d = seq.shape
+    V = items.shape[0]
+    k = int(k)
+    if not 1 <= k <= ITEM_TOPK_MAX:
+        raise ValueError(f"k = {k} not in [1, {ITEM_TOPK_MAX}]")
+    E = 0
+    if exclude is not None:
+        _check(exclude, "exclude", dtype=torch.int64)
+        if exclude.dim() != 2 or exclude.shape[0] != B:
+            raise ValueError(f"exclude must be [B, E], got {tuple(exclude.shape)}")
+        exclude = exclude.contiguous()
+        E = exclude.shape[1]
+    lib = _lib.load()
+    ws_bytes = int(lib.rb_item_topk_workspace(B, V, d, k))
+    ws = torch.empty((ws_bytes,), device=seq.device, dtype=torch.uint8)
+    ids = torch.empty((B, k), device=seq.device, dtype=torch.int64)
+    scores = torch.empty((B, k), device=seq.device, dtype=torch.float32)
+    _launch("rb_item_topk", 2 * B * V * d, seq.data_ptr(), items.data_ptr(), B, V, d, k,
+            int(first_item), exclude.data_ptr() if E > 0 else None, E, ids.data_ptr(),
+            scores.data_ptr(), ws.data_ptr(), ws_bytes, _stream(seq), _flops=True)
+    return ids, scores
 
 
 def item_scores(seq, items):

@@ -36,7 +36,7 @@ from .recbole_compat import BPRLoss, SequentialRecommender, install_interaction_
 from .recurrence import bd_lru, fused_ok, pow2_pad_len, row_pad_lens
 
 
-from .scoring import full_sort_scores, item_cross_entropy, target_ranks
+from .scoring import full_sort_scores, item_cross_entropy, target_ranks, top_items
 
 # RECBLR_CONV_ROWS=0: packed conv forward per sequence instead of per row tile
 _CONV_ROWS = os.environ.get("RECBLR_CONV_ROWS", "1") != "0"
@@ -437,3 +437,15 @@ class RecBLR(SequentialRecommender):
         seq_output = self.forward(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN])
         return target_ranks(seq_output, self.item_embedding.weight,
                             interaction[self.POS_ITEM_ID], first_item)
+
+    @torch.no_grad()
+    def full_sort_topk(self, interaction, k: int = 10, exclude_seen: bool = True,
+                       first_item: int = 1):
+        """(ids, scores) [B, k]: each row's k best items under
+        full_sort_predict's scores (RecBLR.py:114-122) without materialising
+        them, by (score descending, id ascending) over items [first_item,
+        n_items); exclude_seen drops the row's own ITEM_SEQ entries."""
+        item_seq = interaction[self.ITEM_SEQ]
+        seq_output = self.forward(item_seq, interaction[self.ITEM_SEQ_LEN])
+        return top_items(seq_output, self.item_embedding.weight, k, first_item=first_item,
+                         exclude=item_seq if exclude_seen else None)

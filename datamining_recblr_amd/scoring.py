@@ -14,7 +14,9 @@ RECBLR_CE_PIPE), ranking and scores on the fp32 pipe:
     ditems = P^T seq from P = softmax - onehot in registers;
   * target_ranks: per row, the number of items scoring above / equal to the
     target, from which Hit@k, MRR@k and NDCG@k follow exactly;
-  * full_sort_scores: the score matrix itself when a caller needs it.
+  * full_sort_scores: the score matrix itself when a caller needs it;
+  * top_items: each row's k best items (a recommendation list), with
+    seen-item exclusion, selected inside the scoring kernel.
 """
 from __future__ import annotations
 
@@ -26,7 +28,7 @@ import torch.nn.functional as F
 from . import kernels
 
 __all__ = ["item_cross_entropy", "full_sort_scores", "target_ranks", "rank_metrics",
-           "supported"]
+           "top_items", "supported"]
 
 
 def supported(seq: torch.Tensor, table: torch.Tensor) -> bool:
@@ -247,6 +249,65 @@ def target_ranks(seq: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
         raise kernels.RecBLRNativeError("target_ranks needs fp32 CUDA tensors with d in "
                                         f"{kernels.ITEM_DIMS}")
     return kernels.item_rank(seq.detach(), table.detach(), target, first_item=first_item)
+
+
+def _top_items_torch(seq, table, k, first_item, exclude):
+    """top_items' contract in plain torch (any device, any d, any k)."""
+    scores = seq.float() @ table.float().t()
+    B, V = scores.shape
+    dev = scores.device
+    drop = torch.isnan(scores)
+    drop[:, :min(max(int(first_item), 0), V)] = True
+    if exclude is not None and exclude.numel() > 0:
+        ex = exclude.to(device=dev, dtype=torch.int64)
+        ok = (ex >= 0) & (ex < V)
+        rows = torch.arange(B, device=dev)[:, None].expand_as(ex)
+        drop[rows[ok], ex[ok]] = True
+    masked = torch.where(drop, torch.full_like(scores, float("-inf")), scores)
+    # ids ascending, stable descending sort: equal scores keep the smaller id
+    # first; a second stable sort moves the dropped columns behind the rest
+    # (a selectable item may itself score -inf)
+    order = torch.sort(masked, dim=1, descending=True, stable=True).indices
+    back = torch.sort(drop.gather(1, order).to(torch.int8), dim=1, stable=True).indices
+    order = order.gather(1, back)
+    n_ok = (~drop).sum(1, keepdim=True)
+    kk = min(k, V)
+    ids = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+    out = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
+    live = torch.arange(kk, device=dev)[None, :] < n_ok
+    ids[:, :kk] = torch.where(live, order[:, :kk], ids[:, :kk])
+    out[:, :kk] = torch.where(live, scores.gather(1, order[:, :kk]), out[:, :kk])
+    return ids, out
+
+
+@torch.no_grad()
+def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 1,
+              exclude: torch.Tensor | None = None):
+    """Each row's k best items: (ids int64 [B, k], scores fp32 [B, k]).
+
+    Selects over items in [first_item, V) not listed in exclude [B, E] (int64;
+    entries outside [0, V) are ignored and duplicates allowed, so item_seq
+    with its 0 padding serves as the seen-item list), ordered by (score
+    descending, item id ascending) — rank_metrics' "optimistic" convention for
+    a target with the smallest id of its tied group.  NaN scores are never
+    selected; when fewer than k items are selectable the tail holds id -1,
+    score -inf.  On fp32 GPU tensors with d in kernels.ITEM_DIMS and k <= 64
+    the selection runs inside the scoring kernel (rb_item_topk: no [B, V]
+    buffer, scores bit-identical to full_sort_scores'); anything else takes a
+    plain torch path with the same contract."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k = {k} must be positive")
+    if int(first_item) < 0:
+        raise ValueError(f"first_item = {first_item} must be >= 0")
+    if exclude is not None and (exclude.dim() != 2 or exclude.shape[0] != seq.shape[0]):
+        raise ValueError(f"exclude must be [B, E], got {tuple(exclude.shape)}")
+    if supported(seq, table) and k <= kernels.ITEM_TOPK_MAX:
+        if exclude is not None:
+            exclude = exclude.to(device=seq.device, dtype=torch.int64)
+        return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
+                                 exclude=exclude)
+    return _top_items_torch(seq.detach(), table.detach(), k, first_item, exclude)
 
 
 def rank_metrics(n_greater: torch.Tensor, n_equal: torch.Tensor | None = None,

@@ -404,6 +404,26 @@ int rb_item_rank(const float* seq, const float* items, const int64_t* target, in
                  int64_t V, int64_t d, int64_t first_item, int64_t* n_greater, int64_t* n_equal,
                  void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Workspace bytes of the top-k call below: the per-(row, item split) candidate
+ * lists only, 8 k bytes each; nothing proportional to B V.  0 for arguments
+ * the call would reject. */
+int64_t rb_item_topk_workspace(int64_t B, int64_t V, int64_t d, int64_t k);
+
+/* Each row's k best items under full_sort_predict's scores (RecBLR.py:114-122)
+ * without the [B, V] score matrix: over items v in [first_item, V) that are
+ * not listed in exclude[b, :] (exclude [B, E] int64, or NULL with E = 0;
+ * entries outside [0, V) are ignored and duplicates allowed, so item_seq with
+ * its 0 padding can be passed as it is), ordered by (score descending, item id
+ * ascending).  ids, scores: [B, k] contiguous; scores[b][i] is bit-identical
+ * to the score matrix entry (b, ids[b][i]).  A NaN score is never selected,
+ * +-inf order as floats; when fewer than k items are selectable the remaining
+ * slots hold id -1, score -inf.  1 <= k <= 64.  Deterministic: per-split
+ * candidates are merged in a fixed order. */
+int rb_item_topk(const float* seq, const float* items, int64_t B, int64_t V, int64_t d,
+                 int64_t k, int64_t first_item, const int64_t* exclude, int64_t E,
+                 int64_t* ids, float* scores, void* workspace, int64_t workspace_bytes,
+                 void* stream);
+
 /* scores[b][v] = seq[b] . items[v] (full_sort_predict, RecBLR.py:114-122), same
  * fma chain as the kernels above; scores [B, V] contiguous. */
 int rb_item_scores(const float* seq, const float* items, int64_t B, int64_t V, int64_t d,
