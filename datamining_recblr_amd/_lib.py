@@ -4,11 +4,18 @@ The shared library is built in-tree by ``datamining_recblr_amd.build`` (or
 ``__graft_entry__.build()``) as ``datamining_recblr_amd/lib/libdmrecblr.so``.
 There is no fallback: if the library is missing, every product entry point
 raises ``RecBLRNativeError``.
+
+The headers are the only statement of the prototypes and constants: the
+``*SIGNATURES`` tables, ``ABI_VERSION``, ``RB_TILE`` and ``RB_EINVAL`` are
+parsed from them on import (``parse_header``).  A new entry point is declared
+in the header and defined in csrc/capi.hip, and ``RB_ABI_VERSION`` is bumped;
+nothing here is edited.
 """
 from __future__ import annotations
 
 import ctypes
 import os
+import re
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -17,175 +24,128 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RECBLR_LIB") or os.path.join(_HERE, "lib", "libdmrecblr.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "recblr_hip.h")
 
-RB_EINVAL = -1
-RB_TILE = 16
-ABI_VERSION = 45
-
-_i64 = ctypes.c_int64
-_fp = ctypes.c_void_p  # device pointers are passed as integers
-_f32 = ctypes.c_float
-_u64 = ctypes.c_uint64
-
-# name -> (restype, argtypes); kept in the order of include/recblr_hip.h
-SIGNATURES = {
-    "rb_version": (ctypes.c_int, []),
-    "rb_last_error_string": (ctypes.c_char_p, []),
-    "rb_num_kernels": (ctypes.c_int, []),
-    "rb_scan_fwd": (ctypes.c_int, [_fp, _fp, _fp, _i64, _i64, _i64, _fp]),
-    "rb_scan_bwd": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _i64, _i64, _fp]),
-    "rb_conv_silu_fwd": (ctypes.c_int, [_fp, _i64, _fp, _fp, _fp, _i64, _i64, _i64, _i64, _i64, _fp, _fp]),
-    "rb_conv_silu_fwd_rows": (ctypes.c_int, [_fp, _i64, _fp, _fp, _fp, _i64, _i64, _i64, _i64,
-                                             _fp, _fp]),
-    "rb_conv_silu_fwd_rows_bf16": (ctypes.c_int, [_fp, _i64, _fp, _fp, _fp, _i64, _i64, _i64,
-                                                  _i64, _fp, _fp]),
-    "rb_conv_silu_bwd": (ctypes.c_int, [_fp, _i64, _fp, _fp, _fp, _fp, _fp, _i64, _fp, _fp,
-                                        _i64, _i64, _i64, _i64, _fp, _fp]),
-    "rb_gate_scan_fwd": (ctypes.c_int, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp, _i64, _fp,
-                                        _i64, _fp, _i64, _i64, _i64, _fp, _fp]),
-    "rb_gate_scan_fwd_last": (ctypes.c_int, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp,
-                                             _i64, _fp, _fp, _i64, _i64, _i64, _fp, _fp, _fp]),
-    "rb_gate_scan_bwd_last": (ctypes.c_int, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp,
-                                             _fp, _fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp,
-                                             _i64, _i64, _i64, _fp, _fp, _fp]),
-    "rb_gate_scan_bwd": (ctypes.c_int, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _fp,
-                                        _i64, _fp, _i64, _fp, _i64, _fp, _fp, _i64, _i64, _i64,
-                                        _fp, _fp]),
-    "rb_pad_prefix_fwd": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _i64, _i64, _fp, _fp, _fp]),
-    "rb_pad_prefix_bwd": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _i64, _i64, _fp, _fp, _fp,
-                                         _fp, _fp, _fp, ctypes.c_int, _fp]),
-    "rb_add_ln_fwd": (ctypes.c_int, [_fp, _fp, _i64, _fp, _u64, _f32, _fp, _fp, _fp, _f32, _fp,
-                                     _fp, _fp, _fp, _i64, _i64, _fp]),
-    "rb_row_num_parts": (ctypes.c_int64, [_i64, _i64]),
-    "rb_add_ln_bwd": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _u64, _f32, _fp, _fp, _fp, _fp,
-                                     _fp, _i64, _i64, _i64, _fp]),
-    "rb_add_ln_bwd2": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _u64, _f32, _fp, _fp, _fp, _fp,
-                                     _fp, _i64, _i64, _i64, _fp]),
-    "rb_silu_dropout_fwd": (ctypes.c_int, [_fp, _fp, _fp, _u64, _f32, _fp, _i64, _i64, _fp]),
-    "rb_silu_dropout_bwd": (ctypes.c_int, [_fp, _fp, _fp, _u64, _f32, _fp, _fp, _fp, _i64, _i64,
-                                           _i64, _fp]),
-    "rb_dropout_mask": (ctypes.c_int, [_u64, _f32, _fp, _i64, _fp]),
-    "rb_embedding_bwd_workspace": (ctypes.c_int64, [_i64, _i64, _i64]),
-    "rb_embedding_bwd": (ctypes.c_int, [_fp, _fp, _i64, _i64, _i64, _i64, _fp, _fp, _i64, _fp]),
-    "rb_embedding_bwd_plan": (ctypes.c_int, [_fp, _i64, _i64, _i64, _fp, _i64, _fp]),
-    "rb_embedding_bwd_apply": (ctypes.c_int, [_fp, _i64, _i64, _i64, _i64, _fp, _fp, _i64, _fp]),
-    "rb_colsum": (ctypes.c_int, [_fp, _i64, _i64, _i64, _i64, _i64, _fp, _fp]),
-    "rb_colsum_chunked": (ctypes.c_int, [_fp, _i64, _i64, _i64, _i64, _i64, _fp, _fp, _i64, _fp,
-                                         _fp]),
-    "rb_item_ce_workspace": (ctypes.c_int64, [_i64, _i64, _i64]),
-    "rb_item_ce_fwd": (ctypes.c_int, [_fp, _fp, _fp, _i64, _i64, _i64, _fp, _fp, _fp, _i64, _fp]),
-    "rb_item_ce_bwd": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _i64, _i64, _fp, _fp, _fp,
-                                      _i64, _fp]),
-    "rb_item_split_h": (ctypes.c_int, [_fp, _i64, _i64, _fp, _fp, _fp, _fp]),
-    "rb_item_ce_fwd_h": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _i64, _i64, _fp, _fp, _fp,
-                                        _i64, _fp]),
-    "rb_item_ce_probs_h": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _i64, _i64,
-                                          _i64, _fp, _i64, _fp]),
-    "rb_item_ce_probs_h_t": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _i64, _i64,
-                                            _i64, _fp, _i64, _fp, _fp]),
-    "rb_item_ce_probs_h_both": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _i64,
-                                               _i64, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp]),
-    "rb_group_absmax": (ctypes.c_int, [_fp, _i64, _i64, _i64, _fp, _fp]),
-    "rb_item_rank_workspace": (ctypes.c_int64, [_i64, _i64, _i64]),
-    "rb_item_rank": (ctypes.c_int, [_fp, _fp, _fp, _i64, _i64, _i64, _i64, _fp, _fp, _fp, _i64,
-                                    _fp]),
-    "rb_item_topk_workspace": (ctypes.c_int64, [_i64, _i64, _i64, _i64]),
-    "rb_item_topk": (ctypes.c_int, [_fp, _fp, _i64, _i64, _i64, _i64, _i64, _fp, _i64, _fp, _fp,
-                                    _fp, _i64, _fp]),
-    "rb_item_ce_probs": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _i64, _i64, _i64, _fp, _i64,
-                                        _fp]),
-    "rb_item_scores": (ctypes.c_int, [_fp, _fp, _i64, _i64, _i64, _fp, _fp]),
-    "rb_scan_fwd_bf16": (ctypes.c_int, [_fp, _fp, _fp, _i64, _i64, _i64, _fp]),
-    "rb_scan_bwd_bf16": (ctypes.c_int, [_fp, _fp, _fp, _fp, _fp, _i64, _i64, _i64, _fp]),
-    "rb_conv_silu_fwd_bf16": (ctypes.c_int, [_fp, _i64, _fp, _fp, _fp, _i64, _i64, _i64, _i64,
-                                             _i64, _fp, _fp]),
-    "rb_conv_silu_bwd_bf16": (ctypes.c_int, [_fp, _i64, _fp, _fp, _fp, _fp, _fp, _i64, _fp, _fp,
-                                             _i64, _i64, _i64, _i64, _fp, _fp]),
-    "rb_gate_scan_fwd_bf16": (ctypes.c_int, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp,
-                                             _i64, _fp, _i64, _fp, _i64, _i64, _i64, _fp, _fp]),
-    "rb_gate_scan_bwd_bf16": (ctypes.c_int, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp,
-                                             _fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _i64,
-                                             _i64, _i64, _fp, _fp]),
-    "rb_pack_plan": (ctypes.c_int, [_fp, _i64, _fp, _fp, _i64, _i64, _fp, _fp, _fp, _fp, _fp]),
-    "rb_gemm_h_weight_bytes": (ctypes.c_int64, [_i64, _i64]),
-    "rb_gemm_nt_h_mode": (ctypes.c_int, [ctypes.c_int]),
-    "rb_gemm_nt_h_ln": (ctypes.c_int, [_fp, _i64, _i64, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _f32,
-                                       _u64, _f32, _fp, _fp, _fp, _fp, _i64, _fp, _fp]),
-    "rb_gemm_h_split_weights": (ctypes.c_int, [_fp, _i64, _fp]),
-    "rb_gemm_nt_h": (ctypes.c_int, [_fp, _i64, _i64, _i64, _fp, _i64, _fp, _fp, _i64, ctypes.c_int,
-                                    _fp, _fp]),
-    "rb_gemm_nt_h_act": (ctypes.c_int, [_fp, _i64, _i64, _i64, _fp, _i64, _fp, _fp, _i64, _fp,
-                                        _fp, _u64, _f32, _fp]),
-    "rb_adam_step": (ctypes.c_int, [_fp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                    ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                    ctypes.c_double, _fp]),
-    "rb_gemm_nt_h_dact_parts": (_i64, []),
-    "rb_gemm_nt_h_dact": (ctypes.c_int, [_fp, _i64, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _fp,
-                                         _u64, _f32, _fp, _i64, _fp]),
-    "rb_gemm_bf16_weight_image": (ctypes.c_int, [_fp, _i64, _i64, _i64, ctypes.c_int, _fp, _fp]),
-    "rb_gemm_nt_bf16": (ctypes.c_int, [_fp, _i64, _i64, _i64, _fp, _i64, _fp, _fp, _i64, _fp]),
-    "rb_gemm_tn_h": (ctypes.c_int, [_fp, _i64, _fp, _i64, _i64, _i64, _i64, _fp, _fp, _fp, _i64,
-                                    _fp]),
-    "rb_gemm_tn_hs": (ctypes.c_int, [_fp, _i64, _fp, _i64, _i64, _i64, _i64, _fp, ctypes.c_int, _fp]),
-}
-
 
 class RecBLRNativeError(RuntimeError):
     """The HIP extension is missing, failed to load, or a kernel call failed."""
 
 
+# the only types the headers may pass by value (device pointers are passed as integers)
+_BY_VALUE = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+             "float": ctypes.c_float, "double": ctypes.c_double}
+_NOT_DECLARATIONS = re.compile(
+    r'/\*.*?\*/|//[^\n]*|^[ \t]*#[^\n]*|\btypedef\b(?:[^;{]|\{[^}]*\})*;|extern\s+"C"\s*\{|^\s*\}\s*$',
+    re.S | re.M)
+
+
+def parse_header(text: str) -> dict:
+    """name -> (restype, [argtypes]) of every function a C header declares, in
+    declaration order.  Comments, preprocessor lines, typedefs and the
+    extern "C" braces are dropped; what remains must be plain declarations,
+    one per ';', over pointers and the scalar types of _BY_VALUE."""
+    out = {}
+    for decl in _NOT_DECLARATIONS.sub(" ", text).split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        m = re.fullmatch(r"([\w\s*]+?)\s*\b(\w+)\s*\(([^()]*)\)", decl)
+        if m is None:
+            raise RecBLRNativeError(f"header: not a plain function declaration: {decl!r}")
+        ret, name, params = m.groups()
+        if re.fullmatch(r"const\s+char\s*\*", ret):
+            restype = ctypes.c_char_p
+        elif ret in _BY_VALUE:
+            restype = _BY_VALUE[ret]
+        else:
+            raise RecBLRNativeError(f"header: {name}: unsupported return type {ret!r}")
+        argtypes = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            words = param.split()
+            by_value = " ".join(words[:-1] if len(words) > 1 else words)   # drop the name
+            if "*" in param:
+                argtypes.append(ctypes.c_void_p)
+            elif by_value in _BY_VALUE:
+                argtypes.append(_BY_VALUE[by_value])
+            else:
+                raise RecBLRNativeError(f"header: {name}: unsupported parameter {param.strip()!r}")
+        out[name] = (restype, argtypes)
+    return out
+
+
+def _read(path: str) -> str:
+    with open(path) as f:
+        return f.read()
+
+
+def _define(text: str, name: str) -> int:
+    m = re.search(rf"^[ \t]*#[ \t]*define[ \t]+{name}[ \t]+\(?(-?\d+)\)?[ \t]*$", text, re.M)
+    if m is None:
+        raise RecBLRNativeError(f"header: no integer #define {name}")
+    return int(m.group(1))
+
+
+_header = _read(HEADER_PATH)
+RB_EINVAL = _define(_header, "RB_EINVAL")
+RB_TILE = _define(_header, "RB_TILE")
+ABI_VERSION = _define(_header, "RB_ABI_VERSION")
+
+# name -> (restype, argtypes), in header order
+SIGNATURES = parse_header(_header)
 # the experimental library (experimental/recblr_exp.h: opt-in kernels that
 # measured slower than the default path; never loaded unless requested)
-EXP_SIGNATURES = {
-    "rb_exp_version": (ctypes.c_int, []),
-    "rb_exp_last_error_string": (ctypes.c_char_p, []),
-    "rb_grl_fwd": (ctypes.c_int, [_fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _i64,
-                                  _i64, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _i64, _fp, _fp,
-                                  _i64, _fp]),
-    "rb_grl_bwd": (ctypes.c_int, [_fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i64,
-                                  _i64, _i64, _i64, _fp, _i64, _fp, _fp, _fp, _i64, _fp, _fp,
-                                  _fp, _fp, _fp, _fp, _fp]),
-}
-
+EXP_SIGNATURES = parse_header(_read(os.path.join(_HERE, "experimental", "recblr_exp.h")))
 # the probe library (probes/recblr_probe.h: bench.py's measurement aids)
-PROBE_SIGNATURES = {
-    "rb_probe_gemm_pattern": (ctypes.c_int, [_fp, _i64, _i64, _fp, _i64, _fp]),
-    "rb_probe_gate_bwd_pattern": (ctypes.c_int, [_fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _i64,
-                                                 _fp, _i64, _fp, _i64, _i64, _i64, _i64, _fp,
-                                                 _fp]),
-}
+PROBE_SIGNATURES = parse_header(_read(os.path.join(_HERE, "probes", "recblr_probe.h")))
 
 _lock = threading.Lock()
-_lib = None
-_probe = None
-_exp = None
+_loaded = {}
 
 
-def load(path: str | None = None) -> ctypes.CDLL:
-    """Load (once) and return the native library with typed prototypes."""
-    global _lib
+def _load(path, signatures, missing, version=None, mismatch=None, cache=True,
+          hint="") -> ctypes.CDLL:
+    """Load (once per path when cached) a library and type its prototypes."""
     with _lock:
-        if _lib is not None and path is None:
-            return _lib
-        p = path or LIB_PATH
-        if not os.path.exists(p):
-            raise RecBLRNativeError(
-                f"HIP extension not built: {p} is missing. Run "
-                "`python -m datamining_recblr_amd.build` (hipcc --offload-arch=gfx950)."
-            )
+        if cache and path in _loaded:
+            return _loaded[path]
+        if not os.path.exists(path):
+            raise RecBLRNativeError(f"{missing}: {path} is missing. Run "
+                                    f"`python -m datamining_recblr_amd.build`{hint}.")
         try:
-            lib = ctypes.CDLL(p)
+            lib = ctypes.CDLL(path)
         except OSError as exc:  # pragma: no cover - depends on the host
-            raise RecBLRNativeError(f"failed to load {p}: {exc}") from exc
-        for name, (res, args) in SIGNATURES.items():
+            raise RecBLRNativeError(f"failed to load {path}: {exc}") from exc
+        for name, (res, args) in signatures.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        if lib.rb_version() != ABI_VERSION:
-            raise RecBLRNativeError(
-                f"ABI mismatch: library {lib.rb_version()} vs binding {ABI_VERSION}; rebuild")
-        if path is None:
-            _lib = lib
+        if version is not None and getattr(lib, version)() != ABI_VERSION:
+            raise RecBLRNativeError(mismatch.format(getattr(lib, version)(), ABI_VERSION))
+        if cache:
+            _loaded[path] = lib
         return lib
+
+
+def load(path: str | None = None) -> ctypes.CDLL:
+    """Load (once) and return the native library with typed prototypes.  An
+    explicit path is loaded afresh and not cached."""
+    return _load(path or LIB_PATH, SIGNATURES, "HIP extension not built", "rb_version",
+                 "ABI mismatch: library {} vs binding {}; rebuild", cache=path is None,
+                 hint=" (hipcc --offload-arch=gfx950)")
+
+
+def load_probe() -> ctypes.CDLL:
+    """The probe library (lib/libdmrecblr_probe.so): measurement aids for
+    bench.py, never on the model's path."""
+    return _load(os.path.join(os.path.dirname(LIB_PATH), "libdmrecblr_probe.so"),
+                 PROBE_SIGNATURES, "probe library not built")
+
+
+def load_exp() -> ctypes.CDLL:
+    """The experimental library (lib/libdmrecblr_exp.so, experimental/
+    recblr_exp.h): the opt-in fused GatedRecurrentLayer kernels.  Loaded only
+    when one of them is requested; the default path never loads it."""
+    return _load(os.path.join(os.path.dirname(LIB_PATH), "libdmrecblr_exp.so"), EXP_SIGNATURES,
+                 "experimental library not built", "rb_exp_version",
+                 "experimental library ABI {} vs {}; rebuild")
 
 
 _fns = {}
@@ -199,6 +159,19 @@ def on_failure(hook) -> None:
     _failure_hooks.append(hook)
 
 
+def _check(rc: int, name: str, lib: ctypes.CDLL, last_error: str, hooks: bool = True) -> None:
+    """Raise on a non-zero status with the library's message for it."""
+    if rc == 0:
+        return
+    kind = str(rc)
+    if hooks:
+        for hook in _failure_hooks:
+            hook()
+        kind = "invalid argument" if rc == RB_EINVAL else f"hipError {rc}"
+    msg = getattr(lib, last_error)()
+    raise RecBLRNativeError(f"{name} failed ({kind}): {msg.decode() if msg else ''}")
+
+
 def call(name: str, *args) -> None:
     """Invoke a C-ABI entry point and raise on a non-zero status."""
     fn = _fns.get(name)
@@ -206,76 +179,17 @@ def call(name: str, *args) -> None:
         fn = _fns[name] = getattr(load(), name)
     rc = fn(*args)
     if rc != 0:
-        for hook in _failure_hooks:
-            hook()
-        lib = load()
-        msg = lib.rb_last_error_string()
-        msg = msg.decode() if msg else ""
-        kind = "invalid argument" if rc == RB_EINVAL else f"hipError {rc}"
-        raise RecBLRNativeError(f"{name} failed ({kind}): {msg}")
-
-
-def load_probe() -> ctypes.CDLL:
-    """The probe library (lib/libdmrecblr_probe.so): measurement aids for
-    bench.py, never on the model's path."""
-    global _probe
-    with _lock:
-        if _probe is not None:
-            return _probe
-        p = os.path.join(os.path.dirname(LIB_PATH), "libdmrecblr_probe.so")
-        if not os.path.exists(p):
-            raise RecBLRNativeError(f"probe library not built: {p} is missing. Run "
-                                    "`python -m datamining_recblr_amd.build`.")
-        lib = ctypes.CDLL(p)
-        for name, (res, args) in PROBE_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib.rb_probe_last_error_string.restype = ctypes.c_char_p
-        _probe = lib
-        return lib
+        _check(rc, name, load(), "rb_last_error_string")
 
 
 def call_probe(name: str, *args) -> None:
-    """Invoke a probe-library entry point and raise on a non-zero status."""
+    """Invoke a probe-library entry point and raise on a non-zero status (the
+    bare status, and no failure hooks: nothing on the model's path ran)."""
     lib = load_probe()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        msg = lib.rb_probe_last_error_string()
-        raise RecBLRNativeError(f"{name} failed ({rc}): {msg.decode() if msg else ''}")
-
-
-def load_exp() -> ctypes.CDLL:
-    """The experimental library (lib/libdmrecblr_exp.so, experimental/
-    recblr_exp.h): the opt-in fused GatedRecurrentLayer kernels.  Loaded only
-    when one of them is requested; the default path never loads it."""
-    global _exp
-    with _lock:
-        if _exp is not None:
-            return _exp
-        p = os.path.join(os.path.dirname(LIB_PATH), "libdmrecblr_exp.so")
-        if not os.path.exists(p):
-            raise RecBLRNativeError(f"experimental library not built: {p} is missing. Run "
-                                    "`python -m datamining_recblr_amd.build`.")
-        lib = ctypes.CDLL(p)
-        for name, (res, args) in EXP_SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        if lib.rb_exp_version() != ABI_VERSION:
-            raise RecBLRNativeError(f"experimental library ABI {lib.rb_exp_version()} vs "
-                                    f"{ABI_VERSION}; rebuild")
-        _exp = lib
-        return lib
+    _check(getattr(lib, name)(*args), name, lib, "rb_probe_last_error_string", hooks=False)
 
 
 def call_exp(name: str, *args) -> None:
     """Invoke an experimental-library entry point and raise on a non-zero status."""
     lib = load_exp()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        for hook in _failure_hooks:
-            hook()
-        msg = lib.rb_exp_last_error_string()
-        kind = "invalid argument" if rc == RB_EINVAL else f"hipError {rc}"
-        raise RecBLRNativeError(f"{name} failed ({kind}): {msg.decode() if msg else ''}")
+    _check(getattr(lib, name)(*args), name, lib, "rb_exp_last_error_string")

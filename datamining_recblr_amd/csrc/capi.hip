@@ -15,6 +15,12 @@ int fail(const char* msg) {
   return RB_EINVAL;
 }
 
+// an argument error of entry point fn: "<fn>: <msg>"
+static int fail(const char* fn, const char* msg) {
+  g_last_error = std::string(fn) + ": " + msg;
+  return RB_EINVAL;
+}
+
 int num_cus() {
   static std::atomic<int> cache[64];
   int dev = 0;
@@ -40,8 +46,7 @@ int launch_status(const char* what) {
 namespace {
 
 // Per-lane offsets inside one batch row are 32-bit: L * row_stride must fit.
-int check_dims(const char* fn, int64_t B, int64_t L, int64_t H, int64_t max_rs) {
-  (void)fn;
+int check_dims(int64_t B, int64_t L, int64_t H, int64_t max_rs) {
   if (B <= 0 || L <= 0 || H <= 0) return fail("B, L and H must be positive");
   if (L * max_rs + max_rs >= (int64_t(1) << 31)) return fail("L * row_stride exceeds 2^31");
   if (B * ((H + 15) / 16) / 4 + 1 > 0x7fffffffLL) return fail("grid too large");
@@ -51,6 +56,109 @@ int check_dims(const char* fn, int64_t B, int64_t L, int64_t H, int64_t max_rs) 
 int64_t max4(int64_t a, int64_t b, int64_t c = 0, int64_t d = 0) {
   return std::max(std::max(a, b), std::max(c, d));
 }
+
+hipStream_t as_stream(void* stream) { return reinterpret_cast<hipStream_t>(stream); }
+
+// ---- the recurrence entry points: one body per operation, shared by the fp32
+// (T = float) and bf16 (T = bf16_t) storage forms; fn is the entry point's name
+
+template <typename T>
+int scan_fwd(const char* fn, const T* gates, const T* tokens, T* states, int64_t B, int64_t C,
+             int64_t steps, void* stream) {
+  if (!gates || !tokens || !states) return fail(fn, "null pointer");
+  if (B <= 0 || C <= 0 || steps <= 0) return fail(fn, "B, C, T must be positive");
+  const int64_t rows = B * C;
+  if ((rows + 3) / 4 > 0x7fffffffLL) return fail(fn, "too many rows");
+  return launch_scan_fwd<T>(gates, tokens, states, rows, steps, as_stream(stream));
+}
+
+template <typename T>
+int scan_bwd(const char* fn, const T* gates, const T* states, const T* grad, T* d_gates,
+             T* d_tokens, int64_t B, int64_t C, int64_t steps, void* stream) {
+  if (!gates || !states || !grad || !d_gates || !d_tokens) return fail(fn, "null pointer");
+  if (B <= 0 || C <= 0 || steps <= 0) return fail(fn, "B, C, T must be positive");
+  const int64_t rows = B * C;
+  if ((rows + 3) / 4 > 0x7fffffffLL) return fail(fn, "too many rows");
+  return launch_scan_bwd<T>(gates, states, grad, d_gates, d_tokens, rows, steps,
+                            as_stream(stream));
+}
+
+template <typename T>
+int conv_silu_fwd(const char* fn, const T* x, int64_t x_rs, const float* w, const float* bias,
+                  T* xc, int64_t xc_rs, int64_t B, int64_t L, int64_t H, int64_t K,
+                  const int64_t* seq_offsets, void* stream) {
+  if (!x || !w || !bias || !xc) return fail(fn, "null pointer");
+  if (K < 1 || K > 8) return fail(fn, "kernel size K must be in [1, 8]");
+  if (x_rs < H || xc_rs < H) return fail(fn, "row stride < H");
+  if (int r = check_dims(B, L, H, max4(x_rs, xc_rs))) return r;
+  return launch_conv_fwd<T>(x, x_rs, w, bias, xc, xc_rs, B, L, H, K, seq_offsets,
+                            as_stream(stream));
+}
+
+template <typename T>
+int conv_silu_fwd_rows(const char* fn, const T* x, int64_t x_rs, const float* w,
+                       const float* bias, T* xc, int64_t xc_rs, int64_t ntok, int64_t H,
+                       int64_t K, const int64_t* row_pos, void* stream) {
+  if (!x || !w || !bias || !xc || !row_pos) return fail(fn, "null pointer");
+  if (K < 1 || K > 8) return fail(fn, "kernel size K must be in [1, 8]");
+  if (x_rs < H || xc_rs < H) return fail(fn, "row stride < H");
+  if (int r = check_dims(ntok, 1, H, max4(x_rs, xc_rs))) return r;
+  return launch_conv_fwd_rows<T>(x, x_rs, w, bias, xc, xc_rs, ntok, H, K, row_pos,
+                                 as_stream(stream));
+}
+
+template <typename T>
+int conv_silu_bwd(const char* fn, const T* x, int64_t x_rs, const float* w, const float* bias,
+                  const T* g1, const T* g2, T* dx, int64_t dx_rs, float* dw_part, float* db_part,
+                  int64_t B, int64_t L, int64_t H, int64_t K, const int64_t* seq_offsets,
+                  void* stream) {
+  if (!x || !w || !bias || !g1 || !dx || !dw_part)   // db_part NULL: folded layout
+    return fail(fn, "null pointer");
+  if (K < 1 || K > 8) return fail(fn, "kernel size K must be in [1, 8]");
+  if (x_rs < H || dx_rs < H) return fail(fn, "row stride < H");
+  if (int r = check_dims(B, L, H, max4(x_rs, dx_rs, H))) return r;
+  return launch_conv_bwd<T>(x, x_rs, w, bias, g1, g2, dx, dx_rs, dw_part, db_part, B, L, H, K,
+                            seq_offsets, as_stream(stream));
+}
+
+// y_last / batch_row: rb_gate_scan_fwd_last (y NULL, y_rs = H); NULL otherwise
+template <typename T>
+int gate_scan_fwd(const char* fn, const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs,
+                  const T* z, int64_t z_rs, const float* lam, const float* gate_b,
+                  const float* h0, int64_t h0_bs, T* y, int64_t y_rs, float* carries, int64_t B,
+                  int64_t L, int64_t H, const int64_t* seq_offsets, void* stream,
+                  T* y_last = nullptr, const int64_t* batch_row = nullptr) {
+  if (!rg || !xc || !z || !lam || !(y || y_last)) return fail(fn, "null pointer");
+  if (h0_bs != 0 && h0_bs < H) return fail(fn, "h0 batch stride must be 0 or >= H");
+  if (rg_rs < 2 * H || xc_rs < H || z_rs < H || y_rs < H) return fail(fn, "row stride too small");
+  if (int r = check_dims(B, L, H, max4(rg_rs, xc_rs, z_rs, y_rs))) return r;
+  return launch_gate_fwd<T>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, h0, h0_bs, y, y_rs,
+                            carries, B, L, H, seq_offsets, as_stream(stream), y_last, batch_row);
+}
+
+// dy_last / batch_row: rb_gate_scan_bwd_last (dy NULL); NULL otherwise
+template <typename T>
+int gate_scan_bwd(const char* fn, const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs,
+                  const T* z, int64_t z_rs, const float* lam, const float* gate_b,
+                  const float* carries, const T* dy, T* drg, int64_t drg_rs, T* dxc,
+                  int64_t dxc_rs, T* dz, int64_t dz_rs, float* part, float* dh0_part, int64_t B,
+                  int64_t L, int64_t H, const int64_t* seq_offsets, void* stream,
+                  const T* dy_last = nullptr, const int64_t* batch_row = nullptr) {
+  if (!rg || !xc || !z || !lam || !carries || !(dy || dy_last) || !drg || !dxc || !dz || !part ||
+      !dh0_part)
+    return fail(fn, "null pointer");
+  if (rg_rs < 2 * H || xc_rs < H || z_rs < H || drg_rs < 2 * H || dxc_rs < H || dz_rs < H)
+    return fail(fn, "row stride too small");
+  if (int r = check_dims(B, L, H, max4(max4(rg_rs, xc_rs, z_rs, drg_rs), dz_rs, dxc_rs, H)))
+    return r;
+  return launch_gate_bwd<T>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, carries, dy, drg, drg_rs,
+                            dxc, dxc_rs, dz, dz_rs, part, dh0_part, B, L, H, seq_offsets,
+                            as_stream(stream), dy_last, batch_row);
+}
+
+// rb_bf16 (raw bits in the C header) is the kernels' bf16_t
+const bf16_t* bf(const rb_bf16* p) { return reinterpret_cast<const bf16_t*>(p); }
+bf16_t* bf(rb_bf16* p) { return reinterpret_cast<bf16_t*>(p); }
 
 }  // namespace
 
@@ -71,7 +179,7 @@ using namespace rb;
 
 extern "C" {
 
-int rb_version(void) { return 45; }
+int rb_version(void) { return RB_ABI_VERSION; }
 
 const char* rb_last_error_string(void) { return g_last_error.c_str(); }
 
@@ -79,68 +187,51 @@ int rb_num_kernels(void) { return 24; }
 
 int rb_scan_fwd(const float* gates, const float* tokens, float* states, int64_t B, int64_t C,
                 int64_t T, void* stream) {
-  if (!gates || !tokens || !states) return fail("rb_scan_fwd: null pointer");
-  if (B <= 0 || C <= 0 || T <= 0) return fail("rb_scan_fwd: B, C, T must be positive");
-  const int64_t rows = B * C;
-  if ((rows + 3) / 4 > 0x7fffffffLL) return fail("rb_scan_fwd: too many rows");
-  return launch_scan_fwd(gates, tokens, states, rows, T, reinterpret_cast<hipStream_t>(stream));
+  return scan_fwd(__func__, gates, tokens, states, B, C, T, stream);
 }
 
 int rb_scan_bwd(const float* gates, const float* states, const float* grad, float* d_gates,
                 float* d_tokens, int64_t B, int64_t C, int64_t T, void* stream) {
-  if (!gates || !states || !grad || !d_gates || !d_tokens)
-    return fail("rb_scan_bwd: null pointer");
-  if (B <= 0 || C <= 0 || T <= 0) return fail("rb_scan_bwd: B, C, T must be positive");
-  const int64_t rows = B * C;
-  if ((rows + 3) / 4 > 0x7fffffffLL) return fail("rb_scan_bwd: too many rows");
-  return launch_scan_bwd(gates, states, grad, d_gates, d_tokens, rows, T,
-                         reinterpret_cast<hipStream_t>(stream));
+  return scan_bwd(__func__, gates, states, grad, d_gates, d_tokens, B, C, T, stream);
 }
 
 int rb_conv_silu_fwd(const float* x, int64_t x_rs, const float* w, const float* bias, float* xc,
-                     int64_t xc_rs, int64_t B, int64_t L, int64_t H, int64_t K, const int64_t* seq_offsets, void* stream) {
-  if (!x || !w || !bias || !xc) return fail("rb_conv_silu_fwd: null pointer");
-  if (K < 1 || K > 8) return fail("rb_conv_silu_fwd: kernel size K must be in [1, 8]");
-  if (x_rs < H || xc_rs < H) return fail("rb_conv_silu_fwd: row stride < H");
-  if (int r = check_dims("rb_conv_silu_fwd", B, L, H, max4(x_rs, xc_rs))) return r;
-  return launch_conv_fwd(x, x_rs, w, bias, xc, xc_rs, B, L, H, K,
-                         seq_offsets, reinterpret_cast<hipStream_t>(stream));
+                     int64_t xc_rs, int64_t B, int64_t L, int64_t H, int64_t K,
+                     const int64_t* seq_offsets, void* stream) {
+  return conv_silu_fwd(__func__, x, x_rs, w, bias, xc, xc_rs, B, L, H, K, seq_offsets, stream);
 }
 
 int rb_conv_silu_fwd_rows(const float* x, int64_t x_rs, const float* w, const float* bias,
                           float* xc, int64_t xc_rs, int64_t ntok, int64_t H, int64_t K,
                           const int64_t* row_pos, void* stream) {
-  if (!x || !w || !bias || !xc || !row_pos) return fail("rb_conv_silu_fwd_rows: null pointer");
-  if (K < 1 || K > 8) return fail("rb_conv_silu_fwd_rows: kernel size K must be in [1, 8]");
-  if (x_rs < H || xc_rs < H) return fail("rb_conv_silu_fwd_rows: row stride < H");
-  if (int r = check_dims("rb_conv_silu_fwd_rows", ntok, 1, H, max4(x_rs, xc_rs))) return r;
-  return launch_conv_fwd_rows(x, x_rs, w, bias, xc, xc_rs, ntok, H, K, row_pos,
-                              reinterpret_cast<hipStream_t>(stream));
+  return conv_silu_fwd_rows(__func__, x, x_rs, w, bias, xc, xc_rs, ntok, H, K, row_pos, stream);
 }
 
 int rb_conv_silu_bwd(const float* x, int64_t x_rs, const float* w, const float* bias,
                      const float* g1, const float* g2, float* dx, int64_t dx_rs, float* dw_part,
-                     float* db_part, int64_t B, int64_t L, int64_t H, int64_t K, const int64_t* seq_offsets, void* stream) {
-  if (!x || !w || !bias || !g1 || !dx || !dw_part)   // db_part NULL: folded layout
-    return fail("rb_conv_silu_bwd: null pointer");
-  if (K < 1 || K > 8) return fail("rb_conv_silu_bwd: kernel size K must be in [1, 8]");
-  if (x_rs < H || dx_rs < H) return fail("rb_conv_silu_bwd: row stride < H");
-  if (int r = check_dims("rb_conv_silu_bwd", B, L, H, max4(x_rs, dx_rs, H))) return r;
-  return launch_conv_bwd(x, x_rs, w, bias, g1, g2, dx, dx_rs, dw_part, db_part, B, L, H, K,
-                         seq_offsets, reinterpret_cast<hipStream_t>(stream));
+                     float* db_part, int64_t B, int64_t L, int64_t H, int64_t K,
+                     const int64_t* seq_offsets, void* stream) {
+  return conv_silu_bwd(__func__, x, x_rs, w, bias, g1, g2, dx, dx_rs, dw_part, db_part, B, L, H,
+                       K, seq_offsets, stream);
 }
 
 int rb_gate_scan_fwd(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
                      const float* z, int64_t z_rs, const float* lam, const float* gate_b,
                      const float* h0, int64_t h0_bs, float* y, int64_t y_rs, float* carries,
                      int64_t B, int64_t L, int64_t H, const int64_t* seq_offsets, void* stream) {
-  if (!rg || !xc || !z || !lam || !y) return fail("rb_gate_scan_fwd: null pointer");
-  if (h0_bs != 0 && h0_bs < H) return fail("rb_gate_scan_fwd: h0 batch stride must be 0 or >= H");
-  if (rg_rs < 2 * H || xc_rs < H || z_rs < H || y_rs < H)
-    return fail("rb_gate_scan_fwd: row stride too small");
-  if (int r = check_dims("rb_gate_scan_fwd", B, L, H, max4(rg_rs, xc_rs, z_rs, y_rs))) return r;
-  return launch_gate_fwd(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, h0, h0_bs, y, y_rs, carries,
-                         B, L, H, seq_offsets, reinterpret_cast<hipStream_t>(stream));
+  return gate_scan_fwd(__func__, rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, h0, h0_bs, y, y_rs,
+                       carries, B, L, H, seq_offsets, stream);
+}
+
+int rb_gate_scan_bwd(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
+                     const float* z, int64_t z_rs, const float* lam, const float* gate_b,
+                     const float* carries, const float* dy, float* drg, int64_t drg_rs,
+                     float* dxc, int64_t dxc_rs, float* dz, int64_t dz_rs, float* part,
+                     float* dh0_part, int64_t B, int64_t L, int64_t H,
+                     const int64_t* seq_offsets, void* stream) {
+  return gate_scan_bwd(__func__, rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, carries, dy, drg,
+                       drg_rs, dxc, dxc_rs, dz, dz_rs, part, dh0_part, B, L, H, seq_offsets,
+                       stream);
 }
 
 int rb_gate_scan_fwd_last(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
@@ -148,38 +239,10 @@ int rb_gate_scan_fwd_last(const float* rg, int64_t rg_rs, const float* xc, int64
                           const float* h0, int64_t h0_bs, float* y_last, float* carries,
                           int64_t B, int64_t L, int64_t H, const int64_t* seq_offsets,
                           const int64_t* batch_row, void* stream) {
-  if (!rg || !xc || !z || !lam || !y_last) return fail("rb_gate_scan_fwd_last: null pointer");
-  if (h0_bs != 0 && h0_bs < H)
-    return fail("rb_gate_scan_fwd_last: h0 batch stride must be 0 or >= H");
-  if (rg_rs < 2 * H || xc_rs < H || z_rs < H)
-    return fail("rb_gate_scan_fwd_last: row stride too small");
-  if (int r = check_dims("rb_gate_scan_fwd_last", B, L, H, max4(rg_rs, xc_rs, z_rs, H))) return r;
-  return launch_gate_fwd(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, h0, h0_bs, nullptr, H,
-                         carries, B, L, H, seq_offsets, reinterpret_cast<hipStream_t>(stream),
-                         y_last, batch_row);
+  return gate_scan_fwd<float>(__func__, rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, h0, h0_bs,
+                              nullptr, H, carries, B, L, H, seq_offsets, stream, y_last,
+                              batch_row);
 }
-
-int rb_gate_scan_bwd(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
-                     const float* z, int64_t z_rs, const float* lam, const float* gate_b,
-                     const float* carries,
-                     const float* dy, float* drg, int64_t drg_rs, float* dxc, int64_t dxc_rs,
-                     float* dz, int64_t dz_rs, float* part, float* dh0_part, int64_t B,
-                     int64_t L, int64_t H, const int64_t* seq_offsets, void* stream) {
-  if (!rg || !xc || !z || !lam || !carries || !dy || !drg || !dxc || !dz || !part || !dh0_part)
-    return fail("rb_gate_scan_bwd: null pointer");
-  if (rg_rs < 2 * H || xc_rs < H || z_rs < H || drg_rs < 2 * H || dxc_rs < H || dz_rs < H)
-    return fail("rb_gate_scan_bwd: row stride too small");
-  if (int r = check_dims("rb_gate_scan_bwd", B, L, H,
-                         max4(max4(rg_rs, xc_rs, z_rs, drg_rs), dz_rs, dxc_rs, H)))
-    return r;
-  return launch_gate_bwd(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, carries, dy, drg, drg_rs, dxc,
-                         dxc_rs, dz, dz_rs, part, dh0_part, B, L, H,
-                         seq_offsets, reinterpret_cast<hipStream_t>(stream));
-}
-
-// ---- bf16 storage variants (fp32 arithmetic; same checks as the fp32 forms) ----
-#define BF(p) reinterpret_cast<const bf16_t*>(p)
-#define BFW(p) reinterpret_cast<bf16_t*>(p)
 
 int rb_gate_scan_bwd_last(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
                           const float* z, int64_t z_rs, const float* lam, const float* gate_b,
@@ -187,113 +250,66 @@ int rb_gate_scan_bwd_last(const float* rg, int64_t rg_rs, const float* xc, int64
                           int64_t drg_rs, float* dxc, int64_t dxc_rs, float* dz, int64_t dz_rs,
                           float* part, float* dh0_part, int64_t B, int64_t L, int64_t H,
                           const int64_t* seq_offsets, const int64_t* batch_row, void* stream) {
-  if (!rg || !xc || !z || !lam || !carries || !dy_last || !drg || !dxc || !dz || !part ||
-      !dh0_part)
-    return fail("rb_gate_scan_bwd_last: null pointer");
-  if (rg_rs < 2 * H || xc_rs < H || z_rs < H || drg_rs < 2 * H || dxc_rs < H || dz_rs < H)
-    return fail("rb_gate_scan_bwd_last: row stride too small");
-  if (int r = check_dims("rb_gate_scan_bwd_last", B, L, H,
-                         max4(max4(rg_rs, xc_rs, z_rs, drg_rs), dz_rs, dxc_rs, H)))
-    return r;
-  return launch_gate_bwd(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, carries, nullptr, drg,
-                         drg_rs, dxc, dxc_rs, dz, dz_rs, part, dh0_part, B, L, H, seq_offsets,
-                         reinterpret_cast<hipStream_t>(stream), dy_last, batch_row);
+  return gate_scan_bwd<float>(__func__, rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, carries,
+                              nullptr, drg, drg_rs, dxc, dxc_rs, dz, dz_rs, part, dh0_part, B, L,
+                              H, seq_offsets, stream, dy_last, batch_row);
 }
+
+// ---- bf16 storage variants (fp32 arithmetic; the same bodies as the fp32 forms) ----
 
 int rb_scan_fwd_bf16(const rb_bf16* gates, const rb_bf16* tokens, rb_bf16* states, int64_t B,
                      int64_t C, int64_t T, void* stream) {
-  if (!gates || !tokens || !states) return fail("rb_scan_fwd_bf16: null pointer");
-  if (B <= 0 || C <= 0 || T <= 0) return fail("rb_scan_fwd_bf16: B, C, T must be positive");
-  const int64_t rows = B * C;
-  if ((rows + 3) / 4 > 0x7fffffffLL) return fail("rb_scan_fwd_bf16: too many rows");
-  return launch_scan_fwd_bf16(BF(gates), BF(tokens), BFW(states), rows, T,
-                              reinterpret_cast<hipStream_t>(stream));
+  return scan_fwd(__func__, bf(gates), bf(tokens), bf(states), B, C, T, stream);
 }
 
 int rb_scan_bwd_bf16(const rb_bf16* gates, const rb_bf16* states, const rb_bf16* grad,
                      rb_bf16* d_gates, rb_bf16* d_tokens, int64_t B, int64_t C, int64_t T,
                      void* stream) {
-  if (!gates || !states || !grad || !d_gates || !d_tokens)
-    return fail("rb_scan_bwd_bf16: null pointer");
-  if (B <= 0 || C <= 0 || T <= 0) return fail("rb_scan_bwd_bf16: B, C, T must be positive");
-  const int64_t rows = B * C;
-  if ((rows + 3) / 4 > 0x7fffffffLL) return fail("rb_scan_bwd_bf16: too many rows");
-  return launch_scan_bwd_bf16(BF(gates), BF(states), BF(grad), BFW(d_gates), BFW(d_tokens), rows,
-                              T, reinterpret_cast<hipStream_t>(stream));
+  return scan_bwd(__func__, bf(gates), bf(states), bf(grad), bf(d_gates), bf(d_tokens), B, C, T,
+                  stream);
 }
 
 int rb_conv_silu_fwd_bf16(const rb_bf16* x, int64_t x_rs, const float* w, const float* bias,
                           rb_bf16* xc, int64_t xc_rs, int64_t B, int64_t L, int64_t H, int64_t K,
                           const int64_t* seq_offsets, void* stream) {
-  if (!x || !w || !bias || !xc) return fail("rb_conv_silu_fwd_bf16: null pointer");
-  if (K < 1 || K > 8) return fail("rb_conv_silu_fwd_bf16: kernel size K must be in [1, 8]");
-  if (x_rs < H || xc_rs < H) return fail("rb_conv_silu_fwd_bf16: row stride < H");
-  if (int r = check_dims("rb_conv_silu_fwd_bf16", B, L, H, max4(x_rs, xc_rs))) return r;
-  return launch_conv_fwd_bf16(BF(x), x_rs, w, bias, BFW(xc), xc_rs, B, L, H, K,
-                              seq_offsets, reinterpret_cast<hipStream_t>(stream));
+  return conv_silu_fwd(__func__, bf(x), x_rs, w, bias, bf(xc), xc_rs, B, L, H, K, seq_offsets,
+                       stream);
 }
 
 int rb_conv_silu_fwd_rows_bf16(const rb_bf16* x, int64_t x_rs, const float* w, const float* bias,
                                rb_bf16* xc, int64_t xc_rs, int64_t ntok, int64_t H, int64_t K,
                                const int64_t* row_pos, void* stream) {
-  if (!x || !w || !bias || !xc || !row_pos)
-    return fail("rb_conv_silu_fwd_rows_bf16: null pointer");
-  if (K < 1 || K > 8) return fail("rb_conv_silu_fwd_rows_bf16: kernel size K must be in [1, 8]");
-  if (x_rs < H || xc_rs < H) return fail("rb_conv_silu_fwd_rows_bf16: row stride < H");
-  if (int r = check_dims("rb_conv_silu_fwd_rows_bf16", ntok, 1, H, max4(x_rs, xc_rs))) return r;
-  return launch_conv_fwd_rows_bf16(BF(x), x_rs, w, bias, BFW(xc), xc_rs, ntok, H, K, row_pos,
-                                   reinterpret_cast<hipStream_t>(stream));
+  return conv_silu_fwd_rows(__func__, bf(x), x_rs, w, bias, bf(xc), xc_rs, ntok, H, K, row_pos,
+                            stream);
 }
 
 int rb_conv_silu_bwd_bf16(const rb_bf16* x, int64_t x_rs, const float* w, const float* bias,
                           const rb_bf16* g1, const rb_bf16* g2, rb_bf16* dx, int64_t dx_rs,
                           float* dw_part, float* db_part, int64_t B, int64_t L, int64_t H,
                           int64_t K, const int64_t* seq_offsets, void* stream) {
-  if (!x || !w || !bias || !g1 || !dx || !dw_part)   // db_part NULL: folded layout
-    return fail("rb_conv_silu_bwd_bf16: null pointer");
-  if (K < 1 || K > 8) return fail("rb_conv_silu_bwd_bf16: kernel size K must be in [1, 8]");
-  if (x_rs < H || dx_rs < H) return fail("rb_conv_silu_bwd_bf16: row stride < H");
-  if (int r = check_dims("rb_conv_silu_bwd_bf16", B, L, H, max4(x_rs, dx_rs, H))) return r;
-  return launch_conv_bwd_bf16(BF(x), x_rs, w, bias, BF(g1), g2 ? BF(g2) : nullptr, BFW(dx),
-                              dx_rs, dw_part, db_part, B, L, H, K,
-                              seq_offsets, reinterpret_cast<hipStream_t>(stream));
+  return conv_silu_bwd(__func__, bf(x), x_rs, w, bias, bf(g1), bf(g2), bf(dx), dx_rs, dw_part,
+                       db_part, B, L, H, K, seq_offsets, stream);
 }
 
 int rb_gate_scan_fwd_bf16(const rb_bf16* rg, int64_t rg_rs, const rb_bf16* xc, int64_t xc_rs,
                           const rb_bf16* z, int64_t z_rs, const float* lam, const float* gate_b,
                           const float* h0, int64_t h0_bs, rb_bf16* y, int64_t y_rs,
-                          float* carries, int64_t B, int64_t L, int64_t H, const int64_t* seq_offsets, void* stream) {
-  if (!rg || !xc || !z || !lam || !y) return fail("rb_gate_scan_fwd_bf16: null pointer");
-  if (h0_bs != 0 && h0_bs < H)
-    return fail("rb_gate_scan_fwd_bf16: h0 batch stride must be 0 or >= H");
-  if (rg_rs < 2 * H || xc_rs < H || z_rs < H || y_rs < H)
-    return fail("rb_gate_scan_fwd_bf16: row stride too small");
-  if (int r = check_dims("rb_gate_scan_fwd_bf16", B, L, H, max4(rg_rs, xc_rs, z_rs, y_rs)))
-    return r;
-  return launch_gate_fwd_bf16(BF(rg), rg_rs, BF(xc), xc_rs, BF(z), z_rs, lam, gate_b, h0, h0_bs,
-                              BFW(y), y_rs, carries, B, L, H,
-                              seq_offsets, reinterpret_cast<hipStream_t>(stream));
+                          float* carries, int64_t B, int64_t L, int64_t H,
+                          const int64_t* seq_offsets, void* stream) {
+  return gate_scan_fwd(__func__, bf(rg), rg_rs, bf(xc), xc_rs, bf(z), z_rs, lam, gate_b, h0,
+                       h0_bs, bf(y), y_rs, carries, B, L, H, seq_offsets, stream);
 }
 
 int rb_gate_scan_bwd_bf16(const rb_bf16* rg, int64_t rg_rs, const rb_bf16* xc, int64_t xc_rs,
                           const rb_bf16* z, int64_t z_rs, const float* lam, const float* gate_b,
                           const float* carries, const rb_bf16* dy, rb_bf16* drg, int64_t drg_rs,
                           rb_bf16* dxc, int64_t dxc_rs, rb_bf16* dz, int64_t dz_rs, float* part,
-                          float* dh0_part, int64_t B, int64_t L, int64_t H, const int64_t* seq_offsets, void* stream) {
-  if (!rg || !xc || !z || !lam || !carries || !dy || !drg || !dxc || !dz || !part || !dh0_part)
-    return fail("rb_gate_scan_bwd_bf16: null pointer");
-  if (rg_rs < 2 * H || xc_rs < H || z_rs < H || drg_rs < 2 * H || dxc_rs < H || dz_rs < H)
-    return fail("rb_gate_scan_bwd_bf16: row stride too small");
-  if (int r = check_dims("rb_gate_scan_bwd_bf16", B, L, H,
-                         max4(max4(rg_rs, xc_rs, z_rs, drg_rs), dz_rs, dxc_rs, H)))
-    return r;
-  return launch_gate_bwd_bf16(BF(rg), rg_rs, BF(xc), xc_rs, BF(z), z_rs, lam, gate_b, carries,
-                              BF(dy), BFW(drg), drg_rs, BFW(dxc), dxc_rs, BFW(dz), dz_rs, part,
-                              dh0_part, B, L, H, seq_offsets, reinterpret_cast<hipStream_t>(stream));
+                          float* dh0_part, int64_t B, int64_t L, int64_t H,
+                          const int64_t* seq_offsets, void* stream) {
+  return gate_scan_bwd(__func__, bf(rg), rg_rs, bf(xc), xc_rs, bf(z), z_rs, lam, gate_b, carries,
+                       bf(dy), bf(drg), drg_rs, bf(dxc), dxc_rs, bf(dz), dz_rs, part, dh0_part,
+                       B, L, H, seq_offsets, stream);
 }
-
-#undef BF
-#undef BFW
 
 int rb_add_ln_fwd(const float* a, const int64_t* idx, int64_t n_idx_rows, const uint8_t* mask,
                   uint64_t seed, float p, const float* r, const float* gamma, const float* beta,

@@ -327,49 +327,40 @@ DropSpec make_drop(const uint8_t* mask, uint64_t seed, float p);
 int launch_pack_plan(const int64_t* seq, int64_t seq_rs, const int64_t* offs,
                      const int64_t* order, int64_t B, int64_t* ids, int64_t* pos, int64_t* inv,
                      int64_t* last, hipStream_t st);
-int launch_conv_fwd(const float* x, int64_t x_rs, const float* w, const float* bias, float* xc,
-                    int64_t xc_rs, int64_t B, int64_t L, int64_t H, int64_t K, const int64_t* offs, hipStream_t st);
-int launch_conv_bwd(const float* x, int64_t x_rs, const float* w, const float* bias,
-                    const float* g1, const float* g2, float* dx, int64_t dx_rs, float* dw_part,
-                    float* db_part, int64_t B, int64_t L, int64_t H, int64_t K, const int64_t* offs, hipStream_t st);
-int launch_gate_fwd(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
-                    const float* z, int64_t z_rs, const float* lam, const float* gb,
-                    const float* h0, int64_t h0_bs, float* y, int64_t y_rs, float* carries,
-                    int64_t B, int64_t L, int64_t H, const int64_t* offs, hipStream_t st,
-                    float* y_last = nullptr, const int64_t* order = nullptr);
-int launch_gate_bwd(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
-                    const float* z, int64_t z_rs, const float* lam, const float* gb,
-                    const float* carries, const float* dy, float* drg, int64_t drg_rs, float* dxc,
-                    int64_t dxc_rs, float* dz, int64_t dz_rs, float* part, float* dh0_part,
-                    int64_t B, int64_t L, int64_t H, const int64_t* offs, hipStream_t st,
-                    const float* dy_last = nullptr, const int64_t* order = nullptr);
-int launch_scan_fwd_bf16(const bf16_t* gates, const bf16_t* tokens, bf16_t* states,
-                         int64_t rows, int64_t T, hipStream_t st);
-int launch_scan_bwd_bf16(const bf16_t* gates, const bf16_t* states, const bf16_t* grad,
-                         bf16_t* d_gates, bf16_t* d_tokens, int64_t rows, int64_t T,
+// the recurrence launchers exist for T = float and T = bf16_t activation
+// storage (explicit instantiations in scan_rows.hip, conv_silu.hip, gate_scan.hip)
+template <typename T>
+int launch_scan_fwd(const T* gates, const T* tokens, T* states, int64_t rows, int64_t steps,
+                    hipStream_t st);
+template <typename T>
+int launch_scan_bwd(const T* gates, const T* states, const T* grad, T* d_gates, T* d_tokens,
+                    int64_t rows, int64_t steps, hipStream_t st);
+template <typename T>
+int launch_conv_fwd(const T* x, int64_t x_rs, const float* w, const float* bias, T* xc,
+                    int64_t xc_rs, int64_t B, int64_t L, int64_t H, int64_t K,
+                    const int64_t* offs, hipStream_t st);
+template <typename T>
+int launch_conv_fwd_rows(const T* x, int64_t x_rs, const float* w, const float* bias, T* xc,
+                         int64_t xc_rs, int64_t ntok, int64_t H, int64_t K, const int64_t* pos,
                          hipStream_t st);
-int launch_conv_fwd_rows(const float* x, int64_t x_rs, const float* w, const float* bias,
-                         float* xc, int64_t xc_rs, int64_t ntok, int64_t H, int64_t K,
-                         const int64_t* pos, hipStream_t st);
-int launch_conv_fwd_rows_bf16(const bf16_t* x, int64_t x_rs, const float* w, const float* bias,
-                              bf16_t* xc, int64_t xc_rs, int64_t ntok, int64_t H, int64_t K,
-                              const int64_t* pos, hipStream_t st);
-int launch_conv_fwd_bf16(const bf16_t* x, int64_t x_rs, const float* w, const float* bias,
-                         bf16_t* xc, int64_t xc_rs, int64_t B, int64_t L, int64_t H, int64_t K,
-                         const int64_t* offs, hipStream_t st);
-int launch_conv_bwd_bf16(const bf16_t* x, int64_t x_rs, const float* w, const float* bias,
-                         const bf16_t* g1, const bf16_t* g2, bf16_t* dx, int64_t dx_rs,
-                         float* dw_part, float* db_part, int64_t B, int64_t L, int64_t H,
-                         int64_t K, const int64_t* offs, hipStream_t st);
-int launch_gate_fwd_bf16(const bf16_t* rg, int64_t rg_rs, const bf16_t* xc, int64_t xc_rs,
-                         const bf16_t* z, int64_t z_rs, const float* lam, const float* gb,
-                         const float* h0, int64_t h0_bs, bf16_t* y, int64_t y_rs, float* carries,
-                         int64_t B, int64_t L, int64_t H, const int64_t* offs, hipStream_t st);
-int launch_gate_bwd_bf16(const bf16_t* rg, int64_t rg_rs, const bf16_t* xc, int64_t xc_rs,
-                         const bf16_t* z, int64_t z_rs, const float* lam, const float* gb,
-                         const float* carries, const bf16_t* dy, bf16_t* drg, int64_t drg_rs,
-                         bf16_t* dxc, int64_t dxc_rs, bf16_t* dz, int64_t dz_rs, float* part,
-                         float* dh0_part, int64_t B, int64_t L, int64_t H, const int64_t* offs, hipStream_t st);
+template <typename T>
+int launch_conv_bwd(const T* x, int64_t x_rs, const float* w, const float* bias, const T* g1,
+                    const T* g2, T* dx, int64_t dx_rs, float* dw_part, float* db_part, int64_t B,
+                    int64_t L, int64_t H, int64_t K, const int64_t* offs, hipStream_t st);
+// y_last / dy_last [B, H] (rows permuted by order): rb_gate_scan_*_last
+template <typename T>
+int launch_gate_fwd(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* z,
+                    int64_t z_rs, const float* lam, const float* gb, const float* h0,
+                    int64_t h0_bs, T* y, int64_t y_rs, float* carries, int64_t B, int64_t L,
+                    int64_t H, const int64_t* offs, hipStream_t st, T* y_last = nullptr,
+                    const int64_t* order = nullptr);
+template <typename T>
+int launch_gate_bwd(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* z,
+                    int64_t z_rs, const float* lam, const float* gb, const float* carries,
+                    const T* dy, T* drg, int64_t drg_rs, T* dxc, int64_t dxc_rs, T* dz,
+                    int64_t dz_rs, float* part, float* dh0_part, int64_t B, int64_t L, int64_t H,
+                    const int64_t* offs, hipStream_t st, const T* dy_last = nullptr,
+                    const int64_t* order = nullptr);
 int launch_add_ln_fwd(const float* a, const int64_t* idx, int64_t nidx, const DropSpec& drop,
                       const float* r, const float* gamma, const float* beta, float eps, float* y,
                       float* s_out, float* mean, float* rstd, int64_t rows, int64_t d,
@@ -483,9 +474,5 @@ int launch_colsum(const float* in, int64_t M, int64_t P, int64_t C, int64_t rs, 
                   float* out, hipStream_t st);
 int launch_colsum_chunked(const float* in, int64_t M, int64_t P, int64_t C, int64_t rs, int CH,
                           float* part, unsigned* cnt, float* out, hipStream_t st);
-int launch_scan_fwd(const float* gates, const float* tokens, float* states, int64_t rows,
-                    int64_t T, hipStream_t st);
-int launch_scan_bwd(const float* gates, const float* states, const float* grad, float* d_gates,
-                    float* d_tokens, int64_t rows, int64_t T, hipStream_t st);
 
 }  // namespace rb

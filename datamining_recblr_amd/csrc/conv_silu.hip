@@ -424,9 +424,12 @@ bool al4(const void* p) {
   return p == nullptr || reinterpret_cast<uintptr_t>(p) % (4 * sizeof(T)) == 0;
 }
 
+}  // namespace
+
 template <typename T>
-int conv_fwd_k(const T* x, int64_t x_rs, const float* w, const float* bias, T* xc, int64_t xc_rs,
-               int64_t B, int64_t L, int64_t H, int64_t K, const int64_t* offs, hipStream_t st) {
+int launch_conv_fwd(const T* x, int64_t x_rs, const float* w, const float* bias, T* xc,
+                    int64_t xc_rs, int64_t B, int64_t L, int64_t H, int64_t K,
+                    const int64_t* offs, hipStream_t st) {
   const bool vec = H % 4 == 0 && x_rs % 4 == 0 && xc_rs % 4 == 0 && al4<T>(x) && al4<T>(xc) &&
                    aligned16(bias);
   // bf16 at K = 4: 8 channels (16 B) per lane, 8-step chunks (tools/kbench.hip: 6% faster
@@ -448,9 +451,9 @@ int conv_fwd_k(const T* x, int64_t x_rs, const float* w, const float* bias, T* x
 }
 
 template <typename T>
-int conv_fwd_rows_k(const T* x, int64_t x_rs, const float* w, const float* bias, T* xc,
-                    int64_t xc_rs, int64_t ntok, int64_t H, int64_t K, const int64_t* pos,
-                    hipStream_t st) {
+int launch_conv_fwd_rows(const T* x, int64_t x_rs, const float* w, const float* bias, T* xc,
+                         int64_t xc_rs, int64_t ntok, int64_t H, int64_t K, const int64_t* pos,
+                         hipStream_t st) {
   const bool vec = H % 4 == 0 && x_rs % 4 == 0 && xc_rs % 4 == 0 && al4<T>(x) && al4<T>(xc) &&
                    aligned16(bias);
   if (sizeof(T) == 2 && K == 4 && vec && H % 8 == 0 && x_rs % 8 == 0 && xc_rs % 8 == 0 &&
@@ -470,9 +473,9 @@ int conv_fwd_rows_k(const T* x, int64_t x_rs, const float* w, const float* bias,
 }
 
 template <typename T>
-int conv_bwd_k(const T* x, int64_t x_rs, const float* w, const float* bias, const T* g1,
-               const T* g2, T* dx, int64_t dx_rs, float* dw_part, float* db_part, int64_t B,
-               int64_t L, int64_t H, int64_t K, const int64_t* offs, hipStream_t st) {
+int launch_conv_bwd(const T* x, int64_t x_rs, const float* w, const float* bias, const T* g1,
+                    const T* g2, T* dx, int64_t dx_rs, float* dw_part, float* db_part, int64_t B,
+                    int64_t L, int64_t H, int64_t K, const int64_t* offs, hipStream_t st) {
   const bool vec = H % 4 == 0 && x_rs % 4 == 0 && dx_rs % 4 == 0 && al4<T>(x) && al4<T>(g1) &&
                    al4<T>(g2) && al4<T>(dx) && aligned16(dw_part) && aligned16(db_part) &&
                    aligned16(bias);
@@ -489,46 +492,12 @@ int conv_bwd_k(const T* x, int64_t x_rs, const float* w, const float* bias, cons
   }
 }
 
-}  // namespace
-
-int launch_conv_fwd(const float* x, int64_t x_rs, const float* w, const float* bias, float* xc,
-                    int64_t xc_rs, int64_t B, int64_t L, int64_t H, int64_t K,
-                    const int64_t* offs, hipStream_t st) {
-  return conv_fwd_k<float>(x, x_rs, w, bias, xc, xc_rs, B, L, H, K, offs, st);
-}
-
-int launch_conv_fwd_bf16(const bf16_t* x, int64_t x_rs, const float* w, const float* bias,
-                         bf16_t* xc, int64_t xc_rs, int64_t B, int64_t L, int64_t H, int64_t K,
-                         const int64_t* offs, hipStream_t st) {
-  return conv_fwd_k<bf16_t>(x, x_rs, w, bias, xc, xc_rs, B, L, H, K, offs, st);
-}
-
-int launch_conv_fwd_rows(const float* x, int64_t x_rs, const float* w, const float* bias,
-                         float* xc, int64_t xc_rs, int64_t ntok, int64_t H, int64_t K,
-                         const int64_t* pos, hipStream_t st) {
-  return conv_fwd_rows_k<float>(x, x_rs, w, bias, xc, xc_rs, ntok, H, K, pos, st);
-}
-
-int launch_conv_fwd_rows_bf16(const bf16_t* x, int64_t x_rs, const float* w, const float* bias,
-                              bf16_t* xc, int64_t xc_rs, int64_t ntok, int64_t H, int64_t K,
-                              const int64_t* pos, hipStream_t st) {
-  return conv_fwd_rows_k<bf16_t>(x, x_rs, w, bias, xc, xc_rs, ntok, H, K, pos, st);
-}
-
-int launch_conv_bwd(const float* x, int64_t x_rs, const float* w, const float* bias,
-                    const float* g1, const float* g2, float* dx, int64_t dx_rs, float* dw_part,
-                    float* db_part, int64_t B, int64_t L, int64_t H, int64_t K,
-                    const int64_t* offs, hipStream_t st) {
-  return conv_bwd_k<float>(x, x_rs, w, bias, g1, g2, dx, dx_rs, dw_part, db_part, B, L, H, K,
-                           offs, st);
-}
-
-int launch_conv_bwd_bf16(const bf16_t* x, int64_t x_rs, const float* w, const float* bias,
-                         const bf16_t* g1, const bf16_t* g2, bf16_t* dx, int64_t dx_rs,
-                         float* dw_part, float* db_part, int64_t B, int64_t L, int64_t H,
-                         int64_t K, const int64_t* offs, hipStream_t st) {
-  return conv_bwd_k<bf16_t>(x, x_rs, w, bias, g1, g2, dx, dx_rs, dw_part, db_part, B, L, H, K,
-                            offs, st);
-}
+// instantiated for the two storage types of the C ABI, with the signature declared in common.h
+template decltype(launch_conv_fwd<float>) launch_conv_fwd<float>;
+template decltype(launch_conv_fwd<bf16_t>) launch_conv_fwd<bf16_t>;
+template decltype(launch_conv_fwd_rows<float>) launch_conv_fwd_rows<float>;
+template decltype(launch_conv_fwd_rows<bf16_t>) launch_conv_fwd_rows<bf16_t>;
+template decltype(launch_conv_bwd<float>) launch_conv_bwd<float>;
+template decltype(launch_conv_bwd<bf16_t>) launch_conv_bwd<bf16_t>;
 
 }  // namespace rb

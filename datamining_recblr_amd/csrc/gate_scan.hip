@@ -614,13 +614,16 @@ int gate_bwd_v(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* 
   return launch_status("rb_gate_scan_bwd");
 }
 
+}  // namespace
+
 // widest vector the layout allows: fp32 fwd 2 / bwd 4 channels per lane
 // (8 / 16 B); bf16 4 / 4 channels (8 / 8 B)
 template <typename T>
-int gate_fwd_t(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* z,
-               int64_t z_rs, const float* lam, const float* gb, const float* h0, int64_t h0_bs,
-               T* y, int64_t y_rs, float* carries, int64_t B, int64_t L, int64_t H,
-               const int64_t* offs, hipStream_t st, T* y_last, const int64_t* order) {
+int launch_gate_fwd(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* z,
+                    int64_t z_rs, const float* lam, const float* gb, const float* h0,
+                    int64_t h0_bs, T* y, int64_t y_rs, float* carries, int64_t B, int64_t L,
+                    int64_t H, const int64_t* offs, hipStream_t st, T* y_last,
+                    const int64_t* order) {
   constexpr int VW = sizeof(T) == 2 ? 4 : 2;
   const auto strides = {rg_rs, xc_rs, z_rs, y_rs, h0_bs};
   const auto act = {(const void*)rg, (const void*)xc, (const void*)z, (const void*)y,
@@ -638,11 +641,12 @@ int gate_fwd_t(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* 
 }
 
 template <typename T>
-int gate_bwd_t(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* z,
-               int64_t z_rs, const float* lam, const float* gb, const float* carries,
-               const T* dy, T* drg, int64_t drg_rs, T* dxc, int64_t dxc_rs, T* dz, int64_t dz_rs,
-               float* part, float* dh0_part, int64_t B, int64_t L, int64_t H, const int64_t* offs,
-               hipStream_t st, const T* dy_last, const int64_t* order) {
+int launch_gate_bwd(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* z,
+                    int64_t z_rs, const float* lam, const float* gb, const float* carries,
+                    const T* dy, T* drg, int64_t drg_rs, T* dxc, int64_t dxc_rs, T* dz,
+                    int64_t dz_rs, float* part, float* dh0_part, int64_t B, int64_t L, int64_t H,
+                    const int64_t* offs, hipStream_t st, const T* dy_last,
+                    const int64_t* order) {
   constexpr int VW = 4;
   const auto strides = {rg_rs, xc_rs, z_rs, drg_rs, dxc_rs, dz_rs};
   const auto act = {(const void*)rg, (const void*)xc, (const void*)z, (const void*)dy,
@@ -672,43 +676,10 @@ int gate_bwd_t(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* 
                           dxc_rs, dz, dz_rs, part, dh0_part, B, L, H, offs, st, dy_last, order);
 }
 
-}  // namespace
-
-int launch_gate_fwd(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
-                    const float* z, int64_t z_rs, const float* lam, const float* gb,
-                    const float* h0, int64_t h0_bs, float* y, int64_t y_rs, float* carries,
-                    int64_t B, int64_t L, int64_t H, const int64_t* offs, hipStream_t st,
-                    float* y_last, const int64_t* order) {
-  return gate_fwd_t<float>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gb, h0, h0_bs, y, y_rs, carries,
-                           B, L, H, offs, st, y_last, order);
-}
-
-int launch_gate_fwd_bf16(const bf16_t* rg, int64_t rg_rs, const bf16_t* xc, int64_t xc_rs,
-                         const bf16_t* z, int64_t z_rs, const float* lam, const float* gb,
-                         const float* h0, int64_t h0_bs, bf16_t* y, int64_t y_rs, float* carries,
-                         int64_t B, int64_t L, int64_t H, const int64_t* offs, hipStream_t st) {
-  return gate_fwd_t<bf16_t>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gb, h0, h0_bs, y, y_rs, carries,
-                            B, L, H, offs, st, nullptr, nullptr);
-}
-
-int launch_gate_bwd(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
-                    const float* z, int64_t z_rs, const float* lam, const float* gb,
-                    const float* carries, const float* dy, float* drg, int64_t drg_rs, float* dxc,
-                    int64_t dxc_rs, float* dz, int64_t dz_rs, float* part, float* dh0_part,
-                    int64_t B, int64_t L, int64_t H, const int64_t* offs, hipStream_t st,
-                    const float* dy_last, const int64_t* order) {
-  return gate_bwd_t<float>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gb, carries, dy, drg, drg_rs, dxc,
-                           dxc_rs, dz, dz_rs, part, dh0_part, B, L, H, offs, st, dy_last, order);
-}
-
-int launch_gate_bwd_bf16(const bf16_t* rg, int64_t rg_rs, const bf16_t* xc, int64_t xc_rs,
-                         const bf16_t* z, int64_t z_rs, const float* lam, const float* gb,
-                         const float* carries, const bf16_t* dy, bf16_t* drg, int64_t drg_rs,
-                         bf16_t* dxc, int64_t dxc_rs, bf16_t* dz, int64_t dz_rs, float* part,
-                         float* dh0_part, int64_t B, int64_t L, int64_t H, const int64_t* offs,
-                         hipStream_t st) {
-  return gate_bwd_t<bf16_t>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gb, carries, dy, drg, drg_rs,
-                            dxc, dxc_rs, dz, dz_rs, part, dh0_part, B, L, H, offs, st, nullptr, nullptr);
-}
+// instantiated for the two storage types of the C ABI, with the signature declared in common.h
+template decltype(launch_gate_fwd<float>) launch_gate_fwd<float>;
+template decltype(launch_gate_fwd<bf16_t>) launch_gate_fwd<bf16_t>;
+template decltype(launch_gate_bwd<float>) launch_gate_bwd<float>;
+template decltype(launch_gate_bwd<bf16_t>) launch_gate_bwd<bf16_t>;
 
 }  // namespace rb

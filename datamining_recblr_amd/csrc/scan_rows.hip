@@ -183,9 +183,11 @@ k_scan_rows_bwd(const TS* __restrict__ gates, const TS* __restrict__ states,
 template <typename TS>
 bool al4s(const void* p) { return reinterpret_cast<uintptr_t>(p) % (4 * sizeof(TS)) == 0; }
 
+}  // namespace
+
 template <typename TS>
-int scan_fwd_t(const TS* gates, const TS* tokens, TS* states, int64_t rows, int64_t T,
-               hipStream_t st) {
+int launch_scan_fwd(const TS* gates, const TS* tokens, TS* states, int64_t rows, int64_t T,
+                    hipStream_t st) {
   const int64_t blocks = (rows + 3) / 4;
   const bool vec = (T % 4 == 0) && al4s<TS>(gates) && al4s<TS>(tokens) && al4s<TS>(states);
   if (vec)
@@ -198,8 +200,8 @@ int scan_fwd_t(const TS* gates, const TS* tokens, TS* states, int64_t rows, int6
 }
 
 template <typename TS>
-int scan_bwd_t(const TS* gates, const TS* states, const TS* grad, TS* d_gates, TS* d_tokens,
-               int64_t rows, int64_t T, hipStream_t st) {
+int launch_scan_bwd(const TS* gates, const TS* states, const TS* grad, TS* d_gates,
+                    TS* d_tokens, int64_t rows, int64_t T, hipStream_t st) {
   const int64_t blocks = (rows + 3) / 4;
   const bool vec = (T % 4 == 0) && al4s<TS>(gates) && al4s<TS>(states) && al4s<TS>(grad) &&
                    al4s<TS>(d_gates) && al4s<TS>(d_tokens);
@@ -212,27 +214,10 @@ int scan_bwd_t(const TS* gates, const TS* states, const TS* grad, TS* d_gates, T
   return launch_status("rb_scan_bwd");
 }
 
-}  // namespace
-
-int launch_scan_fwd(const float* gates, const float* tokens, float* states, int64_t rows,
-                    int64_t T, hipStream_t st) {
-  return scan_fwd_t<float>(gates, tokens, states, rows, T, st);
-}
-
-int launch_scan_fwd_bf16(const bf16_t* gates, const bf16_t* tokens, bf16_t* states,
-                         int64_t rows, int64_t T, hipStream_t st) {
-  return scan_fwd_t<bf16_t>(gates, tokens, states, rows, T, st);
-}
-
-int launch_scan_bwd(const float* gates, const float* states, const float* grad, float* d_gates,
-                    float* d_tokens, int64_t rows, int64_t T, hipStream_t st) {
-  return scan_bwd_t<float>(gates, states, grad, d_gates, d_tokens, rows, T, st);
-}
-
-int launch_scan_bwd_bf16(const bf16_t* gates, const bf16_t* states, const bf16_t* grad,
-                         bf16_t* d_gates, bf16_t* d_tokens, int64_t rows, int64_t T,
-                         hipStream_t st) {
-  return scan_bwd_t<bf16_t>(gates, states, grad, d_gates, d_tokens, rows, T, st);
-}
+// instantiated for the two storage types of the C ABI, with the signature declared in common.h
+template decltype(launch_scan_fwd<float>) launch_scan_fwd<float>;
+template decltype(launch_scan_fwd<bf16_t>) launch_scan_fwd<bf16_t>;
+template decltype(launch_scan_bwd<float>) launch_scan_bwd<float>;
+template decltype(launch_scan_bwd<bf16_t>) launch_scan_bwd<bf16_t>;
 
 }  // namespace rb

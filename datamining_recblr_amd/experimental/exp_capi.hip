@@ -58,15 +58,12 @@ int launch_grl_bwd(const float* xz, int64_t xz_rs, const float* conv_w, int KC,
 
 using namespace rb;
 
-namespace {
-constexpr int RB_EXP_ABI = 45;   // = the product library's rb_version() it pairs with
-}  // namespace
-
 extern "C" {
 
 #define RB_EXPORT __attribute__((visibility("default")))
 
-RB_EXPORT int rb_exp_version(void) { return RB_EXP_ABI; }
+// the product library's rb_version() it pairs with
+RB_EXPORT int rb_exp_version(void) { return RB_ABI_VERSION; }
 
 RB_EXPORT const char* rb_exp_last_error_string(void) { return g_exp_error.c_str(); }
 

@@ -41,6 +41,14 @@
  * the recurrence is causal, so positions past a sequence's length never reach
  * RecBLR.forward's output (gather_indexes at len - 1, RecBLR.py:84).
  * seq_offsets = NULL: the dense layout above.
+ *
+ * This header is the only statement of the prototypes and constants: the
+ * Python binding (datamining_recblr_amd/_lib.py) parses it, as it does
+ * experimental/recblr_exp.h and probes/recblr_probe.h.  So it stays plain C
+ * declarations, one per ';'; by value only int, int64_t, uint64_t, float and
+ * double (everything else through a pointer); returns of those types or
+ * const char*; integer constants as one-line #defines.  A new entry point is
+ * declared here and defined in csrc/capi.hip, and RB_ABI_VERSION is bumped.
  */
 #ifndef RECBLR_HIP_H
 #define RECBLR_HIP_H
@@ -63,7 +71,8 @@ typedef uint16_t rb_bf16;
  * floats. */
 #define RB_TILE 16
 
-/* ABI version; bumped on any signature change. */
+/* ABI version; bumped on any signature change.  rb_version() returns it. */
+#define RB_ABI_VERSION 45
 int rb_version(void);
 
 /* Human-readable description of the last error on the calling thread. */

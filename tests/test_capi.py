@@ -1,9 +1,16 @@
 """The C-ABI library loads on a CPU-only host and exports exactly what
-include/recblr_hip.h declares (no compute call is made here)."""
+include/recblr_hip.h declares (no compute call is made here), and the ctypes
+prototypes derived from the headers are what the headers say."""
 import ctypes
+import os
 import re
 
+import pytest
+
 from datamining_recblr_amd import _lib
+
+_i64, _p, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
+_f32, _f64, _u64 = ctypes.c_float, ctypes.c_double, ctypes.c_uint64
 
 
 def header_functions():
@@ -16,6 +23,8 @@ def test_header_declares_expected_entry_points():
     names = header_functions()
     assert len(names) == len(set(names))
     assert set(names) == set(_lib.SIGNATURES), set(names) ^ set(_lib.SIGNATURES)
+    assert list(_lib.SIGNATURES) == names          # header order
+    assert (len(_lib.SIGNATURES), len(_lib.EXP_SIGNATURES), len(_lib.PROBE_SIGNATURES)) == (63, 4, 3)
     for must in ("rb_scan_fwd", "rb_scan_bwd", "rb_conv_silu_fwd", "rb_conv_silu_bwd",
                  "rb_gate_scan_fwd", "rb_gate_scan_bwd", "rb_version", "rb_last_error_string"):
         assert must in names
@@ -34,6 +43,72 @@ def test_tile_constant_matches_header():
     text = open(_lib.HEADER_PATH).read()
     assert re.search(r"#define RB_TILE (\d+)", text).group(1) == str(_lib.RB_TILE)
     assert re.search(r"#define RB_EINVAL \((-?\d+)\)", text).group(1) == str(_lib.RB_EINVAL)
+    # Python code sizes buffers and reads statuses with these
+    assert _lib.RB_TILE == 16 and _lib.RB_EINVAL == -1
+    assert re.search(r"#define RB_ABI_VERSION (\d+)", text).group(1) == str(_lib.ABI_VERSION)
+
+
+# prototypes written out by hand, one of each kind of argument and return
+PINNED = {
+    "rb_scan_fwd": (_int, [_p, _p, _p, _i64, _i64, _i64, _p]),
+    "rb_add_ln_fwd": (_int, [_p, _p, _i64, _p, _u64, _f32, _p, _p, _p, _f32, _p, _p, _p, _p, _i64,
+                             _i64, _p]),
+    "rb_adam_step": (_int, [_p, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _f64, _p]),
+    "rb_pad_prefix_bwd": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p,
+                                 _int, _p]),
+    "rb_gemm_nt_h_mode": (_int, [_int]),
+    "rb_row_num_parts": (_i64, [_i64, _i64]),
+    "rb_last_error_string": (ctypes.c_char_p, []),
+    "rb_item_topk": (_int, [_p, _p, _i64, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p]),
+    "rb_grl_fwd": (_int, [_p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _p,
+                          _i64, _p, _p, _p, _p, _i64, _p, _p, _i64, _p]),
+    "rb_probe_gemm_pattern": (_int, [_p, _i64, _i64, _p, _i64, _p]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(PINNED))
+def test_derived_prototype_equals_pinned(name):
+    table = (_lib.EXP_SIGNATURES if name == "rb_grl_fwd" else
+             _lib.PROBE_SIGNATURES if name.startswith("rb_probe") else _lib.SIGNATURES)
+    assert table[name] == PINNED[name]
+    assert name != "rb_grl_fwd" or len(table[name][1]) == 25
+
+
+@pytest.mark.parametrize("decl", ["int rb_x(long n);", "int rb_x(short n);",
+                                  "int rb_x(rb_t job);", "int rb_x(struct rb_s job);",
+                                  "int rb_x(int (*cb)(int));", "long rb_x(void);",
+                                  "void rb_x(void);", "int rb_x(unsigned n);"])
+def test_parser_rejects_what_it_cannot_type(decl):
+    with pytest.raises(_lib.RecBLRNativeError, match="rb_x"):
+        _lib.parse_header(decl)
+
+
+def test_parser_skips_comments_typedefs_and_preprocessor_lines():
+    text = """
+    /* int rb_in_block_comment(void); calls rb_last_error_string() */
+    // int rb_in_line_comment(void);
+    #ifdef __cplusplus
+    extern "C" {
+    #endif
+    #define RB_N 3
+    typedef uint16_t rb_half;
+    typedef struct { int64_t n; } rb_t;
+    typedef struct {
+      float* p;   /* int rb_in_struct(void); */
+      int64_t n;
+    } rb_u;
+    const char* rb_msg(void);
+    int64_t rb_f(const rb_u* jobs, int n, uint64_t seed, float p,
+                 double lr, void* stream);
+    #ifdef __cplusplus
+    }
+    #endif
+    """
+    assert _lib.parse_header(text) == {
+        "rb_msg": (ctypes.c_char_p, []),
+        "rb_f": (_i64, [_p, _int, _u64, _f32, _f64, _p]),
+    }
+    assert _lib.parse_header("typedef struct { int64_t n; } rb_t;") == {}
 
 
 def test_argument_errors_are_reported_without_touching_the_gpu():
@@ -47,6 +122,72 @@ def test_argument_errors_are_reported_without_touching_the_gpu():
     assert b"K must be" in lib.rb_last_error_string()
     rc = lib.rb_gate_scan_fwd(1, 3, 1, 4, 1, 4, 1, 0, 0, 0, 1, 4, 1, 1, 1, 4, None, None)
     assert rc == _lib.RB_EINVAL   # rg row stride < 2H
+
+
+# The seven recurrence entry points exist for fp32 and bf16 storage and share
+# their checks: argument lists that pass every check (H = 4; non-null pointers
+# are fake and never dereferenced), then one bad value each.
+_P = 16
+TWINS = {
+    "rb_scan_fwd": dict(gates=_P, tokens=_P, states=_P, B=1, C=1, T=4, stream=None),
+    "rb_scan_bwd": dict(gates=_P, states=_P, grad=_P, d_gates=_P, d_tokens=_P, B=1, C=1, T=4,
+                        stream=None),
+    "rb_conv_silu_fwd": dict(x=_P, x_rs=4, w=_P, bias=_P, xc=_P, xc_rs=4, B=1, L=1, H=4, K=4,
+                             seq_offsets=None, stream=None),
+    "rb_conv_silu_fwd_rows": dict(x=_P, x_rs=4, w=_P, bias=_P, xc=_P, xc_rs=4, B=8, H=4, K=4,
+                                  row_pos=_P, stream=None),          # B: ntok
+    "rb_conv_silu_bwd": dict(x=_P, x_rs=4, w=_P, bias=_P, g1=_P, g2=_P, dx=_P, dx_rs=4,
+                             dw_part=_P, db_part=_P, B=1, L=1, H=4, K=4, seq_offsets=None,
+                             stream=None),
+    "rb_gate_scan_fwd": dict(rg=_P, rg_rs=8, xc=_P, xc_rs=4, z=_P, z_rs=4, lam=_P, gate_b=None,
+                             h0=None, h0_bs=0, y=_P, y_rs=4, carries=_P, B=1, L=1, H=4,
+                             seq_offsets=None, stream=None),
+    "rb_gate_scan_bwd": dict(rg=_P, rg_rs=8, xc=_P, xc_rs=4, z=_P, z_rs=4, lam=_P, gate_b=None,
+                             carries=_P, dy=_P, drg=_P, drg_rs=8, dxc=_P, dxc_rs=4, dz=_P,
+                             dz_rs=4, part=_P, dh0_part=_P, B=1, L=1, H=4, seq_offsets=None,
+                             stream=None),
+}
+_CONV = ("rb_conv_silu_fwd", "rb_conv_silu_fwd_rows", "rb_conv_silu_bwd")
+_GATE = ("rb_gate_scan_fwd", "rb_gate_scan_bwd")
+TWIN_CASES = (
+    # a required pointer is null: the first, and the last one each check names
+    [(fn, {next(iter(TWINS[fn])): None}, "null pointer") for fn in TWINS]
+    + [("rb_scan_fwd", {"states": None}, "null pointer"),
+       ("rb_scan_bwd", {"d_tokens": None}, "null pointer"),
+       ("rb_conv_silu_fwd", {"xc": None}, "null pointer"),
+       ("rb_conv_silu_fwd_rows", {"row_pos": None}, "null pointer"),
+       ("rb_conv_silu_bwd", {"dw_part": None}, "null pointer"),
+       ("rb_gate_scan_fwd", {"y": None}, "null pointer"),
+       ("rb_gate_scan_bwd", {"dh0_part": None}, "null pointer")]
+    + [(fn, {"K": k}, "kernel size K must be in [1, 8]") for fn in _CONV for k in (9, 0)]
+    + [(fn, {"x_rs": 3}, "row stride < H") for fn in _CONV]
+    + [(fn, {"rg_rs": 7}, "row stride too small") for fn in _GATE]      # rg holds 2H columns
+    + [(fn, {"z_rs": 3}, "row stride too small") for fn in _GATE]
+    + [(fn, {"B": 0}, "B, C, T must be positive") for fn in ("rb_scan_fwd", "rb_scan_bwd")]
+    + [(fn, {"B": 0}, "B, L and H must be positive") for fn in _CONV + _GATE]
+    + [("rb_gate_scan_fwd", {"h0": _P, "h0_bs": 1}, "h0 batch stride must be 0 or >= H")]
+)
+
+
+@pytest.mark.parametrize("fn,bad,what", TWIN_CASES,
+                         ids=[f"{fn}-{'-'.join(f'{k}={v}' for k, v in bad.items())}"
+                              for fn, bad, _ in TWIN_CASES])
+def test_fp32_and_bf16_twins_reject_the_same_arguments(fn, bad, what):
+    """Each recurrence entry point and its _bf16 twin fail the same check,
+    before any launch (RB_EINVAL; a launch returns 0 or a positive hipError),
+    with the same message behind their own name."""
+    lib = _lib.load()
+    assert set(bad) <= set(TWINS[fn])
+    args = list({**TWINS[fn], **bad}.values())
+    messages = []
+    for name in (fn, fn + "_bf16"):
+        assert len(args) == len(_lib.SIGNATURES[name][1])
+        assert getattr(lib, name)(*args) == _lib.RB_EINVAL, name
+        messages.append(lib.rb_last_error_string().decode())
+    # the shape checks shared by the conv and gate entry points carry no name
+    prefix = "" if what.startswith("B, L and H") else fn + ": "
+    assert messages[0] == prefix + what
+    assert messages[1] == (fn + "_bf16: " if prefix else "") + what
 
 
 def test_row_conv_and_batched_split_argument_errors():
@@ -89,11 +230,11 @@ def test_probe_library_is_separate_and_exports_its_header():
     """bench.py's measurement aids live in their own library
     (probes/recblr_probe.h, lib/libdmrecblr_probe.so): the product library
     exports none of them, the probe library exports exactly its header's."""
-    import os
     hdr = os.path.join(os.path.dirname(_lib.__file__), "probes", "recblr_probe.h")
     text = re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)
     names = re.findall(r"\b(rb_[a-z0-9_]+)\s*\(", text)
-    assert set(names) == set(_lib.PROBE_SIGNATURES) | {"rb_probe_last_error_string"}
+    assert set(names) == set(_lib.PROBE_SIGNATURES)
+    assert _lib.PROBE_SIGNATURES["rb_probe_last_error_string"] == (ctypes.c_char_p, [])
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for n in names:
         assert not hasattr(raw, n), n
@@ -127,7 +268,6 @@ def test_experimental_library_is_separate_and_exports_its_header():
     the product library exports none of them, the experimental library
     exactly its header's, at the product's ABI version; argument errors are
     reported without touching the GPU."""
-    import os
     hdr = os.path.join(os.path.dirname(_lib.__file__), "experimental", "recblr_exp.h")
     text = re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)
     names = re.findall(r"\b(rb_[a-z0-9_]+)\s*\(", text)
@@ -136,7 +276,7 @@ def test_experimental_library_is_separate_and_exports_its_header():
     for n in names:
         assert not hasattr(raw, n), n
     exp = _lib.load_exp()
-    assert exp.rb_exp_version() == _lib.ABI_VERSION
+    assert _lib.ABI_VERSION == _lib.load().rb_version() == exp.rb_exp_version()
     try:
         _lib.call_exp("rb_grl_fwd", *[0 if t is ctypes.c_int64 else None
                                       for t in _lib.EXP_SIGNATURES["rb_grl_fwd"][1]])
