@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 
 #include "../../include/recblr_hip.h"
 
@@ -20,6 +21,19 @@ int launch_status(const char* what);
 int num_cus();
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---- run-time values as template arguments (host) ----------------------------
+// f(std::true_type{}) or f(std::false_type{})
+template <class F>
+auto dispatch_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+// f(std::integral_constant<int, V>{}) for the V among Vs that equals v;
+// false when none does
+template <int... Vs, class F>
+bool dispatch_int(int v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
 
 // ---- scalar math, following torch's definitions ------------------------------
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -389,6 +403,20 @@ int launch_gemm_tn_h(const float* Y, int64_t ldy, const float* X, int64_t ldx, i
 __host__ __device__ inline int64_t ws_image_offset(int64_t C, int64_t K) {
   return C * K * 4 + ((C * 4 + 15) / 16) * 16;
 }
+// The parts of an f16 weight image Wf of Bm [C, R] (rb_gemm_h_weight_bytes):
+// the persistent kernel's planes, the column exponents, the weight-stationary
+// kernel's planes.
+struct WeightImage {
+  const void* wf;
+  const int* ew;
+  const void* wi;
+};
+inline WeightImage weight_image(const void* Wf, int64_t C, int64_t R) {
+  const char* base = static_cast<const char*>(Wf);
+  return {Wf, reinterpret_cast<const int*>(base + C * R * 4), base + ws_image_offset(C, R)};
+}
+// zeroes dpart's rows [used, n_parts) (both rb_gemm_nt_h_dact kernels)
+int nt_dact_zero_rest(float* dpart, int64_t used, int64_t n_parts, int C, hipStream_t st);
 bool nt_ws_ok(int64_t M, int K, int C, const float* A, int64_t lda, const float* out, int64_t ldo);
 int launch_gemm_nt_ws(const float* A, int64_t lda, int64_t M, int K, const void* Wf, int C,
                       const float* bias, float* out, int64_t ldo, float* rmax, hipStream_t st);

@@ -45,6 +45,7 @@
 //   lane offset, tile coordinates advance incrementally (divisions once per
 //   tile), and the overflow check is one compare + ballot per k16.
 #include "common.h"
+#include "nt_plan.h"
 
 #include <type_traits>
 
@@ -1365,22 +1366,39 @@ void run_nt_h(const float* A, int64_t lda, int64_t M, int R, const f16x8* wf, co
 }
 
 
-// One phase of a call: the rows [r0, r0 + M) on tiles nbcols columns wide.
-NtPhase nt_phase(const float* A, int64_t lda, int64_t r0, int64_t M, float* out, int64_t ldo,
-                 float* rmax, int C, int nbcols, int G0, float* act = nullptr,
-                 const float* pre = nullptr, float* dpart = nullptr) {
+// A call's operands (act: ACT's second output; pre, dpart: DACT's).
+struct NtArgs {
+  const float* A;
+  int64_t lda, M;
+  int R;
+  const void* Wf;
+  int C;
+  const float* bias;
+  float* out;
+  int64_t ldo;
+  float* rmax;
+  float* act;
+  const float* pre;
+  float* dpart;
+  DropSpec drop;
+  hipStream_t st;
+};
+
+// One phase of a call: the rows [r0, r0 + M), sized by the plan; its
+// workgroups' column sums (DACT) from dpart's row dpart_row on.
+NtPhase nt_phase(const NtArgs& a, int64_t r0, int64_t M, int m_tiles, int grid,
+                 int64_t dpart_row) {
   NtPhase p{};
-  p.A = A + r0 * lda;
+  p.A = a.A + r0 * a.lda;
   p.M = M;
-  p.out = out + r0 * ldo;
-  p.rmax = rmax ? rmax + r0 / 32 : nullptr;
-  p.act = act ? act + r0 * ldo : nullptr;
-  p.pre = pre ? pre + r0 * ldo : nullptr;
-  p.dpart = dpart;
-  p.e_base = r0 * C;
-  p.m_tiles = (int)((M + N_BM - 1) / N_BM);
-  const int64_t nt = (int64_t)((p.m_tiles + 7) / 8) * 8 * (C / nbcols);
-  p.grid = M > 0 ? (int)std::min<int64_t>(nt, (int64_t)G0) : 0;
+  p.out = a.out + r0 * a.ldo;
+  p.rmax = a.rmax ? a.rmax + r0 / 32 : nullptr;
+  p.act = a.act ? a.act + r0 * a.ldo : nullptr;
+  p.pre = a.pre ? a.pre + r0 * a.ldo : nullptr;
+  p.dpart = a.dpart ? a.dpart + dpart_row * a.C : nullptr;
+  p.e_base = r0 * a.C;
+  p.m_tiles = m_tiles;
+  p.grid = grid;
   return p;
 }
 
@@ -1399,6 +1417,41 @@ void run_nt_h2(int64_t lda, int R, const f16x8* wf, const int* ew, int C, const 
   const unsigned grid = (unsigned)std::max(mp.grid, tp.grid);
   k_gemm_nt_h2<BIAS, NB, ACT, DACT><<<grid, N_THREADS, lds, st>>>(lda, R, wf, ew, C, bias, ldo,
                                                                   drop, mp, tp);
+}
+
+// The launches a plan names (nt_plan.h), in stream order.  BIAS, WIDE and NB
+// are the main kernel's arguments; the 256 x 64 tiles are always wide.
+template <bool BIAS, bool WIDE, int NB, bool ACT = false, bool DACT = false>
+int run_nt_plan(const char* what, const NtPlan& p, const NtArgs& a) {
+  const WeightImage w = weight_image(a.Wf, a.C, a.R);
+  const f16x8* wf = (const f16x8*)w.wf;
+  const NtPhase mp = nt_phase(a, 0, p.M_main, p.m_tiles, p.grid, 0);
+  const NtPhase tp = nt_phase(a, p.M_main, a.M - p.M_main, p.m_tiles_t, p.grid_t, p.dpart_tail);
+  auto launch = [&](auto wide_c, auto nb_c, const NtPhase& ph) {
+    run_nt_h<BIAS, decltype(wide_c)::value, decltype(nb_c)::value, ACT, DACT>(
+        ph.A, a.lda, ph.M, a.R, wf, w.ew, a.C, a.bias, ph.out, a.ldo, ph.rmax, ph.m_tiles,
+        (unsigned)ph.grid, a.st, ph.act, a.drop, ph.e_base, ph.pre, ph.dpart);
+    return launch_status(what);
+  };
+  switch (p.path) {
+    case NtPath::error:
+      return fail(p.err);
+    case NtPath::both:
+      run_nt_h2<BIAS, NB, ACT, DACT>(a.lda, a.R, wf, w.ew, a.C, a.bias, a.ldo, a.drop, mp, tp, a.st);
+      return launch_status(what);
+    case NtPath::tail:
+      return launch(std::true_type{}, std::integral_constant<int, 2>{}, tp);
+    case NtPath::few:        // (plain only: the fused entries refuse these shapes)
+    case NtPath::few_main: {
+      const int rc = launch_gemm_nt_hs(tp.A, a.lda, tp.M, a.R, a.Wf, a.C, a.bias, tp.out, a.ldo,
+                                       tp.rmax, a.st);
+      if (rc || p.path == NtPath::few) return rc;
+      break;
+    }
+    case NtPath::main:
+      break;
+  }
+  return launch(std::bool_constant<WIDE>{}, std::integral_constant<int, NB>{}, mp);
 }
 
 }  // namespace
@@ -1435,147 +1488,56 @@ int gemm_nt_h_mode(int mode) {
   return prev;
 }
 
+static_assert(NT_WAVES == N_WAVES && NT_BM == N_BM && NT_MAXC == N_MAXC &&
+              NT_DACT_MAXC == N_DACT_MAXC, "nt_plan.h sizes the kernels' tiles");
+
+// The three entries: the weight-stationary kernel's calls first, then the
+// plan of the persistent launches (nt_plan.h: the row split, the kernels'
+// arguments, what each entry refuses) and its launches (run_nt_plan).
 int launch_gemm_nt_h(const float* A, int64_t lda, int64_t M, int R, const void* Wf, int C,
                      const float* bias, float* out, int64_t ldo, int accumulate, float* rmax,
                      hipStream_t st) {
   (void)accumulate;  // rejected by rb_gemm_nt_h
   if (g_nt_mode == 1 && M >= NT_WS_MIN_ROWS && nt_ws_ok(M, R, C, A, lda, out, ldo))
     return launch_gemm_nt_ws(A, lda, M, R, Wf, C, bias, out, ldo, rmax, st);
-  const bool wide = (reinterpret_cast<uintptr_t>(out) & 15) == 0 && ldo % 4 == 0;
-  const bool nb8 = wide && C % 256 == 0;
-  // The persistent grid runs whole rounds of G tiles; the rows past the last
-  // whole round would run on a fraction of the chip (800 row tiles on 256
-  // CUs: a fourth round on 32 of them, +18% time for +4% rows), so they run
-  // as a second launch of 256 x 64 tiles (2-4x as many, each a fraction of
-  // the time).  Below one round, or for C % 128 != 0, every row goes to that
-  // launch, or to the few-rows kernel (gemm_small.hip) for the few-thousand-
-  // row shapes it wins, or for C % 64 != 0.
-  const int G0 = num_cus() / 8 * 8 * (8 / N_WAVES);
-  // (the few-rows kernel holds R <= 1024; beyond, the persistent kernel takes
-  // every row, a partial round included)
-  const int nct0 = C % 128 ? 0 : C / (nb8 ? 256 : 128);
-  if (R > 1024 && nct0 == 0) return fail("rb_gemm_nt_h: C % 128 != 0 needs R <= 1024");
-  const int64_t rows_round = nct0 ? (int64_t)(G0 / nct0) * N_BM : 0;
-  int64_t M_main = R > 1024 ? M
-                 : (nct0 && G0 % nct0 == 0 && rows_round > 0) ? M / rows_round * rows_round
-                                                              : (nct0 ? M : 0);
-  const f16x8* wf = (const f16x8*)Wf;
-  const int* ew = reinterpret_cast<const int*>(reinterpret_cast<const char*>(Wf) + (int64_t)C * R * 4);
-  if (M_main < M) {
-    // a partial round of 256 x 64 tiles: 4x (2x) the 256 x 256 (256 x 128)
-    // tiles of the main launch, each a quarter (half) of their time
-    // below one round: the few-rows kernel only where it measured faster
-    // (a few thousand rows with K = 512, or C = 128; tools/gemmbench_h.hip,
-    // profiles/r03_gemmbench_small_m.log) — at 8,192 rows it is 2.7x slower
-    const bool few = M_main == 0 && M <= 4096 && (R > 256 || C < 256);
-    if (!few && wide && C % 64 == 0 && M_main > 0) {
-      // both phases in one launch (k_gemm_nt_h2)
-      const int G0w = num_cus() / 8 * 8 * (8 / N_WAVES);
-      const NtPhase mp = nt_phase(A, lda, 0, M_main, out, ldo, rmax, C, nb8 ? 256 : 128, G0w);
-      const NtPhase tp = nt_phase(A, lda, M_main, M - M_main, out, ldo, rmax, C, 64, G0w);
-      if (bias) {
-        if (nb8) run_nt_h2<true, 8>(lda, R, wf, ew, C, bias, ldo, DropSpec{}, mp, tp, st);
-        else run_nt_h2<true, 4>(lda, R, wf, ew, C, bias, ldo, DropSpec{}, mp, tp, st);
-      } else {
-        if (nb8) run_nt_h2<false, 8>(lda, R, wf, ew, C, bias, ldo, DropSpec{}, mp, tp, st);
-        else run_nt_h2<false, 4>(lda, R, wf, ew, C, bias, ldo, DropSpec{}, mp, tp, st);
-      }
-      return launch_status("rb_gemm_nt_h");
-    }
-    if (!few && wide && C % 64 == 0) {
-      const int64_t Mt = M - M_main;
-      const int mt_t = (int)((Mt + N_BM - 1) / N_BM);
-      const int64_t nt_t = (int64_t)((mt_t + 7) / 8) * 8 * (C / 64);
-      const unsigned grid_t = (unsigned)std::min<int64_t>(nt_t, (int64_t)num_cus() / 8 * 8 * (8 / N_WAVES));
-      const float* At = A + M_main * lda;
-      float* ot = out + M_main * ldo;
-      float* rt = rmax ? rmax + M_main / 32 : nullptr;
-      if (bias) run_nt_h<true, true, 2>(At, lda, Mt, R, wf, ew, C, bias, ot, ldo, rt, mt_t, grid_t, st);
-      else run_nt_h<false, true, 2>(At, lda, Mt, R, wf, ew, C, bias, ot, ldo, rt, mt_t, grid_t, st);
-      const int rc = launch_status("rb_gemm_nt_h");
-      if (rc || M_main == 0) return rc;
-    } else
-    {
-      const int rc = launch_gemm_nt_hs(A + M_main * lda, lda, M - M_main, R, Wf, C, bias,
-                                       out + M_main * ldo, ldo,
-                                       rmax ? rmax + M_main / 32 : nullptr, st);
-      if (rc || M_main == 0) return rc;
-    }
-  }
-  M = M_main;
-  const int m_tiles = (int)((M + N_BM - 1) / N_BM);
-  const int64_t n_tiles = (int64_t)((m_tiles + 7) / 8) * 8 * (C / (nb8 ? 256 : 128));
-  // persistent: one workgroup per CU (a multiple of 8: the XCD pairing above)
-  const unsigned grid = (unsigned)std::min<int64_t>(n_tiles, (int64_t)num_cus() / 8 * 8 * (8 / N_WAVES));
-  if (bias) {
-    if (nb8) run_nt_h<true, true, 8>(A, lda, M, R, wf, ew, C, bias, out, ldo, rmax, m_tiles, grid, st);
-    else if (wide) run_nt_h<true, true, 4>(A, lda, M, R, wf, ew, C, bias, out, ldo, rmax, m_tiles, grid, st);
-    else run_nt_h<true, false, 4>(A, lda, M, R, wf, ew, C, bias, out, ldo, rmax, m_tiles, grid, st);
-  } else {
-    if (nb8) run_nt_h<false, true, 8>(A, lda, M, R, wf, ew, C, bias, out, ldo, rmax, m_tiles, grid, st);
-    else if (wide) run_nt_h<false, true, 4>(A, lda, M, R, wf, ew, C, bias, out, ldo, rmax, m_tiles, grid, st);
-    else run_nt_h<false, false, 4>(A, lda, M, R, wf, ew, C, bias, out, ldo, rmax, m_tiles, grid, st);
-  }
-  return launch_status("rb_gemm_nt_h");
+  const bool wide = aligned16(out) && ldo % 4 == 0;
+  const NtPlan p = nt_plan(NtKind::plain, M, R, C, wide, bias != nullptr, num_cus());
+  const NtArgs a{A, lda, M, R, Wf, C, bias, out, ldo, rmax, nullptr, nullptr, nullptr, DropSpec{}, st};
+  return dispatch_bool(p.bias, [&](auto bias_c) {
+    constexpr bool BIAS = decltype(bias_c)::value;
+    if (p.nb == 8) return run_nt_plan<BIAS, true, 8>("rb_gemm_nt_h", p, a);
+    if (p.wide) return run_nt_plan<BIAS, true, 4>("rb_gemm_nt_h", p, a);
+    return run_nt_plan<BIAS, false, 4>("rb_gemm_nt_h", p, a);
+  });
 }
 
 // out = A Bm^T + bias and act = dropout(silu(out)) in one pass (the
-// FeedForward's first projection + its activation, RecBLR.py:219-221).  The
-// same row split as launch_gemm_nt_h; only the shapes whose every row runs on
-// a wide-epilogue launch are taken (16-B aligned out / act, ldo % 4 == 0,
-// C % 256 == 0, not the few-rows kernel's shapes): nt_h_act_ok says which.
-bool nt_h_act_ok(int64_t M, int R, int C, const float* out, const float* act, int64_t ldo) {
-  const bool wide = (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(act) & 15) == 0 && ldo % 4 == 0;
-  const bool few = M <= 4096 && (R > 256 || C < 256);
-  return wide && C % 256 == 0 && C <= N_MAXC && R <= 1024 && !few;
-}
-
-// ACT's main launch: 256 x 256 tiles stored at the tile's end (264 us at
-// 204,632 rows against 140 + 135-142 us for the GEMM and the activation
-// kernel; 256 x 128 tiles with the deferred epilogue took 995 us,
+// FeedForward's first projection + its activation, RecBLR.py:219-221).  Only
+// the shapes whose every row runs on a wide-epilogue launch are taken
+// (nt_h_act_ok).  The main launch: 256 x 256 tiles stored at the tile's end
+// (264 us at 204,632 rows against 140 + 135-142 us for the GEMM and the
+// activation kernel; 256 x 128 tiles with the deferred epilogue took 995 us,
 // profiles/r03_ffn_probe2.txt)
-constexpr int ACT_NB = 8;
 int launch_gemm_nt_h_act(const float* A, int64_t lda, int64_t M, int R, const void* Wf, int C,
                          const float* bias, float* out, int64_t ldo, float* rmax, float* act,
                          DropSpec drop, hipStream_t st) {
   if (g_nt_mode == 1 && M >= NT_WS_MIN_ROWS && nt_ws_act_ok(M, R, C, A, lda, out, act, ldo))
     return launch_gemm_nt_ws_act(A, lda, M, R, Wf, C, bias, out, ldo, rmax, act, drop, st);
-  if (!nt_h_act_ok(M, R, C, out, act, ldo))
-    return fail("rb_gemm_nt_h_act: shape or alignment without a wide-epilogue launch");
-  const int G0 = num_cus() / 8 * 8 * (8 / N_WAVES);
-  const int nct0 = C / (32 * ACT_NB);
-  const int64_t rows_round = (int64_t)(G0 / nct0) * N_BM;
-  const int64_t M_main = (G0 % nct0 == 0 && rows_round > 0) ? M / rows_round * rows_round : M;
-  const f16x8* wf = (const f16x8*)Wf;
-  const int* ew = reinterpret_cast<const int*>(reinterpret_cast<const char*>(Wf) + (int64_t)C * R * 4);
-  if (M_main > 0 && M_main < M) {   // both phases in one launch (k_gemm_nt_h2)
-    const NtPhase mp = nt_phase(A, lda, 0, M_main, out, ldo, rmax, C, 32 * ACT_NB, G0, act);
-    const NtPhase tp = nt_phase(A, lda, M_main, M - M_main, out, ldo, rmax, C, 64, G0, act);
-    if (bias) run_nt_h2<true, ACT_NB, true>(lda, R, wf, ew, C, bias, ldo, drop, mp, tp, st);
-    else run_nt_h2<false, ACT_NB, true>(lda, R, wf, ew, C, bias, ldo, drop, mp, tp, st);
-    return launch_status("rb_gemm_nt_h_act");
-  }
-  if (M_main < M) {   // the rows past the last whole round: 256 x 64 tiles
-    const int64_t Mt = M - M_main;
-    const int mt_t = (int)((Mt + N_BM - 1) / N_BM);
-    const int64_t nt_t = (int64_t)((mt_t + 7) / 8) * 8 * (C / 64);
-    const unsigned grid_t = (unsigned)std::min<int64_t>(nt_t, (int64_t)G0);
-    const float* At = A + M_main * lda;
-    float* ot = out + M_main * ldo;
-    float* at = act + M_main * ldo;
-    float* rt = rmax ? rmax + M_main / 32 : nullptr;
-    if (bias) run_nt_h<true, true, 2, true>(At, lda, Mt, R, wf, ew, C, bias, ot, ldo, rt, mt_t, grid_t, st, at, drop, M_main * C);
-    else run_nt_h<false, true, 2, true>(At, lda, Mt, R, wf, ew, C, bias, ot, ldo, rt, mt_t, grid_t, st, at, drop, M_main * C);
-    const int rc = launch_status("rb_gemm_nt_h_act");
-    if (rc || M_main == 0) return rc;
-  }
-  const int m_tiles = (int)((M_main + N_BM - 1) / N_BM);
-  const int64_t n_tiles = (int64_t)((m_tiles + 7) / 8) * 8 * nct0;
-  const unsigned grid = (unsigned)std::min<int64_t>(n_tiles, (int64_t)G0);
-  if (bias) run_nt_h<true, true, ACT_NB, true>(A, lda, M_main, R, wf, ew, C, bias, out, ldo, rmax, m_tiles, grid, st, act, drop, 0);
-  else run_nt_h<false, true, ACT_NB, true>(A, lda, M_main, R, wf, ew, C, bias, out, ldo, rmax, m_tiles, grid, st, act, drop, 0);
-  return launch_status("rb_gemm_nt_h_act");
+  const bool wide = aligned16(out) && aligned16(act) && ldo % 4 == 0;
+  const NtPlan p = nt_plan(NtKind::act, M, R, C, wide, bias != nullptr, num_cus());
+  const NtArgs a{A, lda, M, R, Wf, C, bias, out, ldo, rmax, act, nullptr, nullptr, drop, st};
+  return dispatch_bool(p.bias, [&](auto bias_c) {
+    return run_nt_plan<decltype(bias_c)::value, true, 8, true>("rb_gemm_nt_h_act", p, a);
+  });
+}
+
+int64_t nt_h_dact_parts() { return nt_h_dact_parts(num_cus()); }
+
+int nt_dact_zero_rest(float* dpart, int64_t used, int64_t n_parts, int C, hipStream_t st) {
+  if (used < n_parts &&
+      hipMemsetAsync(dpart + used * C, 0, (size_t)(n_parts - used) * C * 4, st) != hipSuccess)
+    return fail("rb_gemm_nt_h_dact: hipMemsetAsync failed");
+  return 0;
 }
 
 // The backward of launch_gemm_nt_h_act's activation fused into the
@@ -1583,61 +1545,19 @@ int launch_gemm_nt_h_act(const float* A, int64_t lda, int64_t M, int R, const vo
 // never stored; out = dU * keep * scale * silu'(pre) (pre: the activation's
 // input, [M, C] with row stride ldo) and dpart [n_parts, C] receives the
 // workgroups' column sums of out (rows past the launches' grids zeroed).
-// The same row split and shape contract as the forward (nt_h_act_ok), C <=
-// 512.
-// DACT's main launch: 256 x 128 tiles stored at the tile's end (the 256 x 256
-// tile's 128 accumulators leave no registers for the epilogue's operands)
-constexpr int DACT_NB = 4;
-int64_t nt_h_dact_parts() { return 2 * (int64_t)(num_cus() / 8 * 8 * (8 / N_WAVES)); }
-
+// The forward's shape contract, C <= 512.  The main launch: 256 x 128 tiles
+// stored at the tile's end (the 256 x 256 tile's 128 accumulators leave no
+// registers for the epilogue's operands)
 int launch_gemm_nt_h_dact(const float* A, int64_t lda, int64_t M, int R, const void* Wf, int C,
                           float* out, int64_t ldo, float* rmax, const float* pre, DropSpec drop,
                           float* dpart, int64_t n_parts, hipStream_t st) {
   if (g_nt_mode == 1 && M >= NT_WS_MIN_ROWS && nt_ws_act_ok(M, R, C, A, lda, out, pre, ldo))
     return launch_gemm_nt_ws_dact(A, lda, M, R, Wf, C, out, ldo, rmax, pre, drop, dpart, n_parts, st);
-  if (!nt_h_act_ok(M, R, C, out, pre, ldo) || C > N_DACT_MAXC)
-    return fail("rb_gemm_nt_h_dact: shape or alignment without a wide-epilogue launch");
-  const int G0 = num_cus() / 8 * 8 * (8 / N_WAVES);
-  const int nct0 = C / (32 * DACT_NB);
-  const int64_t rows_round = (int64_t)(G0 / nct0) * N_BM;
-  const int64_t M_main = (G0 % nct0 == 0 && rows_round > 0) ? M / rows_round * rows_round : M;
-  const f16x8* wf = (const f16x8*)Wf;
-  const int* ew = reinterpret_cast<const int*>(reinterpret_cast<const char*>(Wf) + (int64_t)C * R * 4);
-  const int m_tiles = (int)((M_main + N_BM - 1) / N_BM);
-  const int64_t n_tiles = (int64_t)((m_tiles + 7) / 8) * 8 * nct0;
-  const unsigned grid = M_main > 0 ? (unsigned)std::min<int64_t>(n_tiles, (int64_t)G0) : 0u;
-  const int64_t Mt = M - M_main;
-  const int mt_t = (int)((Mt + N_BM - 1) / N_BM);
-  const int64_t nt_t = (int64_t)((mt_t + 7) / 8) * 8 * (C / 64);
-  const unsigned grid_t = Mt > 0 ? (unsigned)std::min<int64_t>(nt_t, (int64_t)G0) : 0u;
-  if ((int64_t)grid + grid_t > n_parts) return fail("rb_gemm_nt_h_dact: dpart has too few rows");
-  if (Mt > 0 && M_main > 0) {   // both phases in one launch (k_gemm_nt_h2)
-    const NtPhase mp = nt_phase(A, lda, 0, M_main, out, ldo, rmax, C, 32 * DACT_NB, G0, nullptr,
-                                pre, dpart);
-    const NtPhase tp = nt_phase(A, lda, M_main, Mt, out, ldo, rmax, C, 64, G0, nullptr, pre,
-                                dpart + (int64_t)grid * C);
-    run_nt_h2<false, DACT_NB, false, true>(lda, R, wf, ew, C, nullptr, ldo, drop, mp, tp, st);
-    const int rc = launch_status("rb_gemm_nt_h_dact");
-    if (rc) return rc;
-  } else if (Mt > 0) {   // the rows past the last whole round: 256 x 64 tiles
-    run_nt_h<false, true, 2, false, true>(A + M_main * lda, lda, Mt, R, wf, ew, C, nullptr,
-                                          out + M_main * ldo, ldo, rmax ? rmax + M_main / 32 : nullptr,
-                                          mt_t, grid_t, st, nullptr, drop, M_main * C,
-                                          pre + M_main * ldo, dpart + (int64_t)grid * C);
-    const int rc = launch_status("rb_gemm_nt_h_dact");
-    if (rc) return rc;
-  }
-  if (M_main > 0 && Mt == 0) {
-    run_nt_h<false, true, DACT_NB, false, true>(A, lda, M_main, R, wf, ew, C, nullptr, out, ldo, rmax,
-                                          m_tiles, grid, st, nullptr, drop, 0, pre, dpart);
-    const int rc = launch_status("rb_gemm_nt_h_dact");
-    if (rc) return rc;
-  }
-  const int64_t used = (int64_t)grid + grid_t;
-  if (used < n_parts &&
-      hipMemsetAsync(dpart + used * C, 0, (size_t)(n_parts - used) * C * 4, st) != hipSuccess)
-    return fail("rb_gemm_nt_h_dact: hipMemsetAsync failed");
-  return 0;
+  const bool wide = aligned16(out) && aligned16(pre) && ldo % 4 == 0;
+  const NtPlan p = nt_plan(NtKind::dact, M, R, C, wide, false, num_cus(), n_parts);
+  const NtArgs a{A, lda, M, R, Wf, C, nullptr, out, ldo, rmax, nullptr, pre, dpart, drop, st};
+  const int rc = run_nt_plan<false, true, 4, false, true>("rb_gemm_nt_h_dact", p, a);
+  return rc ? rc : nt_dact_zero_rest(dpart, p.used, n_parts, C, st);
 }
 
 // dW tile: 256 x 128 when N % 256 == 0 (2), else 128 x 256 when K % 256 == 0

@@ -809,27 +809,24 @@ bool nt_ws_ok(int64_t M, int K, int C, const float* A, int64_t lda, const float*
          (M + ws::RB - 1) / ws::RB <= 0x3fffffffLL;
 }
 
-// Wf: the combined image of gemm_half.hip (persistent-kernel planes, the
-// column exponents, then this kernel's planes at ws_image_offset)
+// Wf: the combined image of gemm_half.hip (weight_image: the persistent
+// kernel's planes, the column exponents, then this kernel's planes)
 int launch_gemm_nt_ws(const float* A, int64_t lda, int64_t M, int K, const void* Wf, int C,
                       const float* bias, float* out, int64_t ldo, float* rmax, hipStream_t st) {
   if (!nt_ws_ok(M, K, C, A, lda, out, ldo)) return fail("rb_gemm_nt_h: no weight-stationary launch for this shape");
-  const void* Wi = reinterpret_cast<const char*>(Wf) + ws_image_offset(C, K);
-  const int* ew = reinterpret_cast<const int*>(reinterpret_cast<const char*>(Wf) + (int64_t)C * K * 4);
+  const WeightImage w = weight_image(Wf, C, K);
   const int ncb = ws::ncb_for(K, C);
   const int grid = ws::grid_for(M, C, ncb);
-  auto go = [&](auto kc, auto nc) {
-    constexpr int KK = decltype(kc)::value, NC = decltype(nc)::value;
-    if (bias) ws::run<KK, NC, ws::depth<KK>(), true, true, 0>(A, lda, M, Wi, ew, C, bias, out, ldo, rmax, grid, st);
-    else ws::run<KK, NC, ws::depth<KK>(), false, true, 0>(A, lda, M, Wi, ew, C, bias, out, ldo, rmax, grid, st);
-  };
-  using std::integral_constant;
-  if (K == 128 && ncb == 4) go(integral_constant<int, 128>{}, integral_constant<int, 4>{});
-  else if (K == 128 && ncb == 2) go(integral_constant<int, 128>{}, integral_constant<int, 2>{});
-  else if (K == 128 && ncb == 1) go(integral_constant<int, 128>{}, integral_constant<int, 1>{});
-  else if (K == 256 && ncb == 2) go(integral_constant<int, 256>{}, integral_constant<int, 2>{});
-  else if (K == 256 && ncb == 1) go(integral_constant<int, 256>{}, integral_constant<int, 1>{});
-  else go(integral_constant<int, 512>{}, integral_constant<int, 1>{});
+  dispatch_int<128, 256, 512>(K, [&](auto kc) {
+    dispatch_int<1, 2, 4>(ncb, [&](auto nc) {
+      dispatch_bool(bias != nullptr, [&](auto bias_c) {
+        constexpr int KK = decltype(kc)::value, NC = decltype(nc)::value;
+        if constexpr (NC <= 16 / (KK / 32))   // (the blocks a wave's weight slice holds)
+          ws::run<KK, NC, ws::depth<KK>(), decltype(bias_c)::value, true, 0>(
+              A, lda, M, w.wi, w.ew, C, bias, out, ldo, rmax, grid, st);
+      });
+    });
+  });
   return launch_status("rb_gemm_nt_h");
 }
 
@@ -846,11 +843,12 @@ int launch_gemm_nt_ws_act(const float* A, int64_t lda, int64_t M, int K, const v
                           const float* bias, float* out, int64_t ldo, float* rmax, float* act,
                           DropSpec drop, hipStream_t st) {
   if (!nt_ws_act_ok(M, K, C, A, lda, out, act, ldo)) return fail("rb_gemm_nt_h_act: shape");
-  const void* Wi = reinterpret_cast<const char*>(Wf) + ws_image_offset(C, K);
-  const int* ew = reinterpret_cast<const int*>(reinterpret_cast<const char*>(Wf) + (int64_t)C * K * 4);
+  const WeightImage w = weight_image(Wf, C, K);
   const int grid = ws::grid_for(M, C, 2);
-  if (bias) ws::run<128, 2, ws::depth<128>(), true, true, 0, 1>(A, lda, M, Wi, ew, C, bias, out, ldo, rmax, grid, st, act, drop);
-  else ws::run<128, 2, ws::depth<128>(), false, true, 0, 1>(A, lda, M, Wi, ew, C, bias, out, ldo, rmax, grid, st, act, drop);
+  dispatch_bool(bias != nullptr, [&](auto bias_c) {
+    ws::run<128, 2, ws::depth<128>(), decltype(bias_c)::value, true, 0, 1>(
+        A, lda, M, w.wi, w.ew, C, bias, out, ldo, rmax, grid, st, act, drop);
+  });
   return launch_status("rb_gemm_nt_h_act");
 }
 
@@ -860,19 +858,14 @@ int launch_gemm_nt_ws_dact(const float* A, int64_t lda, int64_t M, int K, const 
                            float* out, int64_t ldo, float* rmax, const float* pre, DropSpec drop,
                            float* dpart, int64_t n_parts, hipStream_t st) {
   if (!nt_ws_act_ok(M, K, C, A, lda, out, pre, ldo)) return fail("rb_gemm_nt_h_dact: shape");
-  const void* Wi = reinterpret_cast<const char*>(Wf) + ws_image_offset(C, K);
-  const int* ew = reinterpret_cast<const int*>(reinterpret_cast<const char*>(Wf) + (int64_t)C * K * 4);
+  const WeightImage w = weight_image(Wf, C, K);
   const int grid = ws::grid_for(M, C, 2);
   const int64_t used = grid / (C / 256);
   if (used > n_parts) return fail("rb_gemm_nt_h_dact: dpart has too few rows");
-  ws::run<128, 2, ws::depth<128>(), false, true, 0, 2>(A, lda, M, Wi, ew, C, nullptr, out, ldo, rmax, grid,
+  ws::run<128, 2, ws::depth<128>(), false, true, 0, 2>(A, lda, M, w.wi, w.ew, C, nullptr, out, ldo, rmax, grid,
                                                       st, nullptr, drop, pre, dpart);
   const int rc = launch_status("rb_gemm_nt_h_dact");
-  if (rc) return rc;
-  if (used < n_parts &&
-      hipMemsetAsync(dpart + used * C, 0, (size_t)(n_parts - used) * C * 4, st) != hipSuccess)
-    return fail("rb_gemm_nt_h_dact: hipMemsetAsync failed");
-  return 0;
+  return rc ? rc : nt_dact_zero_rest(dpart, used, n_parts, C, st);
 }
 
 // The residual + dropout + LayerNorm after a C = 128 projection (EPI 3):
@@ -891,8 +884,7 @@ int launch_gemm_nt_ws_ln(const float* A, int64_t lda, int64_t M, int K, const vo
   if (!nt_ws_ln_ok(M, K, C, A, lda, y, s_out, resid, ldo) || !gamma || !beta || !mean || !rstd ||
       !aligned16(gamma) || !aligned16(beta))
     return fail("rb_gemm_nt_h_ln: shape, alignment or null pointer");
-  const void* Wi = reinterpret_cast<const char*>(Wf) + ws_image_offset(C, K);
-  const int* ew = reinterpret_cast<const int*>(reinterpret_cast<const char*>(Wf) + (int64_t)C * K * 4);
+  const WeightImage w = weight_image(Wf, C, K);
   const int grid = ws::grid_for(M, C, 1);
   ws::LnSpec ln;
   ln.gamma = gamma;
@@ -900,14 +892,13 @@ int launch_gemm_nt_ws_ln(const float* A, int64_t lda, int64_t M, int K, const vo
   ln.eps = eps;
   ln.mean = mean;
   ln.rstd = rstd;
-  auto go = [&](auto kc) {
-    constexpr int KK = decltype(kc)::value;
-    if (bias) ws::run<KK, 1, ws::depth<KK>(), true, true, 0, 3>(A, lda, M, Wi, ew, C, bias, s_out, ldo, rmax, grid, st, y, drop, resid, nullptr, ln);
-    else ws::run<KK, 1, ws::depth<KK>(), false, true, 0, 3>(A, lda, M, Wi, ew, C, bias, s_out, ldo, rmax, grid, st, y, drop, resid, nullptr, ln);
-  };
-  if (K == 128) go(std::integral_constant<int, 128>{});
-  else if (K == 256) go(std::integral_constant<int, 256>{});
-  else go(std::integral_constant<int, 512>{});
+  dispatch_int<128, 256, 512>(K, [&](auto kc) {
+    dispatch_bool(bias != nullptr, [&](auto bias_c) {
+      constexpr int KK = decltype(kc)::value;
+      ws::run<KK, 1, ws::depth<KK>(), decltype(bias_c)::value, true, 0, 3>(
+          A, lda, M, w.wi, w.ew, C, bias, s_out, ldo, rmax, grid, st, y, drop, resid, nullptr, ln);
+    });
+  });
   return launch_status("rb_gemm_nt_h_ln");
 }
 

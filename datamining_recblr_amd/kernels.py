@@ -1136,6 +1136,7 @@ def nt_h_mode(mode: int):
 def gemm_nt_h_ln_ok(a: torch.Tensor, C: int) -> bool:
     """Whether gemm_nt_h_ln takes a [M, R] operand with C outputs:
     rb_gemm_nt_h_ln's shape contract and the weight-stationary kernel selected."""
+    # mirrors nt_ws_ln_ok (csrc/gemm_ws.hip) for freshly allocated outputs
     return (a.dim() == 2 and C == 128 and a.shape[1] in (128, 256, 512) and a.stride(1) == 1
             and a.stride(0) % 4 == 0 and a.data_ptr() % 16 == 0 and gemm_nt_h_mode() == 1)
 
@@ -1180,6 +1181,8 @@ def gemm_nt_h_ln(a: torch.Tensor, wf: torch.Tensor, C: int, bias: torch.Tensor |
 def gemm_nt_h_act_ok(a: torch.Tensor, C: int) -> bool:
     """Whether gemm_nt_h_act takes a [M, R] operand with C outputs (freshly
     allocated contiguous outputs): rb_gemm_nt_h_act's shape contract."""
+    # mirrors nt_h_act_ok (csrc/nt_plan.h) with wide outputs; the weight-stationary
+    # kernel's shapes (nt_ws_act_ok, csrc/gemm_ws.hip) lie inside it
     M, R = a.shape
     return C % 256 == 0 and C <= 1024 and R % 32 == 0 and R <= 1024 and not (
         M <= 4096 and (R > 256 or C < 256))

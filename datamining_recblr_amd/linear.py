@@ -100,7 +100,10 @@ def _make_image(w, transpose):
 
 
 def _weight_split(w: torch.Tensor, transpose: bool) -> torch.Tensor:
-    """The f16 weight image of w (transpose: of w^T), cached."""
+    """The f16 weight image of w (transpose: of w^T), cached.  Every f16 GEMM
+    launch takes its weight from here, so RECBLR_NT_WS reaches the library
+    here, before the first of them."""
+    _apply_nt_ws()
     if not _cache_on:
         return _make_image(w, transpose)
     key = (id(w), transpose)
@@ -267,7 +270,6 @@ def mm_nt(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None,
         return torch.addmm(bias.to(a.dtype), a, wb.t()) if bias is not None else a @ wb.t()
     N, K = w.shape
     if _split_ok(a, N, K):
-        _apply_nt_ws()
         return kernels.gemm_nt_h(a, _weight_split(w, False), N, bias=bias, rmax=rmax)
     return torch.addmm(bias, a, w.t()) if bias is not None else torch.mm(a, w.t())
 
@@ -330,7 +332,7 @@ def mm_nt_ln_ok(a: torch.Tensor, w: torch.Tensor) -> bool:
     if not (_ln_fused and _half and a.dtype == w.dtype and a.shape[0] >= ACT_MIN_ROWS
             and _split_ok(a, N, K)):
         return False
-    _apply_nt_ws()
+    _apply_nt_ws()   # (the one query that reads the library's mode, before any launch)
     return kernels.gemm_nt_h_ln_ok(a, N)
 
 
@@ -370,7 +372,6 @@ def mm_nn(dy: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = None,
         return out.addmm_(dy, wb) if out is not None else dy @ wb
     N, K = w.shape
     if _split_ok(dy, K, N):
-        _apply_nt_ws()
         r = kernels.gemm_nt_h(dy, _weight_split(w, True), K, rmax=rmax)
         return r if out is None else out.add_(r)
     if out is not None:

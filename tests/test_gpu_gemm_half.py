@@ -438,33 +438,105 @@ def test_weight_gradient_columns_spread_beyond_2_to_the_16(cuda, spread, N, K):
     assert e_h < 1e-5 and e_h < 4 * max(e_t, 1e-7), (e_h, e_t)
 
 
-@pytest.mark.parametrize("M,K,N", [(2048, 512, 128), (2048, 128, 512), (2048, 256, 128),
-                                   (77, 64, 32), (5000, 96, 96), (196608 + 8024, 256, 512),
-                                   (196608 + 8024, 512, 128), (65536 * 3 + 31, 128, 256)])
-def test_few_rows_kernel_and_round_remainder(cuda, M, K, N):
-    """The few-rows kernel (csrc/gemm_small.hip: the gathered last-layer tail,
-    B = 2048 rows; C % 128 != 0) and the rows past the persistent kernel's
-    last whole round (bench-sized M: 196,608 rows there + 8,024 here, on the
-    256 x 64-tile launch of the same kernel).  Every
-    row at fp32 level against fp64 (per-row error against the row's max), the
-    rmax side output equal to the exact 32-row-group maxima across the seam."""
-    from datamining_recblr_amd import kernels
+def _check_rows_and_seam(kernels, x, w, b, ref, out_of=None):
+    """One rb_gemm_nt_h call under the selected kernel mode: every row at fp32
+    level against fp64 (per-row error against the row's max), the bias
+    epilogue exactly the un-biased output plus the bias, the rmax side output
+    equal to the exact 32-row-group maxima across the seam.  out_of: a buffer
+    factory for the output view."""
+    M, N = x.shape[0], w.shape[0]
+    rmax = torch.empty((M + 31) // 32, device=x.device)
+    wf = kernels.gemm_h_weight(w)
+    y = kernels.gemm_nt_h(x, wf, N, rmax=rmax, out=out_of() if out_of else None)
+    row_err = ((y.double() - ref).abs().amax(1) / ref.abs().amax(1)).max().item()
+    assert row_err < 4e-6, row_err
+    # the bias epilogue: exactly the un-biased output plus the bias, in fp32
+    assert torch.equal(kernels.gemm_nt_h(x, wf, N, bias=b, out=out_of() if out_of else None), y + b)
+    want = torch.nn.functional.pad(x.abs().amax(1), (0, (-M) % 32)).view(-1, 32).amax(1)
+    assert torch.equal(rmax, want)
 
+
+def _rows_across_2_to_the_60(M, K, N, cuda):
     g = torch.Generator().manual_seed(M + 3 * K + N)
     x = (torch.randn(M, K, generator=g) * torch.exp2(torch.randint(-30, 30, (M, 1), generator=g)
                                                       .float())).to(cuda)
     w = (torch.randn(N, K, generator=g) / K ** 0.5).to(cuda)
     b = torch.randn(N, generator=g).to(cuda)
-    rmax = torch.empty((M + 31) // 32, device=cuda)
-    wf = kernels.gemm_h_weight(w)
-    y = kernels.gemm_nt_h(x, wf, N, rmax=rmax)
-    ref = x.double() @ w.double().t()
-    row_err = ((y.double() - ref).abs().amax(1) / ref.abs().amax(1)).max().item()
-    assert row_err < 4e-6, row_err
-    # the bias epilogue: exactly the un-biased output plus the bias, in fp32
-    assert torch.equal(kernels.gemm_nt_h(x, wf, N, bias=b), y + b)
-    want = torch.nn.functional.pad(x.abs().amax(1), (0, (-M) % 32)).view(-1, 32).amax(1)
-    assert torch.equal(rmax, want)
+    return x, w, b, x.double() @ w.double().t()
+
+
+@pytest.mark.parametrize("M,K,N", [(2048, 512, 128), (2048, 128, 512), (2048, 256, 128),
+                                   (77, 64, 32), (5000, 96, 96), (196608 + 8024, 256, 512),
+                                   (196608 + 8024, 512, 128), (65536 * 3 + 31, 128, 256),
+                                   (16384 + 293, 32, 1024), (65536 + 293, 32, 128),
+                                   (16384 + 293, 32, 384)])
+def test_few_rows_kernel_and_round_remainder(cuda, M, K, N):
+    """rb_gemm_nt_h's row split (csrc/nt_plan.h) under both kernel modes
+    (kernels.nt_h_mode), against one fp64 reference per shape.  Below 16,384
+    rows both modes run the same launches: the few-rows kernel
+    (csrc/gemm_small.hip: the gathered last-layer tail, B = 2048 rows;
+    C % 128 != 0) or the 256 x 64 tiles of the persistent kernel.  From 16,384
+    rows mode 1 (the default) runs the weight-stationary kernel
+    (csrc/gemm_ws.hip) where it takes the shape (K = 128, 256 or 512) and
+    mode 0 the persistent kernel's whole rounds with the rows past the last
+    whole round on 256 x 64 tiles in the same launch (k_gemm_nt_h2; at 256
+    CUs): bench-sized M, 196,608 rows there + 8,024 here, on 256 x 256
+    (N = 512) and 256 x 128 tiles (N = 128, 256).  The K = 32 shapes run the
+    persistent kernel in both modes: one round of 16,384 rows on 256 x 256
+    tiles plus 293 (N = 1024), one of 65,536 rows on 256 x 128 tiles plus 293
+    (N = 128), and N = 384, whose three column tiles do not divide the grid,
+    so that every row runs in the main launch with a partial round."""
+    from datamining_recblr_amd import kernels
+
+    x, w, b, ref = _rows_across_2_to_the_60(M, K, N, cuda)
+    for mode in (0, 1):
+        with kernels.nt_h_mode(mode):
+            _check_rows_and_seam(kernels, x, w, b, ref)
+
+
+def test_round_remainder_into_an_unaligned_output_view(cuda):
+    """The output a column-offset view of a wider buffer (ldo % 4 != 0: no
+    wide epilogue) at one round of 65,536 rows plus 293: the non-wide 256 x 128
+    main launch after the few-rows kernel on the rows past the round, in both
+    modes (the weight-stationary kernel needs ldo % 4 == 0); the buffer's
+    other columns stay untouched."""
+    from datamining_recblr_amd import kernels
+
+    M, K, N = 65536 + 293, 32, 128
+    x, w, b, ref = _rows_across_2_to_the_60(M, K, N, cuda)
+    bufs = []
+
+    def view():
+        bufs.append(torch.zeros(M, N + 6, device=cuda))
+        return bufs[-1][:, 2:2 + N]
+
+    for mode in (0, 1):
+        with kernels.nt_h_mode(mode):
+            _check_rows_and_seam(kernels, x, w, b, ref, out_of=view)
+    for buf in bufs:
+        assert buf[:, :2].abs().max().item() == 0.0 and buf[:, 2 + N:].abs().max().item() == 0.0
+
+
+def test_nt_ws_switch_reaches_the_fused_activation_first(cuda):
+    """RECBLR_NT_WS=0 in a fresh process whose first GEMM is linear.mm_nt_act
+    (w_1 at 16,384 rows): the library's mode is 0 afterwards, so the call ran
+    on the persistent kernel."""
+    import os
+    import subprocess
+    import sys
+
+    code = ("import torch\n"
+            "from datamining_recblr_amd import kernels, linear\n"
+            "a = torch.randn(16384, 128, device='cuda')\n"
+            "w = torch.randn(512, 128, device='cuda')\n"
+            "out, act = linear.mm_nt_act(a, w, None, seed=1, p=0.0)\n"
+            "torch.cuda.synchronize()\n"
+            "assert kernels.gemm_nt_h_mode() == 0, kernels.gemm_nt_h_mode()\n")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, RECBLR_NT_WS="0")
+    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
 
 
 @pytest.mark.parametrize("M", [1, 100, 2048, 16383])

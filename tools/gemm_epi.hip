@@ -69,8 +69,14 @@ int launch_variant(int v, const float* A, int64_t M, int R, const void* Wf, int 
   const int64_t M_main = M / rows_round * rows_round;
   const f16x8* wf = (const f16x8*)Wf;
   const int* ew = reinterpret_cast<const int*>(reinterpret_cast<const char*>(Wf) + (int64_t)C * R * 4);
-  const NtPhase mp = nt_phase(A, R, 0, M_main, out, C, nullptr, C, nb8 ? 256 : 128, G0);
-  const NtPhase tp = nt_phase(A, R, M_main, M - M_main, out, C, nullptr, C, 64, G0);
+  const NtArgs a{A, R, M, R, Wf, C, nullptr, out, C, nullptr, nullptr, nullptr, nullptr, DropSpec{}, st};
+  auto phase = [&](int64_t r0, int64_t rows, int cols) {   // (sized as nt_plan.h sizes a phase)
+    const int m_tiles = (int)((rows + N_BM - 1) / N_BM);
+    const int64_t n_tiles = (int64_t)((m_tiles + 7) / 8) * 8 * (C / cols);
+    return nt_phase(a, r0, rows, m_tiles, rows > 0 ? (int)std::min<int64_t>(n_tiles, G0) : 0, 0);
+  };
+  const NtPhase mp = phase(0, M_main, nb8 ? 256 : 128);
+  const NtPhase tp = phase(M_main, M - M_main, 64);
   if (v == 2) {
     run_nt_h2<false, 4>(R, R, wf, ew, C, nullptr, C, DropSpec{}, mp, tp, st);
     return launch_status("nb4");
