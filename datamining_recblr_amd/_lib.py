@@ -95,6 +95,9 @@ SIGNATURES = parse_header(_header)
 EXP_SIGNATURES = parse_header(_read(os.path.join(_HERE, "experimental", "recblr_exp.h")))
 # the probe library (probes/recblr_probe.h: bench.py's measurement aids)
 PROBE_SIGNATURES = parse_header(_read(os.path.join(_HERE, "probes", "recblr_probe.h")))
+# the session library (session/recblr_session.h: the one-launch per-event
+# encoder step of session.py; loaded on the first step)
+SESSION_SIGNATURES = parse_header(_read(os.path.join(_HERE, "session", "recblr_session.h")))
 
 _lock = threading.Lock()
 _loaded = {}
@@ -148,6 +151,14 @@ def load_exp() -> ctypes.CDLL:
                  "experimental library ABI {} vs {}; rebuild")
 
 
+def load_session() -> ctypes.CDLL:
+    """The session library (lib/libdmrecblr_session.so, session/
+    recblr_session.h): stateful per-event inference (session.py)."""
+    return _load(os.path.join(os.path.dirname(LIB_PATH), "libdmrecblr_session.so"),
+                 SESSION_SIGNATURES, "session library not built", "rb_session_version",
+                 "session library ABI {} vs {}; rebuild")
+
+
 _fns = {}
 _failure_hooks = []
 
@@ -193,3 +204,11 @@ def call_exp(name: str, *args) -> None:
     """Invoke an experimental-library entry point and raise on a non-zero status."""
     lib = load_exp()
     _check(getattr(lib, name)(*args), name, lib, "rb_exp_last_error_string")
+
+
+def call_session(name: str, *args) -> None:
+    """Invoke a session-library entry point and raise on a non-zero status."""
+    lib = load_session()
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        _check(rc, name, lib, "rb_session_last_error_string")

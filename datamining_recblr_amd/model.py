@@ -449,3 +449,26 @@ class RecBLR(SequentialRecommender):
         seq_output = self.forward(item_seq, interaction[self.ITEM_SEQ_LEN])
         return top_items(seq_output, self.item_embedding.weight, k, first_item=first_item,
                          exclude=item_seq if exclude_seen else None)
+
+    # ---- stateful session inference (session.py) ----------------------------
+    def session_open(self, capacity: int, seq_len: int | None = None):
+        """A session.SessionState of `capacity` slots for the window seq_len
+        (default max_seq_length): after t <= seq_len appended items a slot's
+        output equals forward() on the right-padded row of those items."""
+        from .session import SessionState
+
+        return SessionState(self, capacity, seq_len)
+
+    def session_step(self, state, items, slots=None):
+        """Append one item per row (0 = no event) and return the rows'
+        seq_output [B, d]: the whole encoder in one launch (session.step)."""
+        from .session import step
+
+        return step(self, state, items, slots)
+
+    def session_prefill(self, state, item_seq, item_seq_len, slots=None, reset: bool = True):
+        """Open sessions from stored histories, one step per column
+        (session.prefill)."""
+        from .session import prefill
+
+        return prefill(self, state, item_seq, item_seq_len, slots, reset)

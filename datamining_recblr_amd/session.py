@@ -1,0 +1,395 @@
+"""Stateful session inference: the encoder advanced by one event per call.
+
+RecBLR is a linear recurrent model, so a user's history is summarised by a
+fixed-size state and a new interaction costs O(1): ``step`` runs the whole
+encoder for one new item per session slot in ONE launch (rb_session_step,
+session/session_step.hip) instead of ``RecBLR.forward`` over the ``[B, L]``
+history.
+
+A session is opened for a window ``seq_len = L`` (default: the model's
+``max_seq_length``).  After ``t <= L`` items have been appended to a slot its
+output equals ``RecBLR.forward(item_seq, item_seq_len=t)`` in eval mode for the
+``[1, L]`` right-padded row of those items (the default mode: the pad prefix
+pow2(L) - L of the batch's L).  That holds because the pad prefix depends only
+on L (``recurrence.pad_prefix_state``) and everything after it is causal
+(``model.RecBLR._forward_packed``).  Past ``count == L`` the recurrence simply
+continues over the whole history; the reference would slide its L-window
+instead, which is not emulated.
+
+State per slot (``SessionState``): per layer the recurrent state ``h [H]``
+(initially that layer's pad-prefix state ``h0``) and the last ``K - 1``
+pre-conv rows ``[K - 1, H]`` (initially zero: the reference's causal conv
+zero-pads); ``count`` and the slot's last ``seq_output`` row ``out [d]``.
+
+Item id 0 means "no event for this slot in this call": the state is untouched
+and the returned row is the stored ``out``.  An item id outside ``[0, V)`` (or
+a slot outside the state) is never dereferenced: the row is masked, its state
+left alone, and ``state.status`` (int32 ``[B]``, a device tensor of the last
+call: ``STEPPED``, ``NO_EVENT``, ``BAD_ITEM``, ``BAD_SLOT``) reports it without
+a host sync.
+
+``step_reference`` is the same step in plain torch ops on whatever device the
+state lives on (CPU included): the checked restatement of the kernel, and the
+path ``step`` takes for shapes the kernel refuses (``kernel_supports``).
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib, kernels
+from ._lib import RecBLRNativeError
+from .recurrence import pad_prefix_state, pow2_pad_len
+
+__all__ = ["SessionState", "EncoderParams", "step", "step_reference", "prefill",
+           "kernel_supports", "STEPPED", "NO_EVENT", "BAD_ITEM", "BAD_SLOT"]
+
+_header = _lib._read(os.path.join(_lib._HERE, "session", "recblr_session.h"))
+STEPPED = _lib._define(_header, "RB_SESSION_STEPPED")
+NO_EVENT = _lib._define(_header, "RB_SESSION_NO_EVENT")
+BAD_ITEM = _lib._define(_header, "RB_SESSION_BAD_ITEM")
+BAD_SLOT = _lib._define(_header, "RB_SESSION_BAD_SLOT")
+MAX_LAYERS = _lib._define(_header, "RB_SESSION_MAX_LAYERS")
+MAX_LDS = _lib._define(_header, "RB_SESSION_MAX_LDS")
+LN_EPS = 1e-12   # every LayerNorm of the model (RecBLR.py:45, :131, :216)
+
+_LAYER_FIELDS = ("w_in", "conv_w", "conv_b", "w_gate", "b_gate", "lam", "w_out", "ln_w", "ln_b",
+                 "w1", "b1", "w2", "b2", "ffn_ln_w", "ffn_ln_b", "h0", "h", "conv_state")
+# rb_session_layer's fields -> parameter names under recurrent_layers.{i}.
+_PARAM_OF = {"w_in": "behavior_modeling.input.weight", "conv_w": "behavior_modeling.conv1d.weight",
+             "conv_b": "behavior_modeling.conv1d.bias", "w_gate": "behavior_modeling.gates.weight",
+             "b_gate": "behavior_modeling.gates.bias", "lam": "behavior_modeling.Lambda",
+             "w_out": "behavior_modeling.output.weight", "ln_w": "layer_norm.weight",
+             "ln_b": "layer_norm.bias", "w1": "ffn.w_1.weight", "b1": "ffn.w_1.bias",
+             "w2": "ffn.w_2.weight", "b2": "ffn.w_2.bias", "ffn_ln_w": "ffn.layer_norm.weight",
+             "ffn_ln_b": "ffn.layer_norm.bias"}
+
+
+class _Layer(ctypes.Structure):
+    """rb_session_layer (session/recblr_session.h)."""
+    _fields_ = [(name, ctypes.c_void_p) for name in _LAYER_FIELDS]
+
+
+class EncoderParams:
+    """The tensors and flags one step reads: a ``state_dict``-style mapping
+    with RecBLR's parameter names plus the configuration that is not in the
+    tensors' shapes."""
+
+    def __init__(self, tensors, num_layers: int, disable_conv1d: bool = False,
+                 disable_ffn: bool = False):
+        self.t = tensors
+        self.num_layers = int(num_layers)
+        self.use_conv = not disable_conv1d
+        self.use_ffn = not disable_ffn
+        emb = tensors["item_embedding.weight"]
+        self.V, self.d = emb.shape
+        self.H = tensors["recurrent_layers.0.behavior_modeling.Lambda"].shape[0]
+        self.K = tensors["recurrent_layers.0.behavior_modeling.conv1d.weight"].shape[-1]
+        self.device, self.dtype = emb.device, emb.dtype
+
+    @classmethod
+    def from_model(cls, model) -> "EncoderParams":
+        return cls(dict(model.named_parameters()), len(model.recurrent_layers),
+                   model.disable_conv1d, model.disable_ffn)
+
+    @classmethod
+    def from_state_dict(cls, state_dict, config) -> "EncoderParams":
+        only = bool(config.get("bd_lru_only", False))   # RecBLR.py:33-35
+        return cls(state_dict, config["num_layers"],
+                   only or bool(config.get("disable_conv1d", False)),
+                   only or bool(config.get("disable_ffn", False)))
+
+    def layer(self, i: int, field: str) -> torch.Tensor:
+        return self.t[f"recurrent_layers.{i}.{_PARAM_OF[field]}"]
+
+    def conv_w(self, i: int) -> torch.Tensor:
+        return self.layer(i, "conv_w").reshape(self.H, self.K)   # [H, 1, K] -> [H, K]
+
+    @property
+    def shape(self):
+        return (self.V, self.d, self.H, self.K, self.num_layers, self.use_conv, self.use_ffn)
+
+
+def _params(model_or_params) -> EncoderParams:
+    if isinstance(model_or_params, EncoderParams):
+        return model_or_params
+    return EncoderParams.from_model(model_or_params)
+
+
+def kernel_supports(d: int, H: int, K: int, num_layers: int) -> bool:
+    """Whether rb_session_step takes this shape: d and H multiples of 16 (the
+    MFMA tile), K in [1, 8], at most MAX_LAYERS layers, and the three LDS
+    activation buffers within a compute unit's LDS."""
+    if d % 16 or H % 16 or not 1 <= K <= 8 or not 1 <= num_layers <= MAX_LAYERS:
+        return False
+    return 0 < _lib.load_session().rb_session_lds_bytes(d, H) <= MAX_LDS
+
+
+class SessionState:
+    """The carried state of ``capacity`` session slots of one model, for the
+    window ``seq_len`` (see the module doc).  ``h[i] [N, H]``, ``conv[i]
+    [N, K-1, H]`` (None without a conv history), ``count [N]`` int64,
+    ``out [N, d]``, ``h0[i] [H]``; ``status``: the last call's row statuses."""
+
+    def __init__(self, model_or_params, capacity: int, seq_len: int | None = None):
+        p = _params(model_or_params)
+        if capacity <= 0:
+            raise ValueError("SessionState: capacity must be positive")
+        if seq_len is None:
+            seq_len = getattr(model_or_params, "max_seq_length", None)
+        if seq_len is None or seq_len <= 0:
+            raise ValueError("SessionState: seq_len must be a positive window length")
+        self.source = model_or_params
+        self.capacity, self.seq_len = int(capacity), int(seq_len)
+        self.shape = p.shape
+        self.device = p.device
+        N, kw = self.capacity, dict(device=p.device, dtype=torch.float32)
+        hist = p.use_conv and p.K > 1
+        self.h = [torch.empty((N, p.H), **kw) for _ in range(p.num_layers)]
+        self.conv = [torch.empty((N, p.K - 1, p.H), **kw) if hist else None
+                     for _ in range(p.num_layers)]
+        self.h0 = [torch.zeros((p.H,), **kw) for _ in range(p.num_layers)]
+        self.count = torch.empty((N,), device=p.device, dtype=torch.int64)
+        self.out = torch.empty((N, p.d), **kw)
+        self.status = torch.zeros((0,), device=p.device, dtype=torch.int32)
+        self._plan = None
+        self.reset()
+
+    @torch.no_grad()
+    def reset(self, slots=None) -> None:
+        """Re-initialise the slots (all of them by default) to the empty
+        history; h0 is recomputed from the current parameters."""
+        p = _params(self.source)
+        if p.shape != self.shape:
+            raise ValueError(f"SessionState.reset: the model's shape {p.shape} is not the one "
+                             f"the state was opened for {self.shape}")
+        P = pow2_pad_len(self.seq_len)
+        for i, h0 in enumerate(self.h0):
+            if not (P and p.use_conv):     # as recurrence.bd_lru: no prefix state
+                h0.zero_()
+                continue
+            args = [p.layer(i, f).detach().float() for f in ("conv_b", "w_gate", "b_gate", "lam")]
+            h0.copy_(kernels.pad_prefix_fwd(*args, P) if h0.device.type == "cuda"
+                     else pad_prefix_state(*args, P))
+        idx = slice(None) if slots is None else _slot_tensor(slots, self)
+        for h, h0, conv in zip(self.h, self.h0, self.conv):
+            h[idx] = h0
+            if conv is not None:
+                conv[idx] = 0.0
+        self.count[idx] = 0
+        self.out[idx] = 0.0
+
+
+def _slot_tensor(slots, state: SessionState) -> torch.Tensor:
+    """slots as an int64 tensor on the state's device.  A list or CPU tensor
+    is checked here (range, uniqueness); a device tensor is taken as is:
+    uniqueness is then the caller's precondition (no sync on the hot path),
+    and rb_session_step masks an out-of-range slot."""
+    if isinstance(slots, torch.Tensor) and slots.device.type != "cpu":
+        return slots.to(device=state.device, dtype=torch.int64).reshape(-1).contiguous()
+    host = torch.as_tensor(slots, dtype=torch.int64).reshape(-1)
+    if host.numel() and (int(host.min()) < 0 or int(host.max()) >= state.capacity):
+        raise ValueError(f"slots must lie in [0, {state.capacity})")
+    if torch.unique(host).numel() != host.numel():
+        raise ValueError("slots must be unique: a slot takes one event per call")
+    return host.to(state.device)
+
+
+def _rows(state: SessionState, items, slots):
+    items = torch.as_tensor(items, dtype=torch.int64).reshape(-1).to(state.device).contiguous()
+    B = items.numel()
+    if B == 0:
+        raise ValueError("items must hold at least one row")
+    if slots is None:
+        if B > state.capacity:
+            raise ValueError(f"{B} rows for a state of {state.capacity} slots")
+    else:
+        slots = _slot_tensor(slots, state)
+        if slots.numel() != B:
+            raise ValueError("items and slots must have the same length")
+    return items, slots, B
+
+
+def _match(p: EncoderParams, state: SessionState) -> None:
+    if p.shape != state.shape:
+        raise ValueError(f"the state was opened for a different model shape: {state.shape} "
+                         f"(V, d, H, K, layers, conv, ffn) vs the model's {p.shape}")
+    if p.device != state.device:
+        raise ValueError(f"the state lives on {state.device}, the model on {p.device}")
+
+
+def _ln(p: EncoderParams, prefix: str, x):
+    return F.layer_norm(x, (x.shape[-1],), p.t[prefix + "weight"], p.t[prefix + "bias"], eps=LN_EPS)
+
+
+@torch.no_grad()
+def step_reference(model_or_params, state: SessionState, items, slots=None) -> torch.Tensor:
+    """``step`` in plain torch ops (RecBLR.py:75-84 / :140-145 / :170-207 /
+    :218-227 at one position), on the state's device."""
+    p = _params(model_or_params)
+    _match(p, state)
+    items, slots, B = _rows(state, items, slots)
+    if slots is None:
+        slots = torch.arange(B, device=state.device)
+    slot_ok = (slots >= 0) & (slots < state.capacity)
+    item_ok = (items >= 0) & (items < p.V)
+    valid = slot_ok & item_ok & (items != 0)
+    status = torch.full((B,), NO_EVENT, device=state.device, dtype=torch.int32)
+    status[valid] = STEPPED
+    status[slot_ok & ~item_ok] = BAD_ITEM
+    status[~slot_ok] = BAD_SLOT
+    state.status = status
+    idx, x = slots[valid], None
+    if idx.numel():
+        x = _ln(p, "layer_norm.", p.t["item_embedding.weight"][items[valid]].float())
+    for i in range(p.num_layers if x is not None else 0):
+        W = {f: p.layer(i, f).float() for f in _PARAM_OF if f != "conv_w"}
+        H = p.H
+        xz = x @ W["w_in"].t()
+        u, z = xz[:, :H], xz[:, H:]
+        if p.use_conv:
+            win = u[:, None] if state.conv[i] is None else torch.cat(
+                [state.conv[i][idx], u[:, None]], dim=1)              # [n, K, H], oldest first
+            xc = F.silu(W["conv_b"] + (win * p.conv_w(i).float().t()[None]).sum(1))
+            if state.conv[i] is not None:
+                state.conv[i][idx] = win[:, 1:]
+        else:
+            xc = u
+        r, g = (xc @ W["w_gate"].t() + W["b_gate"]).split(H, dim=-1)
+        alpha = torch.exp(-F.softplus(W["lam"]) * torch.sigmoid(r))
+        beta = torch.sqrt(1 - alpha * alpha + 1e-8) * torch.sigmoid(g)
+        h = state.h[i][idx] * alpha + beta * xc
+        state.h[i][idx] = h
+        pre = f"recurrent_layers.{i}."
+        x = _ln(p, pre + "layer_norm.", (F.silu(z) * h) @ W["w_out"].t() + x)
+        if p.use_ffn:
+            f = F.silu(x @ W["w1"].t() + W["b1"]) @ W["w2"].t() + W["b2"]
+            x = _ln(p, pre + "ffn.layer_norm.", f + x)
+    if x is not None:
+        state.out[idx] = x
+        state.count[idx] += 1
+    y = state.out[slots.clamp(0, state.capacity - 1)]
+    y[~slot_ok] = 0.0
+    return y
+
+
+def _refuse(model, p: EncoderParams, state: SessionState) -> None:
+    """What the fused step cannot honour is an error that names the cause."""
+    if model.training:
+        raise ValueError("session step: the model is in training mode (dropout would be "
+                         "active); call model.eval()")
+    if state.device.type != "cuda":
+        raise RecBLRNativeError(f"session step: the state is on {state.device}; the HIP path "
+                                "needs a ROCm GPU (step_reference runs anywhere)")
+    for name, t in p.t.items():
+        if t.dtype != torch.float32:
+            raise RecBLRNativeError(f"session step: parameter {name} is {t.dtype}; the fused "
+                                    "step takes fp32 parameters only")
+    # the fused step cannot fire module hooks: refuse rather than skip them
+    g = torch.nn.modules.module
+    if g._global_forward_hooks or g._global_forward_pre_hooks:
+        raise RecBLRNativeError("session step: global forward hooks are registered; the fused "
+                                "step cannot fire hooks")
+    for name, m in model.named_modules():
+        if name and (m._forward_hooks or m._forward_pre_hooks):
+            raise RecBLRNativeError(f"session step: submodule {name} carries a forward hook; "
+                                    "the fused step cannot fire hooks")
+
+
+def _plan(p: EncoderParams, state: SessionState):
+    """The rb_session_layer array for (parameters, state), rebuilt only when a
+    tensor has moved."""
+    tensors = []
+    for i in range(p.num_layers):
+        row = {f: p.layer(i, f) for f in _PARAM_OF}
+        row["conv_w"] = p.conv_w(i)
+        if not p.use_ffn:
+            for f in ("w1", "b1", "w2", "b2", "ffn_ln_w", "ffn_ln_b"):
+                row[f] = None
+        if not p.use_conv:
+            row["conv_w"] = row["conv_b"] = None
+        row.update(h0=state.h0[i], h=state.h[i], conv_state=state.conv[i])
+        tensors.append(row)
+    key = tuple(t.data_ptr() if t is not None else 0 for row in tensors for t in row.values())
+    if state._plan is not None and state._plan[0] == key:
+        return state._plan[1]
+    arr = (_Layer * p.num_layers)()
+    for dst, row in zip(arr, tensors):
+        for f, t in row.items():
+            if t is not None and not t.is_contiguous():
+                raise ValueError(f"session step: {f} must be contiguous")
+            setattr(dst, f, t.data_ptr() if t is not None else None)
+    state._plan = (key, arr)
+    return arr
+
+
+def _step_kernel(p: EncoderParams, state: SessionState, layers, items, slots, y, status) -> None:
+    """The one launch (rb_session_step)."""
+    t = p.t
+    _lib.call_session(
+        "rb_session_step", ctypes.addressof(layers), p.num_layers,
+        t["item_embedding.weight"].data_ptr(), t["layer_norm.weight"].data_ptr(),
+        t["layer_norm.bias"].data_ptr(), LN_EPS, items.data_ptr(),
+        slots.data_ptr() if slots is not None else None, state.count.data_ptr(),
+        state.out.data_ptr(), y.data_ptr(), status.data_ptr(), items.numel(), state.capacity,
+        p.V, p.d, p.H, p.K, int(not p.use_conv), int(not p.use_ffn), kernels._stream(y))
+
+
+@torch.no_grad()
+def step(model, state: SessionState, items, slots=None) -> torch.Tensor:
+    """Append items[b] to slot slots[b] (slots None: slot b) and return the
+    rows' seq_output [B, d]: one launch for the whole encoder.  items: int64
+    [B], list or tensor; 0 = no event for that row.  slots must be unique: a
+    list or CPU tensor is checked, for a device tensor it is a precondition
+    (no sync on the hot path).  A shape the kernel refuses (kernel_supports)
+    runs step_reference instead."""
+    p = _params(model)
+    _refuse(model, p, state)
+    _match(p, state)
+    if not kernel_supports(p.d, p.H, p.K, p.num_layers):
+        return step_reference(p, state, items, slots)
+    items, slots, B = _rows(state, items, slots)
+    y = torch.empty((B, p.d), device=state.device, dtype=torch.float32)
+    status = torch.empty((B,), device=state.device, dtype=torch.int32)
+    with torch.cuda.device(state.device):
+        _step_kernel(p, state, _plan(p, state), items, slots, y, status)
+    state.status = status
+    return y
+
+
+@torch.no_grad()
+def prefill(model, state: SessionState, item_seq, item_seq_len, slots=None,
+            reset: bool = True) -> torch.Tensor:
+    """Open sessions from stored histories: item_seq [B, T] right-padded,
+    item_seq_len [B]; one step per column (item 0 for rows already
+    exhausted), so exact by construction.  The slots are reset first unless
+    reset=False (which appends to what they hold).  Returns the rows'
+    seq_output [B, d].  A state on the CPU steps with step_reference."""
+    item_seq = torch.as_tensor(item_seq, dtype=torch.int64)
+    if item_seq.dim() != 2:
+        raise ValueError("item_seq must be [B, T]")
+    host_len = getattr(item_seq_len, "_recblr_host_lengths", None)
+    if host_len is None and not (isinstance(item_seq_len, torch.Tensor)
+                                 and item_seq_len.device.type != "cpu"):
+        host_len = torch.as_tensor(item_seq_len)
+    B, T = item_seq.shape
+    if host_len is not None:        # known on the host: stop at the longest row
+        T = min(T, int(host_len.max())) if B else 0
+    item_seq = item_seq.to(state.device)
+    lens = torch.as_tensor(item_seq_len).to(state.device).reshape(-1, 1)
+    cols = torch.where(torch.arange(item_seq.shape[1], device=state.device)[None] < lens,
+                       item_seq, torch.zeros_like(item_seq)).t().contiguous()
+    if slots is not None:
+        slots = _slot_tensor(slots, state)
+    if reset:
+        state.reset(slots if slots is not None else torch.arange(B))
+    fn = step if state.device.type == "cuda" else step_reference
+    y = None
+    for t in range(T):
+        y = fn(model, state, cols[t], slots)
+    if y is None:
+        y = state.out[slots if slots is not None else slice(0, B)].clone()
+    return y

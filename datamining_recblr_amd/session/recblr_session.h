@@ -1,0 +1,94 @@
+/* recblr_session.h — stateful session inference (libdmrecblr_session.so).
+ *
+ * One entry point advances the whole RecBLR encoder by one event per session
+ * slot in one launch (python: datamining_recblr_amd/session.py).  Its own
+ * library, beside the product library, as the probe and experimental
+ * libraries are ("Stateful sessions").  Same conventions as the
+ * boundary (include/recblr_hip.h): raw device pointers, int status (0 = ok,
+ * RB_EINVAL = -1 for a bad argument, checked before any HIP call),
+ * rb_session_last_error_string() for the message, stream as void*. */
+#ifndef RECBLR_SESSION_H
+#define RECBLR_SESSION_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RB_SESSION_MAX_LAYERS 8
+/* slots per workgroup (the M of the fp32 MFMA tile) */
+#define RB_SESSION_TILE 16
+/* the LDS of one gfx950 compute unit: the step kernel's budget */
+#define RB_SESSION_MAX_LDS 163840
+/* row status written by rb_session_step */
+#define RB_SESSION_NO_EVENT 0
+#define RB_SESSION_STEPPED 1
+#define RB_SESSION_BAD_ITEM (-1)
+#define RB_SESSION_BAD_SLOT (-2)
+
+/* One RecurrentLayer (RecBLR.py:124-145): its parameters (host struct of
+ * device pointers, fp32, contiguous, 16-byte aligned) and the per-slot state
+ * it carries for N slots. */
+typedef struct {
+  const float* w_in;      /* [2H, d]  behavior_modeling.input.weight */
+  const float* conv_w;    /* [H, K]   conv1d.weight (unused with disable_conv1d) */
+  const float* conv_b;    /* [H]      conv1d.bias   (unused with disable_conv1d) */
+  const float* w_gate;    /* [2H, H]  gates.weight */
+  const float* b_gate;    /* [2H]     gates.bias */
+  const float* lam;       /* [H]      Lambda */
+  const float* w_out;     /* [d, H]   output.weight */
+  const float* ln_w;      /* [d]      layer_norm */
+  const float* ln_b;      /* [d] */
+  const float* w1;        /* [4d, d]  ffn.w_1 (the six ffn pointers unused with disable_ffn) */
+  const float* b1;        /* [4d] */
+  const float* w2;        /* [d, 4d]  ffn.w_2 */
+  const float* b2;        /* [d] */
+  const float* ffn_ln_w;  /* [d]      ffn.layer_norm */
+  const float* ffn_ln_b;  /* [d] */
+  const float* h0;        /* [H] state of a slot with count == 0 (the pad-prefix state,
+                             rb_pad_prefix_fwd); NULL = zeros */
+  float* h;               /* [N, H]       recurrent state, read when count > 0, written */
+  float* conv_state;      /* [N, K-1, H]  the last K-1 pre-conv rows, oldest first; zeros
+                             are read when count == 0 (unused with disable_conv1d or K == 1) */
+} rb_session_layer;
+
+/* ABI version of the session library (the product ABI it pairs with). */
+int rb_session_version(void);
+const char* rb_session_last_error_string(void);
+
+/* Dynamic LDS bytes the step kernel needs for (d, H); rb_session_step refuses
+ * shapes whose need exceeds the CU's 160 KiB. */
+int64_t rb_session_lds_bytes(int64_t d, int64_t H);
+
+/* One encoder step (RecBLR.py:75-84 at a single position; eval mode) for B
+ * rows in one launch.  Row b carries item items[b] for slot slots[b] (slots
+ * NULL: slot b); slots must be unique.  For an item v in [1, V):
+ *   x = LN(emb[v]); per layer: xz = x W_in^T, u | z = xz; xc = silu(conv_b +
+ *   sum_j conv_w[:, j] u_hist[j]) over the K-1 stored rows and u, history
+ *   shifted; r | i = xc W_g^T + b_g; alpha = exp(-softplus(Lambda) sigmoid(r));
+ *   beta = sqrt(1 - alpha^2 + 1e-8) sigmoid(i); h = alpha h + beta xc;
+ *   x = LN((silu(z) h) W_out^T + x); x = LN(w_2 silu(w_1 x + b_1) + b_2 + x)
+ *   (no conv with disable_conv1d, no FFN with disable_ffn; FFN width 4d);
+ *   out[slot] = x; count[slot] += 1.
+ * Item 0 is "no event": nothing of the slot is touched.  An item outside
+ * [0, V) or a slot outside [0, N) is never dereferenced: the row is masked
+ * and its state left alone.  y [B, d] (optional) receives the row's out
+ * (the stored one for a row that did not step; zeros for a bad slot) and
+ * status [B] int32 (optional) one of RB_SESSION_*.
+ * emb [V, d]; ln_w, ln_b [d] the embedding LayerNorm; eps for every
+ * LayerNorm; count [N] int64; out [N, d].  d and H multiples of 16, K in
+ * [1, 8], n_layers in [1, RB_SESSION_MAX_LAYERS].  One workgroup owns
+ * RB_SESSION_TILE consecutive rows through every layer; a row's arithmetic
+ * does not depend on the other rows of the call. */
+int rb_session_step(const rb_session_layer* layers, int64_t n_layers, const float* emb,
+                    const float* ln_w, const float* ln_b, float eps, const int64_t* items,
+                    const int64_t* slots, int64_t* count, float* out, float* y,
+                    int32_t* status, int64_t B, int64_t N, int64_t V, int64_t d, int64_t H,
+                    int64_t K, int disable_conv1d, int disable_ffn, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RECBLR_SESSION_H */

@@ -1,0 +1,93 @@
+// session_capi.hip — the extern "C" entry points of the session library
+// (recblr_session.h): argument checks, then the launcher in session_step.hip.
+// Built with hidden visibility, so its error helpers (rb::fail,
+// rb::launch_status) are its own and never interpose the product library's.
+#include "../csrc/common.h"
+#include "recblr_session.h"
+
+#include <string>
+
+namespace rb {
+
+namespace {
+thread_local std::string g_session_error;
+}
+
+int fail(const char* msg) {
+  g_session_error = msg;
+  return RB_EINVAL;
+}
+
+int launch_status(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    g_session_error = std::string(what) + ": " + hipGetErrorString(e);
+    return static_cast<int>(e);
+  }
+  return 0;
+}
+
+int64_t session_lds_bytes(int64_t d, int64_t H);
+int launch_session_step(const rb_session_layer* layers, int n_layers, const float* emb,
+                        const float* ln_w, const float* ln_b, float eps, const int64_t* items,
+                        const int64_t* slots, int64_t* count, float* out, float* y,
+                        int32_t* status, int64_t B, int64_t N, int64_t V, int d, int H, int K,
+                        bool use_conv, bool use_ffn, hipStream_t st);
+}  // namespace rb
+
+using namespace rb;
+
+extern "C" {
+
+#define RB_EXPORT __attribute__((visibility("default")))
+
+// the product library's rb_version() it pairs with
+RB_EXPORT int rb_session_version(void) { return RB_ABI_VERSION; }
+
+RB_EXPORT const char* rb_session_last_error_string(void) { return g_session_error.c_str(); }
+
+RB_EXPORT int64_t rb_session_lds_bytes(int64_t d, int64_t H) {
+  if (d <= 0 || H <= 0 || d > (1 << 20) || H > (1 << 20)) return RB_EINVAL;
+  return session_lds_bytes(d, H);
+}
+
+RB_EXPORT int rb_session_step(const rb_session_layer* layers, int64_t n_layers, const float* emb,
+                    const float* ln_w, const float* ln_b, float eps, const int64_t* items,
+                    const int64_t* slots, int64_t* count, float* out, float* y,
+                    int32_t* status, int64_t B, int64_t N, int64_t V, int64_t d, int64_t H,
+                    int64_t K, int disable_conv1d, int disable_ffn, void* stream) {
+  if (!layers || !emb || !ln_w || !ln_b || !items || !count || !out)
+    return fail("rb_session_step: null pointer");
+  if (n_layers < 1 || n_layers > RB_SESSION_MAX_LAYERS)
+    return fail("rb_session_step: n_layers must be in [1, 8]");
+  if (K < 1 || K > 8) return fail("rb_session_step: conv kernel size K must be in [1, 8]");
+  if (d <= 0 || H <= 0 || d % 16 || H % 16 || d > (1 << 20) || H > (1 << 20))
+    return fail("rb_session_step: d and H must be positive multiples of 16");
+  if (B <= 0 || N <= 0 || V <= 0) return fail("rb_session_step: B, N and V must be positive");
+  if (B >= (1LL << 31) || N >= (1LL << 31) || V >= (1LL << 31))
+    return fail("rb_session_step: B, N and V must be < 2^31");
+  if (session_lds_bytes(d, H) > RB_SESSION_MAX_LDS)
+    return fail("rb_session_step: shape needs more LDS than a compute unit has (160 KiB)");
+  if (!(eps > 0.0f)) return fail("rb_session_step: eps must be positive");
+  const bool use_conv = !disable_conv1d, use_ffn = !disable_ffn;
+  // every operand the MFMA streams is read 16 bytes per lane
+  if (!aligned16(emb) || !aligned16(out) || (y && !aligned16(y)))
+    return fail("rb_session_step: emb, out and y must be 16-byte aligned");
+  for (int64_t i = 0; i < n_layers; ++i) {
+    const rb_session_layer& L = layers[i];
+    if (!L.w_in || !L.w_gate || !L.b_gate || !L.lam || !L.w_out || !L.ln_w || !L.ln_b || !L.h)
+      return fail("rb_session_step: null pointer in a layer");
+    if (use_conv && (!L.conv_w || !L.conv_b || (K > 1 && !L.conv_state)))
+      return fail("rb_session_step: null conv pointer in a layer");
+    if (use_ffn && (!L.w1 || !L.b1 || !L.w2 || !L.b2 || !L.ffn_ln_w || !L.ffn_ln_b))
+      return fail("rb_session_step: null ffn pointer in a layer");
+    if (!aligned16(L.w_in) || !aligned16(L.w_gate) || !aligned16(L.w_out) ||
+        (use_ffn && (!aligned16(L.w1) || !aligned16(L.w2))))
+      return fail("rb_session_step: weight matrices must be 16-byte aligned");
+  }
+  return launch_session_step(layers, (int)n_layers, emb, ln_w, ln_b, eps, items, slots, count,
+                             out, y, status, B, N, V, (int)d, (int)H, (int)K, use_conv, use_ffn,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

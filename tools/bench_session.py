@@ -1,0 +1,99 @@
+#!/usr/bin/env python
+"""Per-event serving cost: RecBLR.session_step (one launch, O(1) in the
+history) against the only way to get the same rows without a carried state,
+RecBLR.forward over the full [B, L] history.
+
+Model: d = 128, 2 layers, expand 2 (H = 256), K = 4, L = 200, 10,544 items
+(BASELINE's C2 shape); B = 1, 64 and 2048 sessions with full-length
+histories.  Both paths run in eval mode under no_grad.  Each is warmed up,
+then timed in windows of back-to-back calls between two device events
+(ending in a synchronise); the two paths alternate window by window and the
+figure is the median window's time per call.  Before timing, the sessions
+are prefilled with the L items and their rows compared with forward's.
+
+Prints one JSON line; --out also writes it to a file."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from datamining_recblr_amd.model import RecBLR, attach_host_lengths  # noqa: E402
+from datamining_recblr_amd.recbole_compat import SyntheticDataset  # noqa: E402
+
+N_ITEMS, L = 10544, 200
+
+
+def window_ms(fn, calls: int) -> float:
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / calls
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 64, 2048])
+    ap.add_argument("--windows", type=int, default=9)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_session needs the GPU: a CPU timing says nothing about it")
+    dev = torch.device("cuda:0")
+    cfg = dict(hidden_size=128, loss_type="CE", num_layers=2, dropout_prob=0.2, expand=2,
+               d_conv=4, bd_lru_only=False, disable_conv1d=False, disable_ffn=False,
+               MAX_ITEM_LIST_LENGTH=L)
+    torch.manual_seed(2020)
+    model = RecBLR(cfg, SyntheticDataset(N_ITEMS)).to(dev).eval()
+    rows = []
+    with torch.no_grad():
+        for B in args.batches:
+            g = torch.Generator().manual_seed(B)
+            seq_h = torch.randint(1, N_ITEMS, (B, L), generator=g)
+            lens_h = torch.full((B,), L, dtype=torch.int64)
+            seq = seq_h.to(dev)
+            lens = attach_host_lengths(lens_h.to(dev), lens_h)   # forward without a host sync
+            state = model.session_open(B)
+            got = model.session_prefill(state, seq, lens)
+            ref = model(seq, lens)
+            err = (got - ref).abs().max().item()
+            nxt = torch.randint(1, N_ITEMS, (B,), generator=g).to(dev)
+            step = lambda: model.session_step(state, nxt)       # noqa: E731
+            full = lambda: model(seq, lens)                      # noqa: E731
+            step_calls = 200
+            full_calls = 20 if B <= 64 else 5
+            for _ in range(2):   # warm-up of both shapes
+                window_ms(step, step_calls)
+                window_ms(full, full_calls)
+            ts, tf = [], []
+            for _ in range(args.windows):   # alternate the two paths
+                ts.append(window_ms(step, step_calls))
+                tf.append(window_ms(full, full_calls))
+            s, f = statistics.median(ts), statistics.median(tf)
+            rows.append(dict(B=B, step_ms=round(s, 4), step_ms_min=round(min(ts), 4),
+                             step_ms_max=round(max(ts), 4), forward_ms=round(f, 4),
+                             forward_ms_min=round(min(tf), 4), forward_ms_max=round(max(tf), 4),
+                             forward_over_step=round(f / s, 1),
+                             prefill_vs_forward_max_abs_err=err))
+    line = json.dumps(dict(bench="session_step", d=128, layers=2, K=4, L=L, n_items=N_ITEMS,
+                           windows=args.windows, rows=rows))
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
