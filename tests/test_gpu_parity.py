@@ -154,6 +154,12 @@ def _model_from_case(case, cuda):
     return model.to(cuda).eval()
 
 
+# max|got - gold| / max|gold| of any golden gradient: twice the worst measured
+# on an MI355X over the six cases (6.0e-6, case 1, layer 1's output.weight;
+# the fp32 oracle is within 7e-6 of fp64 on these tensors)
+GOLDEN_GRAD_REL = 1.2e-5
+
+
 @pytest.mark.parametrize("idx", range(6))
 def test_model_vs_reference_golden(cuda, idx):
     case = load_golden("model_golden.pt")[idx]
@@ -165,7 +171,13 @@ def test_model_vs_reference_golden(cuda, idx):
     close(loss, case["loss"], what="loss")
     for n, p in model.named_parameters():
         if n in case["grads"]:
-            close(p.grad, case["grads"][n], what=f"d{n}")
+            gold = case["grads"][n]
+            close(p.grad, gold, what=f"d{n}")
+            # close()'s absolute 1e-4 is above most recurrence gradients here
+            # (max|gold| of Lambda, conv1d.weight, gates.*: 9e-7 .. 3e-5), so each
+            # gradient is also held to its own scale
+            rel = ((p.grad.cpu() - gold).abs().max() / gold.abs().max()).item()
+            assert rel <= GOLDEN_GRAD_REL, f"d{n}: {rel:.2e} of max|gold| {gold.abs().max():.2e}"
         else:
             assert p.grad is None or p.grad.abs().max() == 0, n
     with torch.no_grad():
