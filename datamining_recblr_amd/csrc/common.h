@@ -398,14 +398,51 @@ int launch_gemm_nt_bf16(const void* A, int64_t lda, int64_t M, int R, const void
 int launch_gemm_tn_h(const float* Y, int64_t ldy, const float* X, int64_t ldx, int64_t M, int N,
                      int K, const float* ymax, const float* xmax, float* parts, int S,
                      hipStream_t st);
-// byte offset of the weight-stationary kernel's planes inside an f16 weight
-// image of Bm [C, K] (after the persistent kernel's planes and the exponents)
+// ---- the f16 weight image -----------------------------------------------------
+// The image of Bm [C, R] (Bm = W, or W^T with transpose) that
+// k_split_weights_h (gemm_half.hip) writes and every f16x3 kernel with a
+// weight operand reads (rb_gemm_h_weight_bytes), three parts:
+//   * the 32-column planes at byte 0, v_mfma_f32_32x32x16_f16 operand order:
+//     16-B slot weight_slot32(R / 16, cb, kb, p, lane) = plane p (0 hi, 1 lo)
+//     of Bm[32 cb + lane % 32][16 kb + 8 (lane / 32) + 0..7] * 2^(kWeightScale - e_c);
+//   * the column exponents at byte C * R * 4: int32 e_c, the frexp exponent
+//     of max_r |Bm[c, r]| (0 for an all-zero column), so every scaled column
+//     max lies in [2^(kWeightScale - 1), 2^kWeightScale);
+//   * the 16-column planes at byte ws_image_offset(C, R) (only when
+//     R % 32 == 0), v_mfma_f32_16x16x32_f16 operand order: slot
+//     weight_slot16(R / 32, cb, ks, p, lane) = plane p of
+//     Bm[16 cb + lane % 16][32 ks + 8 (lane / 16) + 0..7], same scale.
+// A reader un-scales with e_c - kWeightScale, so writer and readers share
+// the one constant.
+constexpr int kWeightScale = 14;
+// a 16-B slot (in units of 16 B from its planes' start) and the column and
+// first k of the 8 values it holds.  S, the slot's type, and I, the type
+// the block index cb * nkb + kb is formed in, only choose the width of a
+// caller's address arithmetic: int64_t S for a whole image, int for an
+// offset inside a few column blocks (the formulas are linear, so an address
+// may be formed as slot(cb, 0, 0, lane) + slot(0, kb, p, 0)).
+template <class S>
+struct WeightSlot {
+  S slot;
+  int col, k0;
+};
+// nkb: the k-blocks of a column block (R / 16, R / 32)
+template <class S = int64_t, class I>
+__host__ __device__ inline WeightSlot<S> weight_slot32(int nkb, I cb, int kb, int p, int lane) {
+  return {((S)(cb * nkb + kb) * 2 + p) * 64 + lane, (int)cb * 32 + (lane & 31),
+          kb * 16 + 8 * (lane >> 5)};
+}
+template <class S = int64_t, class I>
+__host__ __device__ inline WeightSlot<S> weight_slot16(int nkb, I cb, int ks, int p, int lane) {
+  return {((S)(cb * nkb + ks) * 2 + p) * 64 + lane, (int)cb * 16 + (lane & 15),
+          ks * 32 + 8 * (lane >> 4)};
+}
+// byte offset of the 16-column planes (after the 32-column planes and the
+// exponents)
 __host__ __device__ inline int64_t ws_image_offset(int64_t C, int64_t K) {
   return C * K * 4 + ((C * 4 + 15) / 16) * 16;
 }
-// The parts of an f16 weight image Wf of Bm [C, R] (rb_gemm_h_weight_bytes):
-// the persistent kernel's planes, the column exponents, the weight-stationary
-// kernel's planes.
+// The three parts of an image Wf.
 struct WeightImage {
   const void* wf;
   const int* ew;

@@ -21,39 +21,17 @@
 // slot.  LDS: 160 KB, all of a gfx950 CU (3 A stages, A two k-steps ahead,
 // + 2 weight stages).  The launcher checks that the device grants it.
 #include "common.h"
+#include "lane_lds.h"
 
 #include <type_traits>
 
 namespace rb {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 __device__ __forceinline__ f32x4 mfma_bf16x16(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-template <typename T>
-__device__ __forceinline__ T bds_read16(uint32_t addr) {
-  T r;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr));
-  return r;
-}
-template <int OFF, typename T>
-__device__ __forceinline__ T bds_read16o(uint32_t addr) {
-  T r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-
-template <int N>
-__device__ __forceinline__ void bwait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // workgroup barrier that no LDS access is moved across
 __device__ __forceinline__ void bbarrier() { asm volatile("s_barrier" ::: "memory"); }
 
@@ -202,9 +180,9 @@ k_gemm_nt_bf(const __bf16* __restrict__ A, int64_t lda, int64_t M, int R,
     // own DMAs A(u), B(u) landed; younger than B(u): A(u + 1) (4, when it
     // exists) and the 16 stores at the end of step u - 1 (a whole tile's)
     if (u + 1 < U) {
-      if (stored_prev) bwait_vm<20>(); else bwait_vm<4>();
+      if (stored_prev) wait_vm<20>(); else wait_vm<4>();
     } else {
-      if (stored_prev) bwait_vm<16>(); else bwait_vm<0>();
+      if (stored_prev) wait_vm<16>(); else wait_vm<0>();
     }
     bbarrier();
     if (u + 1 < U) issueB((u + 1) & 1);
@@ -220,15 +198,15 @@ k_gemm_nt_bf(const __bf16* __restrict__ A, int64_t lda, int64_t M, int R,
     auto load = [&](auto S_) {
       constexpr int s = decltype(S_)::value;
 #pragma unroll
-      for (int rb = 0; rb < 4; ++rb) fa[s][rb] = bds_read16<bf16x8>(sa + (a_off[rb] ^ (s << 6)));
-      fb[s][0] = bds_read16o<(0 + s) * 1024, bf16x8>(sb);
-      fb[s][1] = bds_read16o<(2 + s) * 1024, bf16x8>(sb);
-      fb[s][2] = bds_read16o<(4 + s) * 1024, bf16x8>(sb);
-      fb[s][3] = bds_read16o<(6 + s) * 1024, bf16x8>(sb);
-      fb[s][4] = bds_read16o<(8 + s) * 1024, bf16x8>(sb);
-      fb[s][5] = bds_read16o<(10 + s) * 1024, bf16x8>(sb);
-      fb[s][6] = bds_read16o<(12 + s) * 1024, bf16x8>(sb);
-      fb[s][7] = bds_read16o<(14 + s) * 1024, bf16x8>(sb);
+      for (int rb = 0; rb < 4; ++rb) fa[s][rb] = lds_read16<bf16x8>(sa + (a_off[rb] ^ (s << 6)));
+      fb[s][0] = lds_read16o<(0 + s) * 1024, bf16x8>(sb);
+      fb[s][1] = lds_read16o<(2 + s) * 1024, bf16x8>(sb);
+      fb[s][2] = lds_read16o<(4 + s) * 1024, bf16x8>(sb);
+      fb[s][3] = lds_read16o<(6 + s) * 1024, bf16x8>(sb);
+      fb[s][4] = lds_read16o<(8 + s) * 1024, bf16x8>(sb);
+      fb[s][5] = lds_read16o<(10 + s) * 1024, bf16x8>(sb);
+      fb[s][6] = lds_read16o<(12 + s) * 1024, bf16x8>(sb);
+      fb[s][7] = lds_read16o<(14 + s) * 1024, bf16x8>(sb);
     };
     auto mma = [&](auto S_) {
       constexpr int s = decltype(S_)::value;

@@ -45,6 +45,7 @@
 //   lane offset, tile coordinates advance incrementally (divisions once per
 //   tile), and the overflow check is one compare + ballot per k16.
 #include "common.h"
+#include "f16x3.h"
 #include "nt_plan.h"
 
 #include <type_traits>
@@ -52,51 +53,13 @@
 namespace rb {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kTA = 4;       // row scale target: first-k16 row max in [2^(kTA-1), 2^kTA)
 constexpr int kHead = 11;    // later values up to 2^(kTA + kHead) = 2^15 (fp16 max 65504)
-constexpr int kTW = 14;      // weight column scale target: column max in [2^13, 2^14)
+constexpr int kTRedo = 14;   // row scale target of the cold recompute tail (exact row max)
 constexpr int kSent = -4096; // row exponent of a row that has been all zero so far
 
-// 2 fp32 (already scaled) -> hi, lo fp16 pairs (v_cvt_pk_f16_f32, RNE; the
-// residual is exact in fp32)
-__device__ __forceinline__ void split2h(f32x2 x, f16x2& h0, f16x2& h1) {
-  h0 = __builtin_convertvector(x, f16x2);
-  const f32x2 r = x - __builtin_convertvector(h0, f32x2);
-  h1 = __builtin_convertvector(r, f16x2);
-}
-
-__device__ __forceinline__ f32x16 mfma_h(f16x8 a, f16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-// max(|a|, |b|, |c|) in one instruction (no NaN canonicalisation: a NaN input
-// propagates to the output through the MFMA anyway)
-__device__ __forceinline__ float max3abs(float a, float b, float c) {
-  float r;
-  asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-
-__device__ __forceinline__ float max8abs(f32x4 x, f32x4 y) {
-  float m = max3abs(x[0], x[1], x[2]);
-  m = max3abs(m, x[3], y[0]);
-  m = max3abs(m, y[1], y[2]);
-  float r;
-  asm("v_max_f32 %0, %1, |%2|" : "=v"(r) : "v"(m), "v"(y[3]));
-  return r;
-}
-
 // ---------------------------------------------------------------------------
-// Weight image: Bm [C, R] (Bm = W, or W^T with transpose) ->
-//   planes: Wf[((cb * (R/16) + kb) * 2 + p) * 64 + lane] (16 B each) = plane p
-//     of Bm[cb*32 + (lane & 31)][kb*16 + 8*(lane >> 5) + 0..7] * 2^(kTW - e_c)
-//   exps:   int32 e_c at byte offset C*R*4 (frexp exponent of max_r |Bm[c, r]|)
+// The weight image of Bm [C, R] (layout: common.h, "the f16 weight image").
 // One workgroup per (job, 32-column block).
 struct SplitJobsH {
   const float* W[RB_MAX_SPLIT_JOBS];
@@ -155,19 +118,14 @@ __global__ void __launch_bounds__(256) k_split_weights_h(const SplitJobsH jobs) 
     float m = smax[tid * 8];
 #pragma unroll
     for (int q = 1; q < 8; ++q) m = fmaxf(m, smax[tid * 8 + q]);
-    const int e = m > 0.0f ? __builtin_amdgcn_frexp_expf(m) : 0;
+    const int e = exp_of(m);
     sexp[tid] = e;
     int* ew = reinterpret_cast<int*>(reinterpret_cast<char*>(jobs.Wf[j]) + (int64_t)C * R * 4);
     ew[cb * 32 + tid] = e;
   }
   __syncthreads();
-  const int KB = R / 16;
-  for (int it = tid; it < KB * 64; it += 256) {
-    const int kb = it >> 6, lane = it & 63;
-    const int c = cb * 32 + (lane & 31);
-    const int r0 = kb * 16 + 8 * (lane >> 5);
-    const int sh = kTW - sexp[lane & 31];
-    f16x8 o0, o1;
+  // the two planes of Bm[c][r0 .. r0 + 7], scaled by 2^sh
+  auto planes = [&](int c, int r0, int sh, f16x8& o0, f16x8& o1) {
 #pragma unroll
     for (int q = 0; q < 8; q += 2) {
       const f32x2 x = {__builtin_amdgcn_ldexpf(bm(c, r0 + q), sh),
@@ -177,36 +135,28 @@ __global__ void __launch_bounds__(256) k_split_weights_h(const SplitJobsH jobs) 
       o0[q] = h0[0]; o0[q + 1] = h0[1];
       o1[q] = h1[0]; o1[q + 1] = h1[1];
     }
-    f16x8* dst = jobs.Wf[j] + ((int64_t)(cb * KB + kb) * 2) * 64 + lane;
-    dst[0] = o0;
-    dst[64] = o1;
+  };
+  const int KB = R / 16;
+  for (int it = tid; it < KB * 64; it += 256) {
+    const int kb = it >> 6, lane = it & 63;
+    const auto w0 = weight_slot32(KB, cb, kb, 0, lane);
+    f16x8 o0, o1;
+    planes(w0.col, w0.k0, kWeightScale - sexp[lane & 31], o0, o1);
+    jobs.Wf[j][w0.slot] = o0;
+    jobs.Wf[j][weight_slot32(KB, cb, kb, 1, lane).slot] = o1;
   }
-  // the weight-stationary kernel's image of the same 32 columns (gemm_ws.hip,
-  // v_mfma_f32_16x16x32_f16 operand order, same column exponents) at
-  // ws_image_offset(C, R): Wi[((c16 * KS + s) * 2 + p) * 64 + lane] = plane p
-  // of Bm[16 c16 + (lane & 15)][32 s + 8 (lane >> 4) + 0..7]
+  // the same 32 columns as two 16-column blocks of the weight-stationary
+  // kernel's planes (gemm_ws.hip), same column exponents
   if (R % 32 == 0) {
     f16x8* wi = reinterpret_cast<f16x8*>(reinterpret_cast<char*>(jobs.Wf[j]) + ws_image_offset(C, R));
     const int KS = R / 32;
     for (int it = tid; it < 2 * KS * 64; it += 256) {
       const int h = it / (KS * 64), s = (it >> 6) % KS, lane = it & 63;
-      const int cl = 16 * h + (lane & 15);
-      const int c = cb * 32 + cl;
-      const int r0 = 32 * s + 8 * (lane >> 4);
-      const int sh = kTW - sexp[cl];
+      const auto w0 = weight_slot16(KS, 2 * cb + h, s, 0, lane);
       f16x8 o0, o1;
-#pragma unroll
-      for (int q = 0; q < 8; q += 2) {
-        const f32x2 x = {__builtin_amdgcn_ldexpf(bm(c, r0 + q), sh),
-                         __builtin_amdgcn_ldexpf(bm(c, r0 + q + 1), sh)};
-        f16x2 h0, h1;
-        split2h(x, h0, h1);
-        o0[q] = h0[0]; o0[q + 1] = h0[1];
-        o1[q] = h1[0]; o1[q + 1] = h1[1];
-      }
-      f16x8* dst = wi + ((int64_t)((2 * cb + h) * KS + s) * 2) * 64 + lane;
-      dst[0] = o0;
-      dst[64] = o1;
+      planes(w0.col, w0.k0, kWeightScale - sexp[16 * h + (lane & 15)], o0, o1);
+      wi[w0.slot] = o0;
+      wi[weight_slot16(KS, 2 * cb + h, s, 1, lane).slot] = o1;
     }
   }
 }
@@ -244,50 +194,6 @@ struct NtCfg {
   static constexpr int RING = NSA * N_A_STAGE + N_NSB * B_STAGE;
   static constexpr int LDS = RING + N_MAXC * 8 + N_WAVES * N_MAXFLAG * 4;
 };
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-template <typename T>
-__device__ __forceinline__ T hds_read16(uint32_t addr) {
-  T r;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr));
-  return r;
-}
-__device__ __forceinline__ int hds_read_i32(uint32_t addr) {
-  int r;
-  asm volatile("ds_read_b32 %0, %1" : "=v"(r) : "v"(addr));
-  return r;
-}
-
-template <int N>
-__device__ __forceinline__ void hwait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// quad_perm DPP moves (lane k of each quad reads lane k ^ 1 / k ^ 2)
-__device__ __forceinline__ float dpp_xor1(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float dpp_xor2(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, false));
-}
-
-// 4 x 4 transpose inside each lane quad: on entry lane k of a quad holds
-// column k (v[r] = row r), on exit row k (v[c] = column c).  Two butterfly
-// stages (lane distance 2, then 1), each a select + DPP move + select.
-__device__ __forceinline__ void quad_transpose(float (&v)[4], int lane) {
-  const bool b1 = (lane & 2) != 0, b0 = (lane & 1) != 0;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const float y = dpp_xor2(b1 ? v[r] : v[r + 2]);
-    if (b1) v[r] = y; else v[r + 2] = y;
-  }
-#pragma unroll
-  for (int r = 0; r < 4; r += 2) {
-    const float y = dpp_xor1(b0 ? v[r] : v[r + 1]);
-    if (b0) v[r] = y; else v[r + 1] = y;
-  }
-}
 
 // ACT (the FeedForward's first projection, RecBLR.py:219-221): a second
 // output act = dropout(silu(out)) — out with the bias, i.e. the activation's
@@ -415,6 +321,9 @@ __device__ __forceinline__ void nt_h_body(char* smem, const int bid, const int G
   auto b_tile = [&]() {
     int mt, ct;
     tile_of(b_i, mt, ct);
+    // weight_slot32(KB16, ct * N_NB, 0, 0, lane); the steps' offsets below are
+    // weight_slot32(KB16, n, 2 b_kt + s, p, 0) (written out: one folded
+    // 64-bit product and 32-bit offsets)
     b_base = Wf + (int64_t)ct * N_NB * KB16 * 2 * 64 + lane;
   };
   auto issueB = [&]() {
@@ -628,13 +537,13 @@ __device__ __forceinline__ void nt_h_body(char* smem, const int bid, const int G
       if constexpr (N_LA == 1) {
         // A(u) itself was issued in step u-1 (after B(u)): only the stores
         // issued after it may stay in flight
-        if (stored_prev) hwait_vm<NST>(); else hwait_vm<0>();
+        if (stored_prev) wait_vm<NST>(); else wait_vm<0>();
       } else if (ya) {
-        if (stored_prev) hwait_vm<4 + NST>(); else hwait_vm<4>();
+        if (stored_prev) wait_vm<4 + NST>(); else wait_vm<4>();
       } else if (u == 0 && U > 1) {
-        hwait_vm<4 * (N_LA - 1)>();
+        wait_vm<4 * (N_LA - 1)>();
       } else {
-        if (stored_prev) hwait_vm<NST>(); else hwait_vm<0>();
+        if (stored_prev) wait_vm<NST>(); else wait_vm<0>();
       }
     }
     __builtin_amdgcn_s_barrier();
@@ -648,10 +557,10 @@ __device__ __forceinline__ void nt_h_body(char* smem, const int bid, const int G
     const uint32_t sa = smem_base + c_slot_a * N_A_STAGE;
     const uint32_t sb = smem_base + N_NSA * N_A_STAGE + c_slot_b * N_B_STAGE + lane * 16;
     auto substep = [&](int s) {
-      const f32x4 x0 = hds_read16<f32x4>(sa + a_rd[s][0]);
-      const f32x4 x1 = hds_read16<f32x4>(sa + a_rd[s][1]);
+      const f32x4 x0 = lds_read16<f32x4>(sa + a_rd[s][0]);
+      const f32x4 x1 = lds_read16<f32x4>(sa + a_rd[s][1]);
       // B fragments two column blocks ahead of the MFMAs that use them
-      auto rb = [&](int n, int p) { return hds_read16<f16x8>(sb + ((n * 2 + s) * 2 + p) * 1024); };
+      auto rb = [&](int n, int p) { return lds_read16<f16x8>(sb + ((n * 2 + s) * 2 + p) * 1024); };
       f16x8 bq[N_NB][2];
       bq[0][0] = rb(0, 0); bq[0][1] = rb(0, 1); bq[1][0] = rb(1, 0); bq[1][1] = rb(1, 1);
       f32x4 xa = x0, xb = x1;
@@ -690,9 +599,7 @@ __device__ __forceinline__ void nt_h_body(char* smem, const int bid, const int G
           asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bq[n][0]), "+v"(bq[n][1]));
         else
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bq[n][0]), "+v"(bq[n][1]));
-        acc[n] = mfma_h(a1, bq[n][0], acc[n]);
-        acc[n] = mfma_h(a0, bq[n][1], acc[n]);
-        acc[n] = mfma_h(a0, bq[n][0], acc[n]);
+        acc[n] = mfma3_h(a0, a1, bq[n][0], bq[n][1], acc[n]);
         if (n + 2 < N_NB) {
           bq[n + 2][0] = rb(n + 2, 0);
           bq[n + 2][1] = rb(n + 2, 1);
@@ -718,11 +625,11 @@ __device__ __forceinline__ void nt_h_body(char* smem, const int bid, const int G
       }
       int ecol[N_NB];
 #pragma unroll
-      for (int n = 0; n < N_NB; ++n) ecol[n] = hds_read_i32(s_ew_addr + (cur_ct * N_BN + n * 32 + ccol) * 4);
+      for (int n = 0; n < N_NB; ++n) ecol[n] = lds_read_i32(s_ew_addr + (cur_ct * N_BN + n * 32 + ccol) * 4);
       if (BIAS) {
 #pragma unroll
         for (int n = 0; n < N_NB; ++n)
-          pbias[n] = __builtin_bit_cast(float, hds_read_i32(s_bias_addr + (cur_ct * N_BN + n * 32 + ccol) * 4));
+          pbias[n] = __builtin_bit_cast(float, lds_read_i32(s_bias_addr + (cur_ct * N_BN + n * 32 + ccol) * 4));
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -733,7 +640,7 @@ __device__ __forceinline__ void nt_h_body(char* smem, const int bid, const int G
       if constexpr (DEFER) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
-          const int erj = __shfl(er, crow(j)) - kTA - kTW;
+          const int erj = __shfl(er, crow(j)) - kTA - kWeightScale;
 #pragma unroll
           for (int n = 0; n < N_NB; ++n) {
             pend[n][j] = __builtin_amdgcn_ldexpf(acc[n][j], erj + ecol[n]);
@@ -750,7 +657,7 @@ __device__ __forceinline__ void nt_h_body(char* smem, const int bid, const int G
           pend_full = full;
 #pragma unroll
           for (int j = 0; j < 16; ++j) {
-            const int erj = __shfl(er, crow(j)) - kTA - kTW;
+            const int erj = __shfl(er, crow(j)) - kTA - kWeightScale;
 #pragma unroll
             for (int n = 0; n < N_NB; ++n) acc[n][j] = __builtin_amdgcn_ldexpf(acc[n][j], erj + ecol[n]);
           }
@@ -808,7 +715,7 @@ __device__ __forceinline__ void nt_h_body(char* smem, const int bid, const int G
   // exact max known first (no overflow possible), operands straight from
   // global memory, stored directly (after this wave's earlier stores)
   if (nflag > 0) {
-    hwait_vm<0>();
+    wait_vm<0>();
     const int ntodo = nflag > N_MAXFLAG ? my_tiles : nflag;
     // DACT, every tile redone: the wave's column sums start over
     if (DACT && nflag > N_MAXFLAG)
@@ -828,11 +735,11 @@ __device__ __forceinline__ void nt_h_body(char* smem, const int bid, const int G
         m = fmaxf(m, max8abs(p, q));
       }
       m = fmaxf(m, __shfl_xor(m, 32));
-      const int e = m > 0.0f ? __builtin_amdgcn_frexp_expf(m) : 0;
-      const float sc = __builtin_amdgcn_ldexpf(1.0f, kTW - e);  // row max < 2^14
+      const int e = exp_of(m);
+      const float sc = __builtin_amdgcn_ldexpf(1.0f, kTRedo - e);  // row max < 2^14
       int erow[16];  // the exact exponent of each C-layout row
 #pragma unroll
-      for (int j = 0; j < 16; ++j) erow[j] = __shfl(e, crow(j)) - 2 * kTW;
+      for (int j = 0; j < 16; ++j) erow[j] = __shfl(e, crow(j)) - kTRedo - kWeightScale;
       // one column block at a time (the A row is re-read per block from L2:
       // a cold path, kept to one accumulator block of registers)
       for (int n = 0; n < N_NB; ++n) {
@@ -843,19 +750,11 @@ __device__ __forceinline__ void nt_h_body(char* smem, const int bid, const int G
           const f32x4 p = *reinterpret_cast<const f32x4*>(arow + kb * 16);
           const f32x4 q = *reinterpret_cast<const f32x4*>(arow + kb * 16 + 4);
           f16x8 a0, a1;
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const f32x2 v = (t < 2 ? f32x2{p[2 * t], p[2 * t + 1]} : f32x2{q[2 * t - 4], q[2 * t - 3]}) * sc;
-            f16x2 h0, h1;
-            split2h(v, h0, h1);
-            a0[2 * t] = h0[0]; a0[2 * t + 1] = h0[1];
-            a1[2 * t] = h1[0]; a1[2 * t + 1] = h1[1];
-          }
+          split8(p, q, sc, a0, a1);
+          // weight_slot32(KB16, ct * N_NB + n, kb, 0 / 1, lane)
           const f16x8* bp = Wf + ((int64_t)((ct * N_NB + n) * KB16 + kb) * 2) * 64 + lane;
           const f16x8 b0 = bp[0], b1 = bp[64];
-          c = mfma_h(a1, b0, c);
-          c = mfma_h(a0, b1, c);
-          c = mfma_h(a0, b0, c);
+          c = mfma3_h(a0, a1, b0, b1, c);
         }
         const int col = ct * N_BN + n * 32 + ccol;
         const int ecol = s_ew[col];
@@ -1001,10 +900,6 @@ __device__ __forceinline__ uint32_t tn_off(int col, int chunk) {
   return col * T_PITCH + ((chunk ^ ((col >> 4) & 3)) << 4);
 }
 
-__device__ __forceinline__ void hds_write16(uint32_t addr, f16x8 v) {
-  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-
 template <int NBN, int NBK>
 __device__ __attribute__((noinline)) void tn_percol(char* smem, const float* __restrict__ Y, int64_t ldy, const float* __restrict__ X,
                                         int64_t ldx, int64_t M, int N, int K,
@@ -1060,8 +955,7 @@ __device__ __forceinline__ void tn_body(char* smem, const float* __restrict__ Y,
     my = fmaxf(my, red[w]);
     mx = fmaxf(mx, red[NW + w]);
   }
-  const int ey = my > 0.0f ? __builtin_amdgcn_frexp_expf(my) : 0;
-  const int ex = mx > 0.0f ? __builtin_amdgcn_frexp_expf(mx) : 0;
+  const int ey = exp_of(my), ex = exp_of(mx);
   __syncthreads();
 
   // conversion role: threads [0, YC) load dY, [YC, YC + XC) load X (YC / 4
@@ -1152,8 +1046,8 @@ __device__ __forceinline__ void tn_body(char* smem, const float* __restrict__ Y,
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       const uint32_t off = tn_off(4 * cc + 2 * p + c, rg);
-      hds_write16(img + off, h0[c]);
-      hds_write16(img + plane + off, h1[c]);
+      lds_write16(img + off, h0[c]);
+      lds_write16(img + plane + off, h1[c]);
     }
   };
 
@@ -1189,14 +1083,14 @@ __device__ __forceinline__ void tn_body(char* smem, const float* __restrict__ Y,
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const uint32_t ob = tn_off(64 * wk + 32 * j + (lane & 31), 2 * st + h);
-        b[j][0] = hds_read16<f16x8>(ix + ob);
-        b[j][1] = hds_read16<f16x8>(ix + CF::XPLANE + ob);
+        b[j][0] = lds_read16<f16x8>(ix + ob);
+        b[j][1] = lds_read16<f16x8>(ix + CF::XPLANE + ob);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const uint32_t oa = tn_off(64 * wm + 32 * i + (lane & 31), 2 * st + h);
-        f16x8 a0 = hds_read16<f16x8>(iy + oa);
-        f16x8 a1 = hds_read16<f16x8>(iy + CF::YPLANE + oa);
+        f16x8 a0 = lds_read16<f16x8>(iy + oa);
+        f16x8 a1 = lds_read16<f16x8>(iy + CF::YPLANE + oa);
         if (i == 0)
           asm volatile("s_waitcnt lgkmcnt(0)"
                        : "+v"(a0), "+v"(a1), "+v"(b[0][0]), "+v"(b[0][1]), "+v"(b[1][0]),
@@ -1205,9 +1099,7 @@ __device__ __forceinline__ void tn_body(char* smem, const float* __restrict__ Y,
           asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a0), "+v"(a1));
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          acc[i][j] = mfma_h(a1, b[j][0], acc[i][j]);
-          acc[i][j] = mfma_h(a0, b[j][1], acc[i][j]);
-          acc[i][j] = mfma_h(a0, b[j][0], acc[i][j]);
+          acc[i][j] = mfma3_h(a0, a1, b[j][0], b[j][1], acc[i][j]);
         }
       }
       if constexpr (CONV && LATE) convert_pair(r, nbuf, st);
@@ -1282,7 +1174,7 @@ __device__ __forceinline__ void tn_body(char* smem, const float* __restrict__ Y,
                             fmaxf(s_cm[2 * NCOL + col], s_cm[3 * NCOL + col]));
       const int ec = col < CF::YC ? ey : ex;   // the chunk exponent
       if (m > 0.0f && m < __builtin_amdgcn_ldexpf(1.0f, ec - 16)) *s_redo = 1;   // all store 1
-      const int e = m > 0.0f ? __builtin_amdgcn_frexp_expf(m) : 0;
+      const int e = exp_of(m);
       const int slot = col < CF::YC ? col * T_PITCH : 2 * CF::YPLANE + (col - CF::YC) * T_PITCH;
       *reinterpret_cast<int*>(smem + slot + 64) = e;
     }

@@ -20,49 +20,17 @@
 //   over the slice: column magnitudes spread over any range keep 22 bits),
 //   and the 8 un-scaled partials are summed in LDS in wave order.
 #include "common.h"
+#include "f16x3.h"
 
 namespace rb {
 namespace {
 
-typedef _Float16 f16x8s __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2s __attribute__((ext_vector_type(2)));
-typedef float f32x16s __attribute__((ext_vector_type(16)));
-typedef float f32x4s __attribute__((ext_vector_type(4)));
-typedef float f32x2s __attribute__((ext_vector_type(2)));
-
-constexpr int kSW = 14;   // operand scale: max lands in [2^13, 2^14)
-
-__device__ __forceinline__ void split2s(f32x2s x, f16x2s& h0, f16x2s& h1) {
-  h0 = __builtin_convertvector(x, f16x2s);
-  const f32x2s r = x - __builtin_convertvector(h0, f32x2s);
-  h1 = __builtin_convertvector(r, f16x2s);
-}
-
-__device__ __forceinline__ void split8(f32x4s p, f32x4s q, float sc, f16x8s& a0, f16x8s& a1) {
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const f32x2s v = (t < 2 ? f32x2s{p[2 * t], p[2 * t + 1]} : f32x2s{q[2 * t - 4], q[2 * t - 3]}) * sc;
-    f16x2s h0, h1;
-    split2s(v, h0, h1);
-    a0[2 * t] = h0[0]; a0[2 * t + 1] = h0[1];
-    a1[2 * t] = h1[0]; a1[2 * t + 1] = h1[1];
-  }
-}
-
-__device__ __forceinline__ f32x16s mfma3(f16x8s a0, f16x8s a1, f16x8s b0, f16x8s b1, f32x16s c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ int exp_of(float m) {
-  return m > 0.0f ? __builtin_amdgcn_frexp_expf(m) : 0;
-}
+constexpr int kSW = 14;   // row / operand scale (not the weights'): max lands in [2^13, 2^14)
 
 template <bool BIAS>
 __global__ void __launch_bounds__(512) k_gemm_nt_hs(const float* __restrict__ A, int64_t lda,
                                                     int64_t M, int R,
-                                                    const f16x8s* __restrict__ Wf,
+                                                    const f16x8* __restrict__ Wf,
                                                     const int* __restrict__ ew, int C,
                                                     const float* __restrict__ bias,
                                                     float* __restrict__ out, int64_t ldo,
@@ -70,7 +38,7 @@ __global__ void __launch_bounds__(512) k_gemm_nt_hs(const float* __restrict__ A,
   constexpr int KMAX = 8;   // k16 blocks per wave held in registers (R <= 8 x 8 x 16 = 1024)
   __shared__ float s_max[8][32];
   __shared__ int s_er[32];
-  __shared__ f32x16s s_acc[8][64];
+  __shared__ f32x16 s_acc[8][64];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int64_t r0 = (int64_t)blockIdx.x * 32;
@@ -81,17 +49,17 @@ __global__ void __launch_bounds__(512) k_gemm_nt_hs(const float* __restrict__ A,
   int64_t row = r0 + (lane & 31);
   row = row < M ? row : M - 1;
   const float* arow = A + row * lda + 8 * (lane >> 5);
-  const f16x8s* wb = Wf + (int64_t)cb * KB * 2 * 64 + lane;
-  f32x4s p[KMAX], q[KMAX];
-  f16x8s b0[KMAX], b1[KMAX];
+  const f16x8* wb = Wf + weight_slot32(KB, (int64_t)cb, 0, 0, lane).slot;
+  f32x4 p[KMAX], q[KMAX];
+  f16x8 b0[KMAX], b1[KMAX];
 #pragma unroll
   for (int j = 0; j < KMAX; ++j) {
     if (kb0 + j < kb1) {
       const int kb = kb0 + j;
-      p[j] = *reinterpret_cast<const f32x4s*>(arow + kb * 16);
-      q[j] = *reinterpret_cast<const f32x4s*>(arow + kb * 16 + 4);
-      b0[j] = wb[(kb * 2) * 64];
-      b1[j] = wb[(kb * 2 + 1) * 64];
+      p[j] = *reinterpret_cast<const f32x4*>(arow + kb * 16);
+      q[j] = *reinterpret_cast<const f32x4*>(arow + kb * 16 + 4);
+      b0[j] = wb[weight_slot32<int>(KB, 0, kb, 0, 0).slot];
+      b1[j] = wb[weight_slot32<int>(KB, 0, kb, 1, 0).slot];
     }
   }
   // exact row max over R: each wave's slice, then the 8 slices in LDS
@@ -121,15 +89,15 @@ __global__ void __launch_bounds__(512) k_gemm_nt_hs(const float* __restrict__ A,
     if (tid == 0) rmax[blockIdx.x] = g;
   }
   const float sc = __builtin_amdgcn_ldexpf(1.0f, kSW - s_er[lane & 31]);
-  f32x16s acc;
+  f32x16 acc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
 #pragma unroll
   for (int j = 0; j < KMAX; ++j) {
     if (kb0 + j < kb1) {
-      f16x8s a0, a1;
+      f16x8 a0, a1;
       split8(p[j], q[j], sc, a0, a1);
-      acc = mfma3(a0, a1, b0[j], b1[j], acc);
+      acc = mfma3_h(a0, a1, b0[j], b1[j], acc);
     }
   }
   s_acc[wave][lane] = acc;
@@ -149,7 +117,7 @@ __global__ void __launch_bounds__(512) k_gemm_nt_hs(const float* __restrict__ A,
     const int rr = 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
     const int64_t r = r0 + rr;
     if (r < M) {
-      const float o = __builtin_amdgcn_ldexpf(v, s_er[rr] + ec - 2 * kSW);
+      const float o = __builtin_amdgcn_ldexpf(v, s_er[rr] + ec - kSW - kWeightScale);
       out[r * ldo + col] = BIAS ? o + bv : o;
     }
   }
@@ -159,7 +127,7 @@ __global__ void __launch_bounds__(512) k_gemm_tn_hs(const float* __restrict__ Y,
                                                     const float* __restrict__ X, int64_t ldx,
                                                     int64_t M, int N, int K,
                                                     float* __restrict__ dw, int accumulate) {
-  __shared__ f32x16s s_acc[8][64];
+  __shared__ f32x16 s_acc[8][64];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n0 = blockIdx.y * 32, k0 = blockIdx.x * 32;
@@ -186,7 +154,7 @@ __global__ void __launch_bounds__(512) k_gemm_tn_hs(const float* __restrict__ Y,
   const int ey = exp_of(my), ex = exp_of(mx);
   const float sy = __builtin_amdgcn_ldexpf(1.0f, kSW - ey);
   const float sx = __builtin_amdgcn_ldexpf(1.0f, kSW - ex);
-  f32x16s acc;
+  f32x16 acc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
   // chunks of 4 steps: 64 loads per lane in flight before the MFMAs
@@ -204,12 +172,12 @@ __global__ void __launch_bounds__(512) k_gemm_tn_hs(const float* __restrict__ Y,
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       if (sc0 + u < s_end) {
-        f16x8s a0, a1, b0, b1;
-        split8(f32x4s{yv[u][0], yv[u][1], yv[u][2], yv[u][3]},
-               f32x4s{yv[u][4], yv[u][5], yv[u][6], yv[u][7]}, sy, a0, a1);
-        split8(f32x4s{xv[u][0], xv[u][1], xv[u][2], xv[u][3]},
-               f32x4s{xv[u][4], xv[u][5], xv[u][6], xv[u][7]}, sx, b0, b1);
-        acc = mfma3(a0, a1, b0, b1, acc);
+        f16x8 a0, a1, b0, b1;
+        split8(f32x4{yv[u][0], yv[u][1], yv[u][2], yv[u][3]},
+               f32x4{yv[u][4], yv[u][5], yv[u][6], yv[u][7]}, sy, a0, a1);
+        split8(f32x4{xv[u][0], xv[u][1], xv[u][2], xv[u][3]},
+               f32x4{xv[u][4], xv[u][5], xv[u][6], xv[u][7]}, sx, b0, b1);
+        acc = mfma3_h(a0, a1, b0, b1, acc);
       }
     }
   }
@@ -224,7 +192,7 @@ __global__ void __launch_bounds__(512) k_gemm_tn_hs(const float* __restrict__ Y,
   s_acc[wave][lane] = acc;
   __syncthreads();
   if (wave != 0) return;
-  f32x16s sum = s_acc[0][lane];
+  f32x16 sum = s_acc[0][lane];
 #pragma unroll
   for (int w = 1; w < 8; ++w) sum += s_acc[w][lane];
 #pragma unroll
@@ -240,14 +208,13 @@ __global__ void __launch_bounds__(512) k_gemm_tn_hs(const float* __restrict__ Y,
 int launch_gemm_nt_hs(const float* A, int64_t lda, int64_t M, int R, const void* Wf, int C,
                       const float* bias, float* out, int64_t ldo, float* rmax, hipStream_t st) {
   if (M <= 0) return 0;
-  const f16x8s* wf = (const f16x8s*)Wf;
-  const int* ew = reinterpret_cast<const int*>(reinterpret_cast<const char*>(Wf) + (int64_t)C * R * 4);
+  const WeightImage w = weight_image(Wf, C, R);
   if (R > 8 * 8 * 16) return fail("rb_gemm_nt_h: the few-rows kernel needs R <= 1024");
   const dim3 grid((unsigned)((M + 31) / 32), (unsigned)(C / 32));
   if (bias)
-    k_gemm_nt_hs<true><<<grid, 512, 0, st>>>(A, lda, M, R, wf, ew, C, bias, out, ldo, rmax);
+    k_gemm_nt_hs<true><<<grid, 512, 0, st>>>(A, lda, M, R, (const f16x8*)w.wf, w.ew, C, bias, out, ldo, rmax);
   else
-    k_gemm_nt_hs<false><<<grid, 512, 0, st>>>(A, lda, M, R, wf, ew, C, bias, out, ldo, rmax);
+    k_gemm_nt_hs<false><<<grid, 512, 0, st>>>(A, lda, M, R, (const f16x8*)w.wf, w.ew, C, bias, out, ldo, rmax);
   return launch_status("rb_gemm_nt_hs");
 }
 

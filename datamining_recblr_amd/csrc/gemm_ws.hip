@@ -43,6 +43,7 @@
 // Measured (tools/gemm_ws_probe.hip, M = 204,632, profiles/r06_ws_probe.txt):
 // the eight encoder shapes 0.66-0.97x the persistent kernel's time.
 #include "common.h"
+#include "f16x3.h"
 
 #include <type_traits>
 #include <utility>
@@ -50,16 +51,7 @@
 namespace rb {
 namespace ws {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kTR = 14;   // row scale: the row max lands in [2^13, 2^14)
-constexpr int kTC = 14;   // column scale (weights), as gemm_half.hip's kTW
 constexpr int WAVES = 8, THREADS = 64 * WAVES, RB = 32;
 
 // K inputs, NCB 16-column blocks per wave (B slice: 8 NCB KS VGPRs, <= 128),
@@ -90,60 +82,6 @@ struct Cfg {
   static_assert(LDS <= 160 * 1024, "LDS");
 };
 
-__device__ __forceinline__ void split2h(f32x2 x, f16x2& h0, f16x2& h1) {
-  h0 = __builtin_convertvector(x, f16x2);
-  const f32x2 r = x - __builtin_convertvector(h0, f32x2);
-  h1 = __builtin_convertvector(r, f16x2);
-}
-
-__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float max4abs(f32x4 x) {
-  float m, r;
-  asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(m) : "v"(x[0]), "v"(x[1]), "v"(x[2]));
-  asm("v_max_f32 %0, %1, |%2|" : "=v"(r) : "v"(m), "v"(x[3]));
-  return r;
-}
-
-__device__ __forceinline__ float dpp_x1(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float dpp_x2(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x4E, 0xF, 0xF, false));
-}
-// lane k of each quad: column k (v[r] = row r) -> row k (v[c] = column c)
-__device__ __forceinline__ void quad_transpose(float (&v)[4], int lane) {
-  const bool b1 = (lane & 2) != 0, b0 = (lane & 1) != 0;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const float y = dpp_x2(b1 ? v[r] : v[r + 2]);
-    if (b1) v[r] = y; else v[r + 2] = y;
-  }
-#pragma unroll
-  for (int r = 0; r < 4; r += 2) {
-    const float y = dpp_x1(b0 ? v[r] : v[r + 1]);
-    if (b0) v[r] = y; else v[r + 1] = y;
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ T lds_read16(uint32_t addr) {
-  T r;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(addr));
-  return r;
-}
-template <int OFF, typename T>
-__device__ __forceinline__ T lds_read16o(uint32_t addr) {
-  T r;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
-  return r;
-}
-template <int OFF>
-__device__ __forceinline__ void lds_write8(uint32_t addr, f16x4 v) {
-  asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
-}
 // 16-B global load into registers: an ordinary load, so the compiler places
 // (and counts) the vmcnt wait before the first use.  (An inline-asm load that
 // the compiler cannot see lets it copy or reuse the destination registers
@@ -156,17 +94,9 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, uint32_t lds, u
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(uintptr_t)lds, 16,
                                            voff, 0, 0, 0);
 }
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
-// Weight image (written by gemm_half.hip's k_split_weights_h beside its own,
-// at byte offset ws_image_offset(C, K) of the same buffer):
-//   Wi[((cb * KS + s) * 2 + p) * 64 + lane] (16 B) = plane p of
-//     Bm[16 cb + (lane & 15)][32 s + 8 (lane >> 4) + 0..7] * 2^(kTC - e_c)
-//   exps: int32 e_c at byte offset C * K * 4 (shared with the persistent
-//   kernel's image: the same column exponents)
+// Wi, ew: the 16-column planes and the column exponents of the weight image
+// (common.h, "the f16 weight image").
 // ABL (timing-only ablations, results not meaningful): 1 no MFMAs, 2 no
 // split (loads still waited), 4 no stores, 8 no A loads, 16 no fragment reads;
 // 32 (results exact): depth 1 with every wave in the late role.
@@ -238,9 +168,9 @@ k_gemm_nt_ws(const float* __restrict__ A, int64_t lda, int64_t M, const f16x8* _
 
   const uint32_t sbase = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
   const uint32_t s_info = sbase + CF::INFO;   // [2][RB] exps, then [2][RB] maxima
-  const uint32_t s_cols = sbase + CF::COLS;   // [NT] column exps - kTR - kTC, [NT] bias
+  const uint32_t s_cols = sbase + CF::COLS;   // [NT] column exps - kTR - kWeightScale, [NT] bias
   for (int c = tid; c < NT; c += THREADS) {
-    const int e = ew[ct * NT + c] - kTR - kTC;
+    const int e = ew[ct * NT + c] - kTR - kWeightScale;
     const float bv = BIAS ? bias[ct * NT + c] : 0.0f;
     asm volatile("ds_write_b32 %0, %1" ::"v"(s_cols + c * 4), "v"(e) : "memory");
     asm volatile("ds_write_b32 %0, %1" ::"v"(s_cols + (NT + c) * 4), "v"(bv) : "memory");
@@ -256,7 +186,7 @@ k_gemm_nt_ws(const float* __restrict__ A, int64_t lda, int64_t M, const f16x8* _
     for (int s = 0; s < KS; ++s)
 #pragma unroll
       for (int p = 0; p < 2; ++p)
-        bw[cb][s][p] = Wi[((int64_t)((col0 / 16 + cb) * KS + s) * 2 + p) * 64 + lane];
+        bw[cb][s][p] = Wi[weight_slot16(KS, col0 / 16 + cb, s, p, lane).slot];
 
   // ---- raw A: lane l loads row 4 wave + l / 16 of the block, 16-B chunks
   // 16 j + l % 16 (a wave-instruction: four 256-B row pieces)
@@ -323,11 +253,11 @@ k_gemm_nt_ws(const float* __restrict__ A, int64_t lda, int64_t M, const f16x8* _
     float mx = max4abs(src[0]);
 #pragma unroll
     for (int j = 1; j < NLD; ++j) mx = fmaxf(mx, max4abs(src[j]));
-    mx = fmaxf(mx, dpp_x1(mx));
-    mx = fmaxf(mx, dpp_x2(mx));
+    mx = fmaxf(mx, dpp_xor1(mx));
+    mx = fmaxf(mx, dpp_xor2(mx));
     mx = fmaxf(mx, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, mx), 0x124, 0xF, 0xF, false)));  // row_ror:4
     mx = fmaxf(mx, __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, mx), 0x128, 0xF, 0xF, false)));  // row_ror:8
-    const int e = mx > 0.0f ? __builtin_amdgcn_frexp_expf(mx) : 0;
+    const int e = exp_of(mx);
     const float sc = __builtin_amdgcn_ldexpf(1.0f, kTR - e);
     const uint32_t img = sbase + ib * CF::IMG;
 #pragma unroll
@@ -383,9 +313,7 @@ k_gemm_nt_ws(const float* __restrict__ A, int64_t lda, int64_t M, const f16x8* _
       }
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb) {
-        acc[r][cb] = mfma16(bw[cb][s][0], fa[t][1], acc[r][cb]);
-        acc[r][cb] = mfma16(bw[cb][s][1], fa[t][0], acc[r][cb]);
-        acc[r][cb] = mfma16(bw[cb][s][0], fa[t][0], acc[r][cb]);
+        acc[r][cb] = mfma3_16(bw[cb][s][0], bw[cb][s][1], fa[t][0], fa[t][1], acc[r][cb]);
       }
       hook(uc);
     };
@@ -540,8 +468,8 @@ k_gemm_nt_ws(const float* __restrict__ A, int64_t lda, int64_t M, const f16x8* _
     // the lane's two rows' exponents; its columns' exponents and bias read
     // per pair of column blocks (fewer live registers)
     int er[2];
-    asm volatile("ds_read_b32 %0, %1" : "=v"(er[0]) : "v"(s_info + (ib * RB + (lane & 15)) * 4));
-    asm volatile("ds_read_b32 %0, %1" : "=v"(er[1]) : "v"(s_info + (ib * RB + 16 + (lane & 15)) * 4));
+    er[0] = lds_read_i32(s_info + (ib * RB + (lane & 15)) * 4);
+    er[1] = lds_read_i32(s_info + (ib * RB + 16 + (lane & 15)) * 4);
     constexpr int NG = NCB == 1 ? 1 : 2;   // column blocks per group
 #pragma unroll
     for (int q = 0; q < NCB / NG; ++q) {
@@ -750,8 +678,8 @@ k_gemm_nt_ws(const float* __restrict__ A, int64_t lda, int64_t M, const f16x8* _
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float x = csum[cb][i];
-        x += dpp_x1(x);
-        x += dpp_x2(x);
+        x += dpp_xor1(x);
+        x += dpp_xor2(x);
         x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x124, 0xF, 0xF, false));
         x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x128, 0xF, 0xF, false));
         csum[cb][i] = x;

@@ -28,11 +28,10 @@
 #include <type_traits>
 
 #include "common.h"
+#include "f16x3.h"
 
 namespace rb {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kWaves = 4;            // waves per workgroup
 constexpr int kTile = 32;            // rows (items or sequences) per wave tile
@@ -67,8 +66,6 @@ struct Stream {
   static constexpr int NI = kTile * D * 4 / 1024; // 1-KB wave DMA instructions per tile
   static constexpr int FLOATS = kTile * D;
 };
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 template <int D>
 __device__ __forceinline__ void tile_dma(float* buf, const float* M, int64_t r0, int64_t n) {
@@ -873,7 +870,6 @@ __global__ __launch_bounds__(256) void k_item_scores(const float* __restrict__ E
 // log-sum-exp and the gradient kernel see bit-identical logits.
 // The rank / score kernels (evaluation) stay on the fp32 pipe: their target
 // score replays the exact fma chain (k_target_dot).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 constexpr int kTS = 14;
 
 // one wave per row: max|x| over the row, then the two planes (4 values per
@@ -893,7 +889,7 @@ __global__ __launch_bounds__(256) void k_split_rows_h(const float* __restrict__ 
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  const int e = m > 0.0f ? __builtin_amdgcn_frexp_expf(m) : 0;
+  const int e = exp_of(m);
   _Float16* h0 = img + r * 2 * D;
   _Float16* h1 = h0 + D;
   for (int q = lane; q < nq; q += 64) {
@@ -906,7 +902,6 @@ __global__ __launch_bounds__(256) void k_split_rows_h(const float* __restrict__ 
       a[i] = (_Float16)sv;
       b[i] = (_Float16)(sv - (float)a[i]);
     }
-    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
     *reinterpret_cast<f16x4*>(h0 + 4 * q) = f16x4{a[0], a[1], a[2], a[3]};
     *reinterpret_cast<f16x4*>(h1 + 4 * q) = f16x4{b[0], b[1], b[2], b[3]};
   }
@@ -939,7 +934,7 @@ __global__ __launch_bounds__(256) void k_split_rows_hg(const float* __restrict__
     wm = fmaxf(wm, m);
     const int64_t r = r0 + j;
     if (r < N) {
-      const int e = m > 0.0f ? __builtin_amdgcn_frexp_expf(m) : 0;
+      const int e = exp_of(m);
       if (lane < nq) {
         const float t[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
         _Float16 a[4], b[4];
@@ -949,7 +944,6 @@ __global__ __launch_bounds__(256) void k_split_rows_hg(const float* __restrict__
           a[i] = (_Float16)sv;
           b[i] = (_Float16)(sv - (float)a[i]);
         }
-        typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
         _Float16* h0 = img + r * 2 * D;
         *reinterpret_cast<f16x4*>(h0 + 4 * lane) = f16x4{a[0], a[1], a[2], a[3]};
         *reinterpret_cast<f16x4*>(h0 + D + 4 * lane) = f16x4{b[0], b[1], b[2], b[3]};
@@ -1002,13 +996,14 @@ __device__ __forceinline__ f32x16 lds_dot_h(const float* tile, int j, int h, con
     }
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (kTileIsA) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1[s], r0[s], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0[s], r1[s], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w0[s], r0[s], acc, 0, 0, 0);
+      acc = mfma_h(w1[s], r0[s], acc);
+      acc = mfma_h(w0[s], r1[s], acc);
+      acc = mfma_h(w0[s], r0[s], acc);
     } else {
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(r0[s], w1[s], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(r1[s], w0[s], acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(r0[s], w0[s], acc, 0, 0, 0);
+      // (the roles swapped: not mfma3_h's operand order)
+      acc = mfma_h(r0[s], w1[s], acc);
+      acc = mfma_h(r1[s], w0[s], acc);
+      acc = mfma_h(r0[s], w0[s], acc);
     }
     __builtin_amdgcn_sched_barrier(0);
   }

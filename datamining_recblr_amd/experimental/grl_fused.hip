@@ -28,22 +28,16 @@
 //      block): bias, alpha, beta, b' = beta xc, the scan (each lane chains its
 //      eight 4-row groups with its partner lane's), y = silu(z) h.
 #include "../csrc/common.h"
+#include "../csrc/f16x3.h"
 #include "recblr_exp.h"
 
 namespace rb {
 namespace {
 
-typedef _Float16 f16x8g __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4g __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2g __attribute__((ext_vector_type(2)));
-typedef float f32x16g __attribute__((ext_vector_type(16)));
-typedef float f32x4g __attribute__((ext_vector_type(4)));
-typedef float f32x2g __attribute__((ext_vector_type(2)));
-
 constexpr int GH = 256;                       // channels
 constexpr int GT = 64;                        // rows per tile
 constexpr int KBG = GH / 16;                  // k16 blocks of the gates GEMM
-constexpr int kSWg = 14;                      // operand scale target (max in [2^13, 2^14))
+constexpr int kTRg = 14;                      // row scale target (row max in [2^13, 2^14))
 constexpr int XC_PITCH = GH * 4 + 16;         // fp32 xc row in LDS (+16 B: bank spread)
 constexpr int FRAG_PITCH = 64 * 16 + 16;      // one (row block, k16) fragment (+16 B)
 constexpr int PLANE_BYTES = 2 * KBG * FRAG_PITCH;
@@ -57,12 +51,6 @@ constexpr int LDS_SEQ = LDS_POS + GT * 4;       //          packed sequence inde
 constexpr int LDS_LAST = LDS_SEQ + GT * 4;      //          last row of its sequence
 constexpr int LDS_CW = LDS_LAST + GT * 4;       // conv weights [H][KC] and bias [H] (once)
 constexpr int LDS_BYTES = LDS_CW + GH * 4 * 4 + GH * 4;
-
-typedef int i32x4g __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x16g mfma_g(f16x8g a, f16x8g b, f32x16g c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
 
 // A lane-dependent value the compiler may not hoist out of the tile loop:
 // LDS addresses are built as (this per-lane base) + compile-time offsets, so
@@ -107,7 +95,7 @@ struct GrlFwdArgs {
   int64_t xz_rs;
   const float* conv_w;        // [H, KC]
   const float* conv_b;        // [H]
-  const f16x8g* wf;           // f16 image of W_g [2H, H] (rb_gemm_h_split_weights)
+  const f16x8* wf;           // f16 image of W_g [2H, H] (rb_gemm_h_split_weights)
   const int* ew;              // its 2H column exponents
   const float* gate_b;        // [2H]
   const float* lam;           // [H]
@@ -162,6 +150,7 @@ __global__ void __launch_bounds__(512, 1) k_grl_fwd(const GrlFwdArgs a) {
   // element offsets are 32-bit (rb_grl_fwd checks ntok * row stride < 2^31)
   const int xzr = (int)a.xz_rs, yr = (int)a.y_rs;
   // the wave's r and i column blocks of the weight image (wave-uniform bases)
+  // (byte offsets of weight_slot32(KBG, wave, 0, 0, 0) and (KBG, 8 + wave, ..))
   const char* wr = reinterpret_cast<const char*>(a.wf) + (int64_t)wave * KBG * 2048;
   const char* wi = reinterpret_cast<const char*>(a.wf) + (int64_t)(8 + wave) * KBG * 2048;
 
@@ -191,7 +180,7 @@ __global__ void __launch_bounds__(512, 1) k_grl_fwd(const GrlFwdArgs a) {
   // and the KC-1 rows before its first) are issued right after phase A has
   // used the current ones, phase D's z values right after phase D; both
   // land while the GEMM and the scan of the current tile run.
-  f32x4g xo[8], xh[KC - 1];
+  f32x4 xo[8], xh[KC - 1];
   float zp[2][16];
   auto load_x = [&]() {
 #pragma unroll
@@ -200,8 +189,8 @@ __global__ void __launch_bounds__(512, 1) k_grl_fwd(const GrlFwdArgs a) {
       const int grow = __builtin_amdgcn_readlane(mrow, vr);
       const int pos = __builtin_amdgcn_readlane(mpos, vr);
       xo[j] = pos >= 0
-                  ? *reinterpret_cast<const f32x4g*>(a.xz + (uint32_t)(grow * xzr + 4 * lane))
-                  : f32x4g{0.0f, 0.0f, 0.0f, 0.0f};
+                  ? *reinterpret_cast<const f32x4*>(a.xz + (uint32_t)(grow * xzr + 4 * lane))
+                  : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
     const int g0 = __builtin_amdgcn_readlane(mrow, 8 * wave);
     const int p0 = __builtin_amdgcn_readlane(mpos, 8 * wave);
@@ -209,8 +198,8 @@ __global__ void __launch_bounds__(512, 1) k_grl_fwd(const GrlFwdArgs a) {
     for (int i = 0; i < KC - 1; ++i) {   // row g0 - (KC - 1 - i)
       const int l = KC - 1 - i;
       xh[i] = p0 >= l
-                  ? *reinterpret_cast<const f32x4g*>(a.xz + (uint32_t)((g0 - l) * xzr + 4 * lane))
-                  : f32x4g{0.0f, 0.0f, 0.0f, 0.0f};
+                  ? *reinterpret_cast<const f32x4*>(a.xz + (uint32_t)((g0 - l) * xzr + 4 * lane))
+                  : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     }
   };
   auto load_z = [&](int rb) {   // C layout: row 32 rb + 8 (e / 4) + 4 h + e % 4
@@ -239,8 +228,8 @@ __global__ void __launch_bounds__(512, 1) k_grl_fwd(const GrlFwdArgs a) {
     for (int j = 0; j < 8; ++j) {
       const int vr = 8 * wave + j;
       if (s_pos[vr] >= 0)
-        __builtin_nontemporal_store(*reinterpret_cast<const f32x4g*>(yb + vr * XC_PITCH),
-                                    reinterpret_cast<f32x4g*>(a.y + (uint32_t)(s_row[vr] * yr + 4 * lane)));
+        __builtin_nontemporal_store(*reinterpret_cast<const f32x4*>(yb + vr * XC_PITCH),
+                                    reinterpret_cast<f32x4*>(a.y + (uint32_t)(s_row[vr] * yr + 4 * lane)));
     }
   };
 
@@ -267,11 +256,11 @@ __global__ void __launch_bounds__(512, 1) k_grl_fwd(const GrlFwdArgs a) {
       const char* cwp = smem + opaque(LDS_CW + 64 * lane);
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const f32x4g w4 = *reinterpret_cast<const f32x4g*>(cwp + 16 * v);
+        const f32x4 w4 = *reinterpret_cast<const f32x4*>(cwp + 16 * v);
 #pragma unroll
         for (int k = 0; k < KC; ++k) cw[k][v] = w4[k];
       }
-      const f32x4g b4 = *reinterpret_cast<const f32x4g*>(smem + opaque(LDS_CW + GH * 16 + 16 * lane));
+      const f32x4 b4 = *reinterpret_cast<const f32x4*>(smem + opaque(LDS_CW + GH * 16 + 16 * lane));
 #pragma unroll
       for (int v = 0; v < 4; ++v) cb[v] = b4[v];
     }
@@ -280,7 +269,7 @@ __global__ void __launch_bounds__(512, 1) k_grl_fwd(const GrlFwdArgs a) {
       const int vr = 8 * wave + j;
       const int grow = __builtin_amdgcn_readlane(mrow, vr);
       const int pos = __builtin_amdgcn_readlane(mpos, vr);   // -1: past the span
-      f32x4g xcv = {0.0f, 0.0f, 0.0f, 0.0f};
+      f32x4 xcv = {0.0f, 0.0f, 0.0f, 0.0f};
       if (pos >= 0) {
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
@@ -293,11 +282,11 @@ __global__ void __launch_bounds__(512, 1) k_grl_fwd(const GrlFwdArgs a) {
           }
           xcv[v] = fsilu(acc);
         }
-        if (a.xc_out) __builtin_nontemporal_store(xcv, reinterpret_cast<f32x4g*>(a.xc_out + (uint32_t)(grow * GH + 4 * lane)));
+        if (a.xc_out) __builtin_nontemporal_store(xcv, reinterpret_cast<f32x4*>(a.xc_out + (uint32_t)(grow * GH + 4 * lane)));
       }
-      *reinterpret_cast<f32x4g*>(ab_xc + vr * XC_PITCH) = xcv;
+      *reinterpret_cast<f32x4*>(ab_xc + vr * XC_PITCH) = xcv;
       const float m = wave_max(fmaxf(fmaxf(fabsf(xcv[0]), fabsf(xcv[1])), fmaxf(fabsf(xcv[2]), fabsf(xcv[3]))));
-      const int e = m > 0.0f ? __builtin_amdgcn_frexp_expf(m) : 0;
+      const int e = exp_of(m);
       if (lane == 0) {
         if (a.xc_rmax && pos >= 0)   // non-negative floats order as their bit patterns
           atomicMax(reinterpret_cast<int*>(a.xc_rmax) + (grow >> 5), __float_as_int(m));
@@ -307,26 +296,26 @@ __global__ void __launch_bounds__(512, 1) k_grl_fwd(const GrlFwdArgs a) {
         s_seq[vr] = __builtin_amdgcn_readlane(mseq, vr);
         s_last[vr] = __builtin_amdgcn_readlane(mlast, vr);
       }
-      const float sc = __builtin_amdgcn_ldexpf(1.0f, kSWg - e);
-      f16x4g h0v, h1v;
+      const float sc = __builtin_amdgcn_ldexpf(1.0f, kTRg - e);
+      f16x4 h0v, h1v;
 #pragma unroll
       for (int v = 0; v < 4; v += 2) {
-        const f32x2g xv = f32x2g{xcv[v], xcv[v + 1]} * sc;
-        const f16x2g p0 = __builtin_convertvector(xv, f16x2g);
-        const f16x2g p1 = __builtin_convertvector(xv - __builtin_convertvector(p0, f32x2g), f16x2g);
+        const f32x2 xv = f32x2{xcv[v], xcv[v + 1]} * sc;
+        f16x2 p0, p1;
+        split2h(xv, p0, p1);
         h0v[v] = p0[0]; h0v[v + 1] = p0[1];
         h1v[v] = p1[0]; h1v[v + 1] = p1[1];
       }
       // A fragment (row block vr / 32, k16 block lane / 4): fragment lane
       // (vr % 32) + 32 * ((lane >> 1) & 1), halfs 4 * (lane & 1) .. + 3
       const int fo = (vr >> 5) * KBG * FRAG_PITCH + (vr & 31) * 16;
-      *reinterpret_cast<f16x4g*>(ab_fr + fo) = h0v;
-      *reinterpret_cast<f16x4g*>(ab_fr + PLANE_BYTES + fo) = h1v;
+      *reinterpret_cast<f16x4*>(ab_fr + fo) = h0v;
+      *reinterpret_cast<f16x4*>(ab_fr + PLANE_BYTES + fo) = h1v;
     }
     lds_sync();
 
     // ---- phase C: r / i columns of channels 32w.. for the 64 rows
-    f32x16g ar[2], ai[2];
+    f32x16 ar[2], ai[2];
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -334,14 +323,14 @@ __global__ void __launch_bounds__(512, 1) k_grl_fwd(const GrlFwdArgs a) {
     // weight fragments: a wave-uniform base (kb advances it) + the lane's 16 B
     const int wl = opaque(lane * 16);
     auto wfrag = [&](const char* base, int kb, int p) {
-      return *reinterpret_cast<const f16x8g*>(base + kb * 2048 + p * 1024 + wl);
+      return *reinterpret_cast<const f16x8*>(base + weight_slot32<int>(KBG, 0, kb, p, 0).slot * 16 + wl);
     };
     // weight fragments two k16 steps ahead (L2 latency over one step's MFMAs)
-    f16x8g br0 = wfrag(wr, 0, 0), br1 = wfrag(wr, 0, 1), bi0 = wfrag(wi, 0, 0), bi1 = wfrag(wi, 0, 1);
-    f16x8g nr0 = wfrag(wr, 1, 0), nr1 = wfrag(wr, 1, 1), ni0 = wfrag(wi, 1, 0), ni1 = wfrag(wi, 1, 1);
+    f16x8 br0 = wfrag(wr, 0, 0), br1 = wfrag(wr, 0, 1), bi0 = wfrag(wi, 0, 0), bi1 = wfrag(wi, 0, 1);
+    f16x8 nr0 = wfrag(wr, 1, 0), nr1 = wfrag(wr, 1, 1), ni0 = wfrag(wi, 1, 0), ni1 = wfrag(wi, 1, 1);
 #pragma unroll 1
     for (int kb = 0; kb < KBG; ++kb) {
-      f16x8g mr0, mr1, mi0, mi1;
+      f16x8 mr0, mr1, mi0, mi1;
       if (kb + 2 < KBG) {
         mr0 = wfrag(wr, kb + 2, 0); mr1 = wfrag(wr, kb + 2, 1);
         mi0 = wfrag(wi, kb + 2, 0); mi1 = wfrag(wi, kb + 2, 1);
@@ -349,14 +338,10 @@ __global__ void __launch_bounds__(512, 1) k_grl_fwd(const GrlFwdArgs a) {
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb) {
         const int fo = (rb * KBG + kb) * FRAG_PITCH;
-        const f16x8g a0 = *reinterpret_cast<const f16x8g*>(gb + fo);
-        const f16x8g a1 = *reinterpret_cast<const f16x8g*>(gb + PLANE_BYTES + fo);
-        ar[rb] = mfma_g(a1, br0, ar[rb]);
-        ar[rb] = mfma_g(a0, br1, ar[rb]);
-        ar[rb] = mfma_g(a0, br0, ar[rb]);
-        ai[rb] = mfma_g(a1, bi0, ai[rb]);
-        ai[rb] = mfma_g(a0, bi1, ai[rb]);
-        ai[rb] = mfma_g(a0, bi0, ai[rb]);
+        const f16x8 a0 = *reinterpret_cast<const f16x8*>(gb + fo);
+        const f16x8 a1 = *reinterpret_cast<const f16x8*>(gb + PLANE_BYTES + fo);
+        ar[rb] = mfma3_h(a0, a1, br0, br1, ar[rb]);
+        ai[rb] = mfma3_h(a0, a1, bi0, bi1, ai[rb]);
       }
       br0 = nr0; br1 = nr1; bi0 = ni0; bi1 = ni1;
       if (kb + 2 < KBG) { nr0 = mr0; nr1 = mr1; ni0 = mi0; ni1 = mi1; }
@@ -383,8 +368,8 @@ __global__ void __launch_bounds__(512, 1) k_grl_fwd(const GrlFwdArgs a) {
       for (int e = 0; e < 16; ++e) {
         const int rc = 32 * rb + 8 * (e >> 2) + (e & 3);   // row = rc + 4h
         const int er = DER(rc);
-        const float r = __builtin_amdgcn_ldexpf(ar[rb][e], er + ec_r - 2 * kSWg);
-        const float i = __builtin_amdgcn_ldexpf(ai[rb][e], er + ec_i - 2 * kSWg);
+        const float r = __builtin_amdgcn_ldexpf(ar[rb][e], er + ec_r - kTRg - kWeightScale);
+        const float i = __builtin_amdgcn_ldexpf(ai[rb][e], er + ec_i - kTRg - kWeightScale);
         const int pos = DPOS(rc);
         if (a.rg_out && pos >= 0) {
           float* o = a.rg_out + (uint32_t)(DROW(rc) * (2 * GH) + c);
@@ -502,9 +487,9 @@ struct GrlBwdArgs {
   int64_t xz_rs;
   const float* conv_w;
   const float* conv_b;
-  const f16x8g* wf;           // W_g [2H, H] image (rg = xc W_g^T)
+  const f16x8* wf;           // W_g [2H, H] image (rg = xc W_g^T)
   const int* ew;
-  const f16x8g* wft;          // W_g^T [H, 2H] image (dxc_g = drg W_g)
+  const f16x8* wft;          // W_g^T [H, 2H] image (dxc_g = drg W_g)
   const int* ewt;
   const float* gate_b;
   const float* lam;
@@ -557,6 +542,7 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
   const float hz = a.h0 ? a.h0[c] : 0.0f;
   // element offsets are 32-bit (rb_grl_bwd checks ntok * row stride < 2^31)
   const int xzr = (int)a.xz_rs, dxr = (int)a.dxz_rs;
+  // (byte offsets of weight_slot32(KBG, wave, 0, 0, 0) and (KBG, 8 + wave, ..))
   const char* wr = reinterpret_cast<const char*>(a.wf) + (int64_t)wave * KBG * 2048;
   const char* wi = reinterpret_cast<const char*>(a.wf) + (int64_t)(8 + wave) * KBG * 2048;
   const char* wt = reinterpret_cast<const char*>(a.wft) + (int64_t)wave * (2 * KBG) * 2048;
@@ -587,11 +573,11 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
     const char* cwp = smem + (B_CW + 64 * lf);
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
-      const f32x4g w4 = *reinterpret_cast<const f32x4g*>(cwp + 16 * v);
+      const f32x4 w4 = *reinterpret_cast<const f32x4*>(cwp + 16 * v);
 #pragma unroll
       for (int k = 0; k < KC; ++k) cw[k][v] = w4[k];
     }
-    const f32x4g b4 = *reinterpret_cast<const f32x4g*>(smem + (B_CW + GH * 16 + 16 * lf));
+    const f32x4 b4 = *reinterpret_cast<const f32x4*>(smem + (B_CW + GH * 16 + 16 * lf));
 #pragma unroll
     for (int v = 0; v < 4; ++v) cbv[v] = b4[v];
   };
@@ -621,14 +607,14 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
         const int vr = 8 * wave + j;
         const int grow = __builtin_amdgcn_readlane(rrow, vr);
         const int pos = __builtin_amdgcn_readlane(rpos, vr);
-        f32x4g xcv = {0.0f, 0.0f, 0.0f, 0.0f};
+        f32x4 xcv = {0.0f, 0.0f, 0.0f, 0.0f};
         if (pos >= 0) {
-          f32x4g xs[KC];
+          f32x4 xs[KC];
 #pragma unroll
           for (int k = 0; k < KC; ++k)
             xs[k] = KC - 1 - k <= pos
-                        ? *reinterpret_cast<const f32x4g*>(a.xz + (uint32_t)((grow - (KC - 1 - k)) * xzr + 4 * lane))
-                        : f32x4g{0.0f, 0.0f, 0.0f, 0.0f};
+                        ? *reinterpret_cast<const f32x4*>(a.xz + (uint32_t)((grow - (KC - 1 - k)) * xzr + 4 * lane))
+                        : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
           for (int v = 0; v < 4; ++v) {
             float acc = cbv[v];
@@ -637,11 +623,11 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
               acc = acc + (KC - 1 - k <= pos ? cw[k][v] * xs[k][v] : 0.0f);
             xcv[v] = fsilu(acc);
           }
-          __builtin_nontemporal_store(xcv, reinterpret_cast<f32x4g*>(a.xc_out + (uint32_t)(grow * GH + 4 * lane)));
+          __builtin_nontemporal_store(xcv, reinterpret_cast<f32x4*>(a.xc_out + (uint32_t)(grow * GH + 4 * lane)));
         }
-        *reinterpret_cast<f32x4g*>(ab_xc + vr * XC_PITCH) = xcv;
+        *reinterpret_cast<f32x4*>(ab_xc + vr * XC_PITCH) = xcv;
         const float m = wave_max(fmaxf(fmaxf(fabsf(xcv[0]), fabsf(xcv[1])), fmaxf(fabsf(xcv[2]), fabsf(xcv[3]))));
-        const int e = m > 0.0f ? __builtin_amdgcn_frexp_expf(m) : 0;
+        const int e = exp_of(m);
         if (lane == 0) {
           if (a.xc_rmax && pos >= 0)
             atomicMax(reinterpret_cast<int*>(a.xc_rmax) + (grow >> 5), __float_as_int(m));
@@ -651,25 +637,25 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
           *reinterpret_cast<int*>(smem + B_SEQ + 4 * vr) = __builtin_amdgcn_readlane(rseq, vr);
           *reinterpret_cast<int*>(smem + B_LAST + 4 * vr) = __builtin_amdgcn_readlane(rrem, vr);
         }
-        const float sc = __builtin_amdgcn_ldexpf(1.0f, kSWg - e);
-        f16x4g h0v, h1v;
+        const float sc = __builtin_amdgcn_ldexpf(1.0f, kTRg - e);
+        f16x4 h0v, h1v;
 #pragma unroll
         for (int v = 0; v < 4; v += 2) {
-          const f32x2g xv = f32x2g{xcv[v], xcv[v + 1]} * sc;
-          const f16x2g p0 = __builtin_convertvector(xv, f16x2g);
-          const f16x2g p1 = __builtin_convertvector(xv - __builtin_convertvector(p0, f32x2g), f16x2g);
+          const f32x2 xv = f32x2{xcv[v], xcv[v + 1]} * sc;
+          f16x2 p0, p1;
+          split2h(xv, p0, p1);
           h0v[v] = p0[0]; h0v[v + 1] = p0[1];
           h1v[v] = p1[0]; h1v[v + 1] = p1[1];
         }
         const int fo = (vr >> 5) * KBG * FRAG_PITCH + (vr & 31) * 16;
-        *reinterpret_cast<f16x4g*>(ab_fr + fo) = h0v;
-        *reinterpret_cast<f16x4g*>(ab_fr + PLANE_BYTES + fo) = h1v;
+        *reinterpret_cast<f16x4*>(ab_fr + fo) = h0v;
+        *reinterpret_cast<f16x4*>(ab_fr + PLANE_BYTES + fo) = h1v;
       }
     }
     lds_sync();
 
     // ---- C: GEMM 1 (r, i)
-    f32x16g ar[2], ai[2];
+    f32x16 ar[2], ai[2];
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -678,13 +664,13 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
       const int wl = opaque(lane * 16);
       const char* const gb = smem + opaque(B_R1 + lane * 16);
       auto wfrag = [&](const char* base, int kb, int p) {
-        return *reinterpret_cast<const f16x8g*>(base + kb * 2048 + p * 1024 + wl);
+        return *reinterpret_cast<const f16x8*>(base + weight_slot32<int>(KBG, 0, kb, p, 0).slot * 16 + wl);
       };
-      f16x8g br0 = wfrag(wr, 0, 0), br1 = wfrag(wr, 0, 1), bi0 = wfrag(wi, 0, 0), bi1 = wfrag(wi, 0, 1);
-      f16x8g nr0 = wfrag(wr, 1, 0), nr1 = wfrag(wr, 1, 1), ni0 = wfrag(wi, 1, 0), ni1 = wfrag(wi, 1, 1);
+      f16x8 br0 = wfrag(wr, 0, 0), br1 = wfrag(wr, 0, 1), bi0 = wfrag(wi, 0, 0), bi1 = wfrag(wi, 0, 1);
+      f16x8 nr0 = wfrag(wr, 1, 0), nr1 = wfrag(wr, 1, 1), ni0 = wfrag(wi, 1, 0), ni1 = wfrag(wi, 1, 1);
 #pragma unroll 1
       for (int kb = 0; kb < KBG; ++kb) {
-        f16x8g mr0, mr1, mi0, mi1;
+        f16x8 mr0, mr1, mi0, mi1;
         if (kb + 2 < KBG) {
           mr0 = wfrag(wr, kb + 2, 0); mr1 = wfrag(wr, kb + 2, 1);
           mi0 = wfrag(wi, kb + 2, 0); mi1 = wfrag(wi, kb + 2, 1);
@@ -692,14 +678,10 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) {
           const int fo = (rb * KBG + kb) * FRAG_PITCH;
-          const f16x8g a0 = *reinterpret_cast<const f16x8g*>(gb + fo);
-          const f16x8g a1 = *reinterpret_cast<const f16x8g*>(gb + PLANE_BYTES + fo);
-          ar[rb] = mfma_g(a1, br0, ar[rb]);
-          ar[rb] = mfma_g(a0, br1, ar[rb]);
-          ar[rb] = mfma_g(a0, br0, ar[rb]);
-          ai[rb] = mfma_g(a1, bi0, ai[rb]);
-          ai[rb] = mfma_g(a0, bi1, ai[rb]);
-          ai[rb] = mfma_g(a0, bi0, ai[rb]);
+          const f16x8 a0 = *reinterpret_cast<const f16x8*>(gb + fo);
+          const f16x8 a1 = *reinterpret_cast<const f16x8*>(gb + PLANE_BYTES + fo);
+          ar[rb] = mfma3_h(a0, a1, br0, br1, ar[rb]);
+          ai[rb] = mfma3_h(a0, a1, bi0, bi1, ai[rb]);
         }
         br0 = nr0; br1 = nr1; bi0 = ni0; bi1 = ni1;
         if (kb + 2 < KBG) { nr0 = mr0; nr1 = mr1; ni0 = mi0; ni1 = mi1; }
@@ -753,8 +735,8 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
           if ((e & 3) == 0) __builtin_amdgcn_sched_barrier(0);
           const int rc = 32 * rb + 8 * (e >> 2) + (e & 3);
           const int er = BER(rc);
-          const float r = __builtin_amdgcn_ldexpf(ar[rb][e], er + ec_r - 2 * kSWg) + br;
-          const float i = __builtin_amdgcn_ldexpf(ai[rb][e], er + ec_i - 2 * kSWg) + bi;
+          const float r = __builtin_amdgcn_ldexpf(ar[rb][e], er + ec_r - kTRg - kWeightScale) + br;
+          const float i = __builtin_amdgcn_ldexpf(ai[rb][e], er + ec_i - kTRg - kWeightScale) + bi;
           const bool ok = BPOS(rc) >= 0;
           const float sr = fsigm(r);
           const float aa = ok ? fexp(nsp * sr) : 1.0f;
@@ -933,49 +915,49 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
       for (int j = 0; j < 8; ++j) {
         const int vr = 8 * wave + j;
         const int pos = *reinterpret_cast<const int*>(smem + B_POS + 4 * vr);
-        const f32x4g dr4 = *reinterpret_cast<const f32x4g*>(e0 + vr * XC_PITCH);
-        const f32x4g di4 = *reinterpret_cast<const f32x4g*>(e1 + vr * XC_PITCH);
+        const f32x4 dr4 = *reinterpret_cast<const f32x4*>(e0 + vr * XC_PITCH);
+        const f32x4 di4 = *reinterpret_cast<const f32x4*>(e1 + vr * XC_PITCH);
         const int grow = *reinterpret_cast<const int*>(smem + B_ROW + 4 * vr);
         if (pos >= 0) {
-          __builtin_nontemporal_store(dr4, reinterpret_cast<f32x4g*>(a.drg + (uint32_t)(grow * (2 * GH) + 4 * lane)));
-          __builtin_nontemporal_store(di4, reinterpret_cast<f32x4g*>(a.drg + (uint32_t)(grow * (2 * GH) + GH + 4 * lane)));
+          __builtin_nontemporal_store(dr4, reinterpret_cast<f32x4*>(a.drg + (uint32_t)(grow * (2 * GH) + 4 * lane)));
+          __builtin_nontemporal_store(di4, reinterpret_cast<f32x4*>(a.drg + (uint32_t)(grow * (2 * GH) + GH + 4 * lane)));
         }
         float m = 0.0f;
 #pragma unroll
         for (int v = 0; v < 4; ++v) m = fmaxf(m, fmaxf(fabsf(dr4[v]), fabsf(di4[v])));
         m = wave_max(m);
-        const int e = m > 0.0f ? __builtin_amdgcn_frexp_expf(m) : 0;
+        const int e = exp_of(m);
         if (lane == 0) {
           *reinterpret_cast<int*>(smem + B_ER2 + 4 * vr) = e;
           if (a.drg_rmax && pos >= 0)
             atomicMax(reinterpret_cast<int*>(a.drg_rmax) + (grow >> 5), __float_as_int(m));
         }
-        const float sc = __builtin_amdgcn_ldexpf(1.0f, kSWg - e);
+        const float sc = __builtin_amdgcn_ldexpf(1.0f, kTRg - e);
         // in place: the row's hi plane at +0, lo plane at +PL_LO (halfs)
-        f16x4g rh, rl, ih, il;
+        f16x4 rh, rl, ih, il;
 #pragma unroll
         for (int v = 0; v < 4; v += 2) {
-          const f32x2g xr = f32x2g{dr4[v], dr4[v + 1]} * sc;
-          const f16x2g r0 = __builtin_convertvector(xr, f16x2g);
-          const f16x2g r1 = __builtin_convertvector(xr - __builtin_convertvector(r0, f32x2g), f16x2g);
-          const f32x2g xi = f32x2g{di4[v], di4[v + 1]} * sc;
-          const f16x2g i0 = __builtin_convertvector(xi, f16x2g);
-          const f16x2g i1 = __builtin_convertvector(xi - __builtin_convertvector(i0, f32x2g), f16x2g);
+          const f32x2 xr = f32x2{dr4[v], dr4[v + 1]} * sc;
+          f16x2 r0, r1;
+          split2h(xr, r0, r1);
+          const f32x2 xi = f32x2{di4[v], di4[v + 1]} * sc;
+          f16x2 i0, i1;
+          split2h(xi, i0, i1);
           rh[v] = r0[0]; rh[v + 1] = r0[1]; rl[v] = r1[0]; rl[v + 1] = r1[1];
           ih[v] = i0[0]; ih[v + 1] = i0[1]; il[v] = i1[0]; il[v + 1] = i1[1];
         }
         // the wave's own row: its 16-B reads above are done before these writes
-        *reinterpret_cast<f16x4g*>(e0 - 8 * lane + vr * XC_PITCH) = rh;
-        *reinterpret_cast<f16x4g*>(e0 - 8 * lane + vr * XC_PITCH + PL_LO) = rl;
-        *reinterpret_cast<f16x4g*>(e1 - 8 * lane + vr * XC_PITCH) = ih;
-        *reinterpret_cast<f16x4g*>(e1 - 8 * lane + vr * XC_PITCH + PL_LO) = il;
+        *reinterpret_cast<f16x4*>(e0 - 8 * lane + vr * XC_PITCH) = rh;
+        *reinterpret_cast<f16x4*>(e0 - 8 * lane + vr * XC_PITCH + PL_LO) = rl;
+        *reinterpret_cast<f16x4*>(e1 - 8 * lane + vr * XC_PITCH) = ih;
+        *reinterpret_cast<f16x4*>(e1 - 8 * lane + vr * XC_PITCH + PL_LO) = il;
       }
     }
     lds_sync();
 
     // ---- F: GEMM 2, dxc_g for channels 32w.. (K = 512: dr's planes in R0,
     // di's in R1)
-    f32x16g ax[2];
+    f32x16 ax[2];
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -985,21 +967,19 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
       // A fragment of lane l: row l % 32, halfs 8 (l / 32) .. + 7 of a k16 block
       const char* const g2 = smem + opaque((lane & 31) * XC_PITCH + 16 * (lane >> 5));
       auto tfrag = [&](int kk, int p) {
-        return *reinterpret_cast<const f16x8g*>(wt + kk * 2048 + p * 1024 + wl);
+        return *reinterpret_cast<const f16x8*>(wt + weight_slot32<int>(2 * KBG, 0, kk, p, 0).slot * 16 + wl);
       };
-      f16x8g b0 = tfrag(0, 0), b1 = tfrag(0, 1), n0 = tfrag(1, 0), n1 = tfrag(1, 1);
+      f16x8 b0 = tfrag(0, 0), b1 = tfrag(0, 1), n0 = tfrag(1, 0), n1 = tfrag(1, 1);
 #pragma unroll 1
       for (int kk = 0; kk < 2 * KBG; ++kk) {
-        f16x8g m0, m1;
+        f16x8 m0, m1;
         if (kk + 2 < 2 * KBG) { m0 = tfrag(kk + 2, 0); m1 = tfrag(kk + 2, 1); }
         const char* const ga = g2 + (kk < KBG ? B_R0 + kk * 32 : B_R1 + (kk - KBG) * 32);
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb) {
-          const f16x8g a0 = *reinterpret_cast<const f16x8g*>(ga + rb * 32 * XC_PITCH);
-          const f16x8g a1 = *reinterpret_cast<const f16x8g*>(ga + rb * 32 * XC_PITCH + PL_LO);
-          ax[rb] = mfma_g(a1, b0, ax[rb]);
-          ax[rb] = mfma_g(a0, b1, ax[rb]);
-          ax[rb] = mfma_g(a0, b0, ax[rb]);
+          const f16x8 a0 = *reinterpret_cast<const f16x8*>(ga + rb * 32 * XC_PITCH);
+          const f16x8 a1 = *reinterpret_cast<const f16x8*>(ga + rb * 32 * XC_PITCH + PL_LO);
+          ax[rb] = mfma3_h(a0, a1, b0, b1, ax[rb]);
         }
         b0 = n0; b1 = n1;
         if (kk + 2 < 2 * KBG) { n0 = m0; n1 = m1; }
@@ -1017,7 +997,7 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
           if ((e & 3) == 0) __builtin_amdgcn_sched_barrier(0);
           const int rc = 32 * rb + 8 * (e >> 2) + (e & 3);
           *reinterpret_cast<float*>(r0c + rc * XC_PITCH) =
-              __builtin_amdgcn_ldexpf(ax[rb][e], BER2(rc) + ec_t - 2 * kSWg) + dxd[rb][e];
+              __builtin_amdgcn_ldexpf(ax[rb][e], BER2(rc) + ec_t - kTRg - kWeightScale) + dxd[rb][e];
         }
     }
     lds_sync();
@@ -1035,16 +1015,16 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
       for (int j = 0; j < 8; ++j) {
         const int vr = 8 * wave + j;
         const int pos = *reinterpret_cast<const int*>(smem + B_POS + 4 * vr);
-        f32x4g dpv = {0.0f, 0.0f, 0.0f, 0.0f};
+        f32x4 dpv = {0.0f, 0.0f, 0.0f, 0.0f};
         if (pos >= 0) {
           const int grow = *reinterpret_cast<const int*>(smem + B_ROW + 4 * vr);
-          f32x4g xs[KC];
+          f32x4 xs[KC];
 #pragma unroll
           for (int k = 0; k < KC; ++k)
             xs[k] = KC - 1 - k <= pos
-                        ? *reinterpret_cast<const f32x4g*>(a.xz + (uint32_t)((grow - (KC - 1 - k)) * xzr + 4 * lane))
-                        : f32x4g{0.0f, 0.0f, 0.0f, 0.0f};
-          const f32x4g g1 = *reinterpret_cast<const f32x4g*>(dp + vr * XC_PITCH);
+                        ? *reinterpret_cast<const f32x4*>(a.xz + (uint32_t)((grow - (KC - 1 - k)) * xzr + 4 * lane))
+                        : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+          const f32x4 g1 = *reinterpret_cast<const f32x4*>(dp + vr * XC_PITCH);
 #pragma unroll
           for (int v = 0; v < 4; ++v) {
             float acc = cbv[v];
@@ -1056,7 +1036,7 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
             cb_acc[v] = cb_acc[v] + dpv[v];
           }
         }
-        *reinterpret_cast<f32x4g*>(dp + vr * XC_PITCH) = dpv;
+        *reinterpret_cast<f32x4*>(dp + vr * XC_PITCH) = dpv;
       }
       lds_sync();
 #pragma unroll 2
@@ -1066,27 +1046,27 @@ __global__ void __launch_bounds__(512, 1) k_grl_bwd(const GrlBwdArgs a) {
         if (pos < 0) continue;
         const int grow = *reinterpret_cast<const int*>(smem + B_ROW + 4 * vr);
         const int rem = *reinterpret_cast<const int*>(smem + B_LAST + 4 * vr);
-        f32x4g dxv = {0.0f, 0.0f, 0.0f, 0.0f};
+        f32x4 dxv = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int k = 0; k < KC; ++k) {
           const int lag = KC - 1 - k;   // dpre of row vr + lag reads x_vr through tap k
           if (lag <= rem) {
             const int vn = vr + lag;
-            const f32x4g dn = vn < GT ? *reinterpret_cast<const f32x4g*>(dp + vn * XC_PITCH)
-                                      : *reinterpret_cast<const f32x4g*>(dh + (vn - GT) * XC_PITCH);
+            const f32x4 dn = vn < GT ? *reinterpret_cast<const f32x4*>(dp + vn * XC_PITCH)
+                                      : *reinterpret_cast<const f32x4*>(dh + (vn - GT) * XC_PITCH);
 #pragma unroll
             for (int v = 0; v < 4; ++v) dxv[v] = dxv[v] + cw[k][v] * dn[v];
           }
         }
-        __builtin_nontemporal_store(dxv, reinterpret_cast<f32x4g*>(a.dxz + (uint32_t)(grow * dxr + 4 * lane)));
+        __builtin_nontemporal_store(dxv, reinterpret_cast<f32x4*>(a.dxz + (uint32_t)(grow * dxr + 4 * lane)));
       }
     }
     lds_sync();
     if (wave == 0) {   // this tile's first 3 rows of dpre: the halo of the next (earlier) tile
 #pragma unroll
       for (int j = 0; j < 3; ++j)
-        *reinterpret_cast<f32x4g*>(smem + B_HALO + j * XC_PITCH + 16 * lane) =
-            *reinterpret_cast<const f32x4g*>(smem + B_R0 + j * XC_PITCH + 16 * lane);
+        *reinterpret_cast<f32x4*>(smem + B_HALO + j * XC_PITCH + 16 * lane) =
+            *reinterpret_cast<const f32x4*>(smem + B_R0 + j * XC_PITCH + 16 * lane);
     }
 #undef GRL_BASES
 #undef BPOS
@@ -1129,7 +1109,7 @@ int launch_grl_fwd(const float* xz, int64_t xz_rs, const float* conv_w, int KC,
                    float* tile_carries, int64_t max_tiles, hipStream_t st) {
   GrlFwdArgs a;
   a.xz = xz; a.xz_rs = xz_rs; a.conv_w = conv_w; a.conv_b = conv_b;
-  a.wf = (const f16x8g*)wf;
+  a.wf = (const f16x8*)wf;
   a.ew = reinterpret_cast<const int*>(reinterpret_cast<const char*>(wf) + (int64_t)2 * GH * GH * 4);
   a.gate_b = gate_b; a.lam = lam; a.h0 = h0;
   a.pieces = pieces; a.B = (int)B; a.G = (int)G; a.ntok = ntok;
@@ -1167,9 +1147,9 @@ int launch_grl_bwd(const float* xz, int64_t xz_rs, const float* conv_w, int KC,
                    float* drg_rmax, float* xc_rmax, float* part, float* cpart, hipStream_t st) {
   GrlBwdArgs a;
   a.xz = xz; a.xz_rs = xz_rs; a.conv_w = conv_w; a.conv_b = conv_b;
-  a.wf = (const f16x8g*)wf;
+  a.wf = (const f16x8*)wf;
   a.ew = reinterpret_cast<const int*>(reinterpret_cast<const char*>(wf) + (int64_t)2 * GH * GH * 4);
-  a.wft = (const f16x8g*)wft;
+  a.wft = (const f16x8*)wft;
   a.ewt = reinterpret_cast<const int*>(reinterpret_cast<const char*>(wft) + (int64_t)2 * GH * GH * 4);
   a.gate_b = gate_b; a.lam = lam; a.h0 = h0; a.pieces = pieces; a.B = (int)B; a.G = (int)G;
   a.ntok = ntok; a.tile_carries = tile_carries; a.max_tiles = (int)max_tiles; a.dy = dy;

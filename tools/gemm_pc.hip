@@ -137,16 +137,16 @@ k_gemm_nt_pc(const float* __restrict__ A, int64_t lda, int64_t M, int R,
     int issued = 0;
     for (; issued < LA && issued < U; ++issued) issue();
     // step 0 landed: its 12 pieces are the oldest
-    if (issued >= 2) hwait_vm<12 * (LA - 1)>(); else hwait_vm<0>();
+    if (issued >= 2) wait_vm<12 * (LA - 1)>(); else wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     for (int u = 0; u < U; ++u) {
       // slot of step u + LA was read at step u - 1 (finished: the barrier)
       if (issued < U) { issue(); ++issued; }
       // step u + 1 landed: the pieces of the steps after it may stay in flight
       const int after = issued - (u + 2);   // steps issued beyond u + 1
-      if (after >= 2) hwait_vm<24>();
-      else if (after == 1) hwait_vm<12>();
-      else hwait_vm<0>();
+      if (after >= 2) wait_vm<24>();
+      else if (after == 1) wait_vm<12>();
+      else wait_vm<0>();
       __builtin_amdgcn_s_barrier();
     }
     return;
@@ -190,14 +190,14 @@ k_gemm_nt_pc(const float* __restrict__ A, int64_t lda, int64_t M, int R,
       f16x8 bq[4][2];
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
-        bq[n][0] = hds_read16<f16x8>(sb + ((n * 2 + s) * 2 + 0) * 1024);
-        bq[n][1] = hds_read16<f16x8>(sb + ((n * 2 + s) * 2 + 1) * 1024);
+        bq[n][0] = lds_read16<f16x8>(sb + ((n * 2 + s) * 2 + 0) * 1024);
+        bq[n][1] = lds_read16<f16x8>(sb + ((n * 2 + s) * 2 + 1) * 1024);
       }
       f32x4 x[2][2];
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb) {
-        x[rb][0] = hds_read16<f32x4>(sa + a_rd[rb][s][0]);
-        x[rb][1] = hds_read16<f32x4>(sa + a_rd[rb][s][1]);
+        x[rb][0] = lds_read16<f32x4>(sa + a_rd[rb][s][0]);
+        x[rb][1] = lds_read16<f32x4>(sa + a_rd[rb][s][1]);
       }
       asm volatile("s_waitcnt lgkmcnt(0)"
                    : "+v"(bq[0][0]), "+v"(bq[0][1]), "+v"(bq[1][0]), "+v"(bq[1][1]),
@@ -250,7 +250,7 @@ k_gemm_nt_pc(const float* __restrict__ A, int64_t lda, int64_t M, int R,
           const char* base = reinterpret_cast<const char*>(out + r0 * ldo + cur_ct * P_BN);
 #pragma unroll
           for (int j = 0; j < 16; ++j) {
-            const int erj = __shfl(er[rb], crow(j)) - kTA - kTW;
+            const int erj = __shfl(er[rb], crow(j)) - kTA - kWeightScale;
 #pragma unroll
             for (int n = 0; n < 4; ++n)
               acc[rb][n][j] = __builtin_amdgcn_ldexpf(acc[rb][n][j], erj + ecol[n]);
