@@ -20,6 +20,7 @@ Everything needs a ROCm GPU; there is no CPU fallback.
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 
@@ -142,8 +143,10 @@ class GatedRecurrentLayer(nn.Module):
         for m in (self.input, self.output):
             m.forward = HipLinearForward(m)
 
-    def forward(self, x, pad=None, slot=None, rows=None, seq=None, project=True):
-        """pad: None (the reference's pow2 pad prefix for x's length) or an
+    def forward(self, x, pad=None, slot=None, rows=None, seq=None, project=True, capture=None):
+        """capture: optional callable (x, xc, rg, carries) handed to
+        recurrence.bd_lru (the scan's inputs and tile carries of this layer).
+        pad: None (the reference's pow2 pad prefix for x's length) or an
         int64 tensor [B] of per-row pad lengths (see recurrence.bd_lru).
         slot: blocks.ResidualGrad of the enclosing RecurrentLayer.
         rows: flat positions at which the output is needed (the
@@ -169,7 +172,7 @@ class GatedRecurrentLayer(nn.Module):
                 fire_hooks(self.gates, (xc,), rg + self.gates.bias)
         y = bd_lru(xz, self.conv1d.weight, self.conv1d.bias, self.gates.weight,
                    self.gates.bias, self.Lambda, use_conv=not self.disable_conv1d, pad=pad,
-                   seq=seq, last_only=last_only, observe=observe)
+                   seq=seq, last_only=last_only, observe=observe, capture=capture)
         if last_only:
             if seq.order is None:   # packed-sequence order -> batch order
                 y = y.index_select(0, seq.inv)
@@ -213,8 +216,10 @@ class RecurrentLayer(nn.Module):
         self.layer_norm = nn.LayerNorm(d_model, eps=1e-12)
         self.ffn = FeedForward(d_model=d_model, inner_size=d_model * 4, dropout=dropout)
 
-    def forward(self, input_tensor, pad=None, rows=None, seq=None, slot=None, out_addend=None):
-        """rows: evaluate the position-wise tail (out-projection, residual
+    def forward(self, input_tensor, pad=None, rows=None, seq=None, slot=None, out_addend=None,
+                capture=None):
+        """capture: see GatedRecurrentLayer.forward.
+        rows: evaluate the position-wise tail (out-projection, residual
         LayerNorm, FFN) only at these flat positions -> [len(rows), d].
         seq: kernels.Packed (input_tensor is [ntok, d]).
         slot: blocks.ResidualGrad for the residual branch's gradient (RecBLR
@@ -232,7 +237,8 @@ class RecurrentLayer(nn.Module):
         # full rows: the out-projection and the residual LayerNorm in one
         # launch where it applies (blocks.linear_add_dropout_layer_norm)
         fuse = rows is None and not has_hooks(out)
-        y = self.behavior_modeling(input_tensor, pad, slot, rows, seq, project=not fuse)
+        y = self.behavior_modeling(input_tensor, pad, slot, rows, seq, project=not fuse,
+                                   capture=capture)
 
         def add_ln(addend):
             if fuse:
@@ -354,8 +360,14 @@ class RecBLR(SequentialRecommender):
             return [None] * (n + 1)
         return [ResidualGrad(last_rows if i == n - 1 else None) for i in range(n)] + [None]
 
-    def _forward_packed(self, item_seq, item_seq_len, pad):
-        """forward() on the valid positions only.  RecBole right-pads every
+    def _forward_packed(self, item_seq, item_seq_len, pad, capture=None):
+        """capture: optional callable (layer index, seq, x, xc, rg, carries)
+        run once per layer with the packed layout (kernels.Packed: offsets,
+        order) and that layer's scan inputs and tile carries
+        (recurrence.bd_lru); session.prefill(method="forward") reads the
+        sessions' state from them.
+
+        forward() on the valid positions only.  RecBole right-pads every
         sequence to L; the encoder is causal (causal conv, forward scan,
         position-wise projections / LayerNorms / FFN), so position t of row b
         influences only positions >= t of that row, and forward() returns
@@ -402,9 +414,10 @@ class RecBLR(SequentialRecommender):
         h = embed_dropout_layer_norm(ids, self.item_embedding, self.dropout, self.layer_norm,
                                      self.training, slots[0])
         for i, layer in enumerate(self.recurrent_layers):
+            cap = None if capture is None else functools.partial(capture, i, seq)
             if i == n - 1 and self.gather_last_layer:
-                return layer(h, pad, last, seq, slot=slots[i])
-            h = layer(h, pad, seq=seq, slot=slots[i], out_addend=slots[i + 1])
+                return layer(h, pad, last, seq, slot=slots[i], capture=cap)
+            h = layer(h, pad, seq=seq, slot=slots[i], out_addend=slots[i + 1], capture=cap)
         return h.index_select(0, last)
 
     def _scores_all(self, seq_output):
@@ -466,9 +479,11 @@ class RecBLR(SequentialRecommender):
 
         return step(self, state, items, slots)
 
-    def session_prefill(self, state, item_seq, item_seq_len, slots=None, reset: bool = True):
-        """Open sessions from stored histories, one step per column
-        (session.prefill)."""
+    def session_prefill(self, state, item_seq, item_seq_len, slots=None, reset: bool = True,
+                        method: str = "steps"):
+        """Open sessions from stored histories (session.prefill): one step
+        per column (method="steps"), or one packed forward whose
+        intermediates give the state (method="forward")."""
         from .session import prefill
 
-        return prefill(self, state, item_seq, item_seq_len, slots, reset)
+        return prefill(self, state, item_seq, item_seq_len, slots, reset, method)

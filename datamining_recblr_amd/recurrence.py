@@ -117,11 +117,14 @@ class BDLRUCore(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xz, conv_w, conv_b, gate_w, gate_b, lam, h0, use_conv, seq=None,
-                last_only=False, pad_len=None, observe=None):
+                last_only=False, pad_len=None, observe=None, capture=None):
         """h0: an initial state given as an input (its gradient returned), or
         pad_len (int P > 0 or int64 [B] per-row lengths) with h0 None: the
         pad-prefix state computed here, its gradient added in place into the
-        parameters' gradients (no separate autograd node and add launches)."""
+        parameters' gradients (no separate autograd node and add launches).
+        capture: optional callable (x, xc, rg, carries) run after the scan;
+        like observe it selects the three-launch path, and the scan then
+        writes its tile carries whether or not a gradient is wanted."""
         if pad_len is not None:
             h0 = kernels.pad_prefix_fwd(conv_b, gate_w, gate_b, lam, pad_len)
         ctx.pad_len = pad_len
@@ -132,7 +135,7 @@ class BDLRUCore(torch.autograd.Function):
         # last_only on packed sequences: y_last in batch order (seq.order)
         batch_row = seq.order if (last_only and seq is not None) else None
         ctx.batch_row = batch_row
-        if (observe is None and (h0 is None or h0.dim() == 1)
+        if (observe is None and capture is None and (h0 is None or h0.dim() == 1)
                 and fused_ok(seq is not None and seq.pieces is not None, H, use_conv, conv_w.shape[-1], xz.dtype)):
             # conv + gates GEMM + gate scan in one launch (rb_grl_fwd).  Its
             # backward is one launch too (rb_grl_bwd), from the 64-row tile
@@ -162,9 +165,12 @@ class BDLRUCore(torch.autograd.Function):
             ctx.r_xc = r_xc
             if observe is not None:   # module hooks of the fused conv / gates (model.py)
                 observe(x, xc, rg)
-            y, carries = kernels.gate_scan_fwd(rg, xc, z, lam, h0, want_carries=train,
+            y, carries = kernels.gate_scan_fwd(rg, xc, z, lam, h0,
+                                               want_carries=train or capture is not None,
                                                gate_b=gate_b, seq=seq, last_only=last_only,
                                                batch_row=batch_row)
+            if capture is not None:   # the session state of a stored history (session.py)
+                capture(x, xc, rg, carries)
         ctx.use_conv = use_conv
         ctx.last_only = last_only
         ctx.has_h0 = h0 is not None and pad_len is None
@@ -218,7 +224,7 @@ class BDLRUCore(torch.autograd.Function):
             kernels.pad_prefix_bwd(conv_b, gate_w, gate_b, lam, ctx.pad_len, dh0.float(),
                                    into=(dconv_b, dgate_w, dgate_b, dlam))
         return (dxz, dconv_w, dconv_b, dgate_w, dgate_b, dlam,
-                dh0 if ctx.has_h0 else None, None, None, None, None, None)
+                dh0 if ctx.has_h0 else None, None, None, None, None, None, None)
 
     @staticmethod
     def _backward_fused(ctx, dy):
@@ -244,7 +250,7 @@ class BDLRUCore(torch.autograd.Function):
             kernels.pad_prefix_bwd(conv_b, gate_w, gate_b, lam, ctx.pad_len, dh0,
                                    into=(dconv_b, dgate_w, dgate_b, dlam))
         return (dxz, dconv_w, dconv_b, dgate_w, dgate_b, dlam,
-                dh0 if ctx.has_h0 else None, None, None, None, None, None)
+                dh0 if ctx.has_h0 else None, None, None, None, None, None, None)
 
 
 def row_pad_lens(lengths: torch.Tensor) -> torch.Tensor:
@@ -257,7 +263,7 @@ def row_pad_lens(lengths: torch.Tensor) -> torch.Tensor:
 
 
 def bd_lru(xz, conv_w, conv_b, gate_w, gate_b, lam, use_conv=True, pad=None, seq=None,
-           last_only=False, observe=None):
+           last_only=False, observe=None, capture=None):
     """Everything between the in- and out-projections of RecBLR.py:170-207.
 
     pad=None: the reference's pad prefix pow2(L) - L for the batch's L.
@@ -269,7 +275,10 @@ def bd_lru(xz, conv_w, conv_b, gate_w, gate_b, lam, use_conv=True, pad=None, seq
     ([ntok, 2H]); the batch's L (for the pad prefix) is seq.L.
     last_only: return only each sequence's last position, [B, H] (fp32); in
     batch order when seq.order is set, else in packed-sequence order.
-    observe: optional callable (x, xc, rg) run in the forward (module hooks)."""
+    observe: optional callable (x, xc, rg) run in the forward (module hooks).
+    capture: optional callable (x, xc, rg, carries) run in the forward with the
+    scan's inputs and its tile carries [B, ceil(L / RB_TILE), H] (session.py's
+    prefill by one forward); selects the three-launch path, as observe does."""
     if pad is None:
         P = pow2_pad_len(seq.L if seq is not None else xz.shape[1])
         pad_len = P if (P and use_conv) else None
@@ -278,6 +287,6 @@ def bd_lru(xz, conv_w, conv_b, gate_w, gate_b, lam, use_conv=True, pad=None, seq
     if not _FOLD_PAD and pad_len is not None:   # A/B: separate autograd node
         h0 = PadPrefix.apply(conv_b, gate_w, gate_b, lam, pad_len)
         return BDLRUCore.apply(xz, conv_w, conv_b, gate_w, gate_b, lam, h0, use_conv, seq,
-                               last_only, None, observe)
+                               last_only, None, observe, capture)
     return BDLRUCore.apply(xz, conv_w, conv_b, gate_w, gate_b, lam, None, use_conv, seq,
-                           last_only, pad_len, observe)
+                           last_only, pad_len, observe, capture)

@@ -31,6 +31,12 @@ a host sync.
 ``step_reference`` is the same step in plain torch ops on whatever device the
 state lives on (CPU included): the checked restatement of the kernel, and the
 path ``step`` takes for shapes the kernel refuses (``kernel_supports``).
+
+``prefill`` opens sessions from stored histories: one step per column
+(``method="steps"``, bitwise a step loop), or one packed forward plus one
+rb_session_capture launch per layer (``method="forward"``,
+session/session_capture.hip), which reads the state off the forward's
+intermediates; ``capture_reference`` is that kernel's restatement in torch ops.
 """
 from __future__ import annotations
 
@@ -45,7 +51,7 @@ from ._lib import RecBLRNativeError
 from .recurrence import pad_prefix_state, pow2_pad_len
 
 __all__ = ["SessionState", "EncoderParams", "step", "step_reference", "prefill",
-           "kernel_supports", "STEPPED", "NO_EVENT", "BAD_ITEM", "BAD_SLOT"]
+           "capture_reference", "kernel_supports", "STEPPED", "NO_EVENT", "BAD_ITEM", "BAD_SLOT"]
 
 _header = _lib._read(os.path.join(_lib._HERE, "session", "recblr_session.h"))
 STEPPED = _lib._define(_header, "RB_SESSION_STEPPED")
@@ -276,8 +282,10 @@ def step_reference(model_or_params, state: SessionState, items, slots=None) -> t
     return y
 
 
-def _refuse(model, p: EncoderParams, state: SessionState) -> None:
-    """What the fused step cannot honour is an error that names the cause."""
+def _refuse(model, p: EncoderParams, state: SessionState, hooks: bool = True) -> None:
+    """What the fused step cannot honour is an error that names the cause.
+    hooks=False: forward hooks are no obstacle (the caller runs the model's
+    forward, which fires them)."""
     if model.training:
         raise ValueError("session step: the model is in training mode (dropout would be "
                          "active); call model.eval()")
@@ -288,6 +296,8 @@ def _refuse(model, p: EncoderParams, state: SessionState) -> None:
         if t.dtype != torch.float32:
             raise RecBLRNativeError(f"session step: parameter {name} is {t.dtype}; the fused "
                                     "step takes fp32 parameters only")
+    if not hooks:
+        return
     # the fused step cannot fire module hooks: refuse rather than skip them
     g = torch.nn.modules.module
     if g._global_forward_hooks or g._global_forward_pre_hooks:
@@ -361,13 +371,174 @@ def step(model, state: SessionState, items, slots=None) -> torch.Tensor:
 
 
 @torch.no_grad()
+def capture_reference(u, xc, rg, lam, gate_b, carries, seq_offsets, slots, h,
+                      conv_state=None) -> None:
+    """rb_session_capture in plain torch ops, on the tensors' device: the
+    state of one layer after each packed sequence's last position, read off
+    that layer's forward.  u, xc [ntok, H] (pre-conv rows, conv + SiLU
+    output), rg [ntok, 2H] (gates GEMM without bias), carries
+    [B, tiles, H] (the state entering every RB_TILE-step tile, as the gate
+    scan wrote them), seq_offsets [B + 1], slots [B].  Writes h[slots[b]] =
+    the carry of sequence b's last tile advanced by that tile's steps, and
+    conv_state[slots[b]] ([N, K - 1, H], or None) = the last K - 1 rows of u,
+    oldest first, zeros before the sequence's start.  A sequence that is
+    empty, has more tiles than carries holds, or names a slot outside
+    [0, N) is skipped; no other slot is written."""
+    T, (N, H) = _lib.RB_TILE, h.shape
+    B, ntok, dev = seq_offsets.numel() - 1, u.shape[0], h.device
+    start, n = seq_offsets[:-1], seq_offsets[1:] - seq_offsets[:-1]
+    valid = (n >= 1) & (n <= carries.shape[1] * T) & (slots >= 0) & (slots < N)
+    nc = n.clamp(1, carries.shape[1] * T)        # skipped sequences: any row in range
+    tile = (nc - 1) // T
+    hv = carries[torch.arange(B, device=dev), tile]
+    nsp = -F.softplus(lam)
+    for s in range(T):
+        t = tile * T + s
+        row = (start + torch.minimum(t, nc - 1)).clamp(0, ntok - 1)
+        alpha = torch.exp(nsp * torch.sigmoid(rg[row, :H] + gate_b[:H]))
+        beta = torch.sqrt(1 - alpha * alpha + 1e-8) * torch.sigmoid(rg[row, H:] + gate_b[H:])
+        hv = torch.where((t < nc)[:, None], hv * alpha + beta * xc[row], hv)
+    idx = slots[valid]
+    h[idx] = hv[valid]
+    if conv_state is not None and conv_state.shape[1]:
+        hist = conv_state.shape[1]
+        pos = n[:, None] - hist + torch.arange(hist, device=dev)[None]        # [B, K - 1]
+        rows = (start[:, None] + pos.clamp_min(0)).clamp(0, ntok - 1)
+        conv_state[idx] = torch.where((pos >= 0)[..., None], u[rows], 0.0)[valid]
+
+
+def _row_stride(t: torch.Tensor, C: int) -> int:
+    return t.stride(0) if t.shape[0] > 1 else C
+
+
+def _capture_kernel(state: SessionState, i: int, u, xc, rg, lam, gate_b, carries, seq, slots,
+                    K: int) -> None:
+    """One launch (rb_session_capture): layer i's state from its forward."""
+    H, conv = u.shape[1], state.conv[i]
+    _lib.call_session(
+        "rb_session_capture", u.data_ptr(), _row_stride(u, H), xc.data_ptr(), _row_stride(xc, H),
+        rg.data_ptr(), _row_stride(rg, 2 * H), lam.data_ptr(), gate_b.data_ptr(),
+        carries.data_ptr(), seq.offsets.data_ptr(), slots.data_ptr(), state.h[i].data_ptr(),
+        conv.data_ptr() if conv is not None else None, seq.B, seq.L, state.capacity, H, K,
+        kernels._stream(u))
+
+
+def _capture_ok(H: int, K: int, u, xc, rg, *aligned) -> bool:
+    """Whether rb_session_capture's argument check passes: 16-byte row
+    pieces (H and the row strides multiples of 4, aligned pointers)."""
+    if H % 4 or not 1 <= K <= 8:
+        return False
+    if any(t.stride(1) != 1 or _row_stride(t, C) % 4 for t, C in ((u, H), (xc, H), (rg, 2 * H))):
+        return False
+    return all(t is None or (t.is_contiguous() and t.data_ptr() % 16 == 0) for t in aligned) \
+        and all(t.data_ptr() % 16 == 0 for t in (u, xc, rg))
+
+
+def _prefill_forward(model, state: SessionState, item_seq, item_seq_len, slots, reset):
+    """prefill(method="forward"), see prefill."""
+    from .model import HOST_LENGTHS, attach_host_lengths
+
+    if not reset:
+        raise ValueError('prefill(method="forward") needs reset=True: the forward starts from '
+                         'the empty history (method="steps" appends to a slot)')
+    item_seq = torch.as_tensor(item_seq, dtype=torch.int64)
+    if item_seq.dim() != 2:
+        raise ValueError("item_seq must be [B, T]")
+    B, T = item_seq.shape
+    host_len = getattr(item_seq_len, HOST_LENGTHS, None)
+    if host_len is None:           # lengths only on the device: one sync, as forward()
+        host_len = torch.as_tensor(item_seq_len).to("cpu")
+    host_len = host_len.to(torch.int64).reshape(-1)
+    if host_len.numel() != B:
+        raise ValueError("item_seq and item_seq_len must have the same number of rows")
+    longest = int(host_len.max()) if B else 0
+    if longest > state.seq_len:
+        raise ValueError(f'prefill(method="forward"): a history of {longest} items is longer '
+                         f"than the state's window seq_len = {state.seq_len} "
+                         '(method="steps" continues past the window)')
+    if longest > T:
+        raise ValueError(f'prefill(method="forward"): a length of {longest} exceeds item_seq\'s '
+                         f"width {T}")
+    p = _params(model)
+    _refuse(model, p, state, hooks=False)
+    _match(p, state)
+    dev = state.device
+    if slots is None:
+        if B > state.capacity:
+            raise ValueError(f"{B} rows for a state of {state.capacity} slots")
+        slots = torch.arange(B, device=dev)
+    else:
+        slots = _slot_tensor(slots, state)
+        if slots.numel() != B:
+            raise ValueError("item_seq and slots must have the same number of rows")
+    state.reset(slots)
+    status = torch.full((B,), NO_EVENT, device=dev, dtype=torch.int32)
+    y = torch.zeros((B, p.d), device=dev, dtype=torch.float32)
+    state.status = status
+    rows_h = torch.nonzero(host_len > 0).reshape(-1)    # a row of length 0 stays reset
+    if rows_h.numel() == 0:
+        return y
+    seq, lens_h = item_seq.to(dev), host_len
+    if rows_h.numel() < B:
+        rows = rows_h.to(dev)
+        seq, slots, lens_h = seq.index_select(0, rows), slots.index_select(0, rows), host_len[rows_h]
+    # the state's window: its pad prefix pow2(L) - L is the forward's.  Ids are
+    # clamped into the table (forward()'s contract is ids in [1, V))
+    L = state.seq_len
+    seq = (seq[:, :L] if T >= L else F.pad(seq, (0, L - T))).clamp(0, p.V - 1).contiguous()
+    lens = attach_host_lengths(lens_h.to(dev), lens_h)
+    K = p.K if p.use_conv else 1
+    packed_slots = []
+
+    def sink(i, packed, u, xc, rg, carries):
+        if not packed_slots:        # sequence b of the packed order is row packed.order[b]
+            packed_slots.append(slots.index_select(0, packed.order).contiguous())
+        lam, gate_b = p.layer(i, "lam"), p.layer(i, "b_gate")
+        if _capture_ok(p.H, K, u, xc, rg, lam, gate_b, carries, state.h[i], state.conv[i]):
+            _capture_kernel(state, i, u, xc, rg, lam, gate_b, carries, packed, packed_slots[0], K)
+        else:
+            capture_reference(u, xc, rg, lam, gate_b, carries, packed.offsets, packed_slots[0],
+                              state.h[i], state.conv[i])
+
+    with torch.cuda.device(dev):
+        out = model._forward_packed(seq, lens, None, capture=sink)
+    state.out[slots] = out
+    state.count[slots] = lens
+    if rows_h.numel() < B:
+        status[rows] = STEPPED
+        y[rows] = out
+        return y
+    status.fill_(STEPPED)
+    return out
+
+
+@torch.no_grad()
 def prefill(model, state: SessionState, item_seq, item_seq_len, slots=None,
-            reset: bool = True) -> torch.Tensor:
+            reset: bool = True, method: str = "steps") -> torch.Tensor:
     """Open sessions from stored histories: item_seq [B, T] right-padded,
-    item_seq_len [B]; one step per column (item 0 for rows already
-    exhausted), so exact by construction.  The slots are reset first unless
-    reset=False (which appends to what they hold).  Returns the rows'
-    seq_output [B, d].  A state on the CPU steps with step_reference."""
+    item_seq_len [B].  Returns the rows' seq_output [B, d].
+
+    method="steps" (the default): one step per column (item 0 for rows
+    already exhausted), so exact by construction.  The slots are reset first
+    unless reset=False (which appends to what they hold).  A state on the CPU
+    steps with step_reference.
+
+    method="forward": one packed forward over the histories
+    (RecBLR._forward_packed at the state's window, whatever RECBLR_PACKED
+    says) and one rb_session_capture launch per layer, which reads the slots'
+    state off the forward's intermediates: h from the gate scan's tile
+    carries, the conv history from the in-projection's rows; out is the
+    forward's row, count the length.  No step launch.  It needs reset=True,
+    every length <= state.seq_len, item ids of [1, V) in the valid prefixes
+    (forward()'s contract; step's "item 0 = no event" has no meaning inside a
+    history), an eval-mode fp32 model and a GPU state; forward hooks fire.  A
+    row of length 0 is reset and returns its zero row.  The state agrees with
+    the step-built one to rounding (the forward's f16x3 projections against
+    the step's fp32 MFMA), not bitwise."""
+    if method == "forward":
+        return _prefill_forward(model, state, item_seq, item_seq_len, slots, reset)
+    if method != "steps":
+        raise ValueError(f'prefill: method must be "steps" or "forward", got {method!r}')
     item_seq = torch.as_tensor(item_seq, dtype=torch.int64)
     if item_seq.dim() != 2:
         raise ValueError("item_seq must be [B, T]")

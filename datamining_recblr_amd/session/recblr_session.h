@@ -1,7 +1,9 @@
 /* recblr_session.h — stateful session inference (libdmrecblr_session.so).
  *
- * One entry point advances the whole RecBLR encoder by one event per session
- * slot in one launch (python: datamining_recblr_amd/session.py).  Its own
+ * rb_session_step advances the whole RecBLR encoder by one event per session
+ * slot in one launch; rb_session_capture reads a layer's session state off
+ * its forward over stored histories (python:
+ * datamining_recblr_amd/session.py).  Its own
  * library, beside the product library, as the probe and experimental
  * libraries are ("Stateful sessions").  Same conventions as the
  * boundary (include/recblr_hip.h): raw device pointers, int status (0 = ok,
@@ -86,6 +88,35 @@ int rb_session_step(const rb_session_layer* layers, int64_t n_layers, const floa
                     const int64_t* slots, int64_t* count, float* out, float* y,
                     int32_t* status, int64_t B, int64_t N, int64_t V, int64_t d, int64_t H,
                     int64_t K, int disable_conv1d, int disable_ffn, void* stream);
+
+/* The state of one layer after each of B packed sequences' last position,
+ * read off that layer's forward (one launch per layer; python:
+ * session.prefill(method="forward")).  Sequence b occupies rows
+ * seq_offsets[b] .. seq_offsets[b+1] of the packed activations and has
+ * n = seq_offsets[b+1] - seq_offsets[b] positions; for n >= 1:
+ *   h[slots[b]] = the carry of tile j = (n - 1) / RB_TILE advanced by the
+ *   steps 16 j .. n - 1 of rb_gate_scan_fwd's recurrence: r | i = rg + gate_b;
+ *   alpha = exp(-softplus(lam) sigmoid(r)); beta = sqrt(1 - alpha^2 + 1e-8)
+ *   sigmoid(i); h = alpha h + beta xc;
+ *   conv_state[slots[b], k] = the u row at position n - (K - 1) + k for k in
+ *   [0, K - 1), oldest first; zeros for a position before the sequence start.
+ * u [ntok, H] the pre-conv rows (the x half of the in-projection), xc
+ * [ntok, H] the conv + SiLU output (xc == u with disable_conv1d), rg
+ * [ntok, 2H] the gates GEMM's output without its bias; u_rs, xc_rs, rg_rs
+ * their row strides in floats; lam [H]; gate_b [2H]; carries
+ * [B, ceil(L / RB_TILE), H] as rb_gate_scan_fwd(_last) wrote them for the
+ * same B, L and seq_offsets; seq_offsets [B + 1]; slots [B], unique; h
+ * [N, H]; conv_state [N, K - 1, H], NULL only when K == 1 or xc == u (then
+ * no history is written).  A sequence with n < 1, with more tiles than
+ * carries holds (n > RB_TILE ceil(L / RB_TILE)) or with a slot outside
+ * [0, N) is skipped before any address is formed from it; the other
+ * slots of h and conv_state are not written.  H a positive multiple of 4,
+ * strides multiples of 4, pointers 16-byte aligned, K in [1, 8]. */
+int rb_session_capture(const float* u, int64_t u_rs, const float* xc, int64_t xc_rs,
+                       const float* rg, int64_t rg_rs, const float* lam, const float* gate_b,
+                       const float* carries, const int64_t* seq_offsets, const int64_t* slots,
+                       float* h, float* conv_state, int64_t B, int64_t L, int64_t N, int64_t H,
+                       int64_t K, void* stream);
 
 #ifdef __cplusplus
 }

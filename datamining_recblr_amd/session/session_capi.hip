@@ -1,5 +1,6 @@
 // session_capi.hip — the extern "C" entry points of the session library
-// (recblr_session.h): argument checks, then the launcher in session_step.hip.
+// (recblr_session.h): argument checks, then the launchers in session_step.hip
+// and session_capture.hip.
 // Built with hidden visibility, so its error helpers (rb::fail,
 // rb::launch_status) are its own and never interpose the product library's.
 #include "../csrc/common.h"
@@ -33,6 +34,11 @@ int launch_session_step(const rb_session_layer* layers, int n_layers, const floa
                         const int64_t* slots, int64_t* count, float* out, float* y,
                         int32_t* status, int64_t B, int64_t N, int64_t V, int d, int H, int K,
                         bool use_conv, bool use_ffn, hipStream_t st);
+int launch_session_capture(const float* u, int64_t u_rs, const float* xc, int64_t xc_rs,
+                           const float* rg, int64_t rg_rs, const float* lam, const float* gate_b,
+                           const float* carries, const int64_t* offs, const int64_t* slots,
+                           float* h, float* conv_state, int64_t B, int L, int64_t N, int H, int K,
+                           hipStream_t st);
 }  // namespace rb
 
 using namespace rb;
@@ -88,6 +94,36 @@ RB_EXPORT int rb_session_step(const rb_session_layer* layers, int64_t n_layers, 
   return launch_session_step(layers, (int)n_layers, emb, ln_w, ln_b, eps, items, slots, count,
                              out, y, status, B, N, V, (int)d, (int)H, (int)K, use_conv, use_ffn,
                              reinterpret_cast<hipStream_t>(stream));
+}
+
+RB_EXPORT int rb_session_capture(const float* u, int64_t u_rs, const float* xc, int64_t xc_rs,
+                       const float* rg, int64_t rg_rs, const float* lam, const float* gate_b,
+                       const float* carries, const int64_t* seq_offsets, const int64_t* slots,
+                       float* h, float* conv_state, int64_t B, int64_t L, int64_t N, int64_t H,
+                       int64_t K, void* stream) {
+  if (!u || !xc || !rg || !lam || !gate_b || !carries || !seq_offsets || !slots || !h)
+    return fail("rb_session_capture: null pointer");
+  if (K < 1 || K > 8) return fail("rb_session_capture: conv kernel size K must be in [1, 8]");
+  if (H <= 0 || H % 4 || H > (1 << 20))
+    return fail("rb_session_capture: H must be a positive multiple of 4");
+  if (B <= 0 || L <= 0 || N <= 0) return fail("rb_session_capture: B, L and N must be positive");
+  if (B >= (1LL << 31) || L >= (1LL << 31) || N >= (1LL << 31))
+    return fail("rb_session_capture: B, L and N must be < 2^31");
+  // one wave per (sequence, 256 channels), four waves per workgroup
+  if (B * ((H + 255) / 256) >= (1LL << 26))
+    return fail("rb_session_capture: too many (sequence, channel span) pairs for one launch");
+  if (u_rs < H || xc_rs < H || rg_rs < 2 * H || u_rs % 4 || xc_rs % 4 || rg_rs % 4)
+    return fail("rb_session_capture: row strides must be multiples of 4, at least H (rg: 2H)");
+  if (!conv_state && K > 1 && xc != u)
+    return fail("rb_session_capture: conv_state may be NULL only when K == 1 or xc == u");
+  // every row piece is one 16-byte access per lane
+  if (!aligned16(u) || !aligned16(xc) || !aligned16(rg) || !aligned16(lam) ||
+      !aligned16(gate_b) || !aligned16(carries) || !aligned16(h) || !aligned16(conv_state))
+    return fail("rb_session_capture: u, xc, rg, lam, gate_b, carries, h and conv_state must be "
+                "16-byte aligned");
+  return launch_session_capture(u, u_rs, xc, xc_rs, rg, rg_rs, lam, gate_b, carries, seq_offsets,
+                                slots, h, conv_state, B, (int)L, N, (int)H, (int)K,
+                                reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -11,6 +11,12 @@ then timed in windows of back-to-back calls between two device events
 figure is the median window's time per call.  Before timing, the sessions
 are prefilled with the L items and their rows compared with forward's.
 
+A second leg times opening the B sessions from their histories:
+session_prefill(method="steps"), L step launches, against
+session_prefill(method="forward"), one packed forward plus one capture launch
+per layer; same windows, alternating, with the largest deviation of the two
+states' h, conv history and out (prefill_rows).
+
 Prints one JSON line; --out also writes it to a file."""
 from __future__ import annotations
 
@@ -42,6 +48,36 @@ def window_ms(fn, calls: int) -> float:
     return e0.elapsed_time(e1) / calls
 
 
+def prefill_leg(model, B: int, seq, lens, windows: int) -> dict:
+    """Opening B sessions from their L-item histories: session_prefill by a
+    step per column (method="steps", the default) against one packed forward
+    plus a capture launch per layer (method="forward"), alternating window by
+    window; and how far the two states are apart."""
+    by_steps, by_fwd = model.session_open(B), model.session_open(B)
+    steps = lambda: model.session_prefill(by_steps, seq, lens)                    # noqa: E731
+    fwd = lambda: model.session_prefill(by_fwd, seq, lens, method="forward")      # noqa: E731
+    steps_calls = 2                       # 2 x 200 step launches, as the step leg's window
+    fwd_calls = 20 if B <= 64 else 5      # as the forward leg's window
+    for _ in range(2):
+        window_ms(steps, steps_calls)
+        window_ms(fwd, fwd_calls)
+    ts, tf = [], []
+    for _ in range(windows):
+        ts.append(window_ms(steps, steps_calls))
+        tf.append(window_ms(fwd, fwd_calls))
+    s, f = statistics.median(ts), statistics.median(tf)
+    dev = lambda a, b: max((x - y).abs().max().item() for x, y in zip(a, b))     # noqa: E731
+    return dict(B=B, steps_ms=round(s, 4), steps_ms_min=round(min(ts), 4),
+                steps_ms_max=round(max(ts), 4), forward_ms=round(f, 4),
+                forward_ms_min=round(min(tf), 4), forward_ms_max=round(max(tf), 4),
+                steps_over_forward=round(s / f, 1),
+                h_max_abs_dev=dev(by_fwd.h, by_steps.h),
+                conv_max_abs_dev=dev(by_fwd.conv, by_steps.conv),
+                out_max_abs_dev=dev([by_fwd.out], [by_steps.out]),
+                h_max_abs=max(h.abs().max().item() for h in by_steps.h),
+                count_equal=bool(torch.equal(by_fwd.count, by_steps.count)))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 64, 2048])
@@ -56,7 +92,7 @@ def main() -> None:
                MAX_ITEM_LIST_LENGTH=L)
     torch.manual_seed(2020)
     model = RecBLR(cfg, SyntheticDataset(N_ITEMS)).to(dev).eval()
-    rows = []
+    rows, prefill_rows = [], []
     with torch.no_grad():
         for B in args.batches:
             g = torch.Generator().manual_seed(B)
@@ -86,8 +122,9 @@ def main() -> None:
                              forward_ms_min=round(min(tf), 4), forward_ms_max=round(max(tf), 4),
                              forward_over_step=round(f / s, 1),
                              prefill_vs_forward_max_abs_err=err))
+            prefill_rows.append(prefill_leg(model, B, seq, lens, args.windows))
     line = json.dumps(dict(bench="session_step", d=128, layers=2, K=4, L=L, n_items=N_ITEMS,
-                           windows=args.windows, rows=rows))
+                           windows=args.windows, rows=rows, prefill_rows=prefill_rows))
     print(line)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
