@@ -479,6 +479,15 @@ class RecBLR(SequentialRecommender):
 
         return step(self, state, items, slots)
 
+    def session_append(self, state, item_seq, item_seq_len=None, slots=None, reset: bool = False,
+                       return_all: bool = False):
+        """Append several events per row (item_seq [B, W], right-padded with
+        0), 16 columns per launch, and return the slots' seq_output [B, d]
+        (session.append); bitwise a session_step per column."""
+        from .session import append
+
+        return append(self, state, item_seq, item_seq_len, slots, reset, return_all)
+
     def session_prefill(self, state, item_seq, item_seq_len, slots=None, reset: bool = True,
                         method: str = "steps"):
         """Open sessions from stored histories (session.prefill): one step

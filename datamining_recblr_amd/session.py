@@ -37,6 +37,13 @@ path ``step`` takes for shapes the kernel refuses (``kernel_supports``).
 rb_session_capture launch per layer (``method="forward"``,
 session/session_capture.hip), which reads the state off the forward's
 intermediates; ``capture_reference`` is that kernel's restatement in torch ops.
+
+``append`` adds several events per slot at once: 16 columns of a right-padded
+``[B, W]`` batch per launch (rb_session_append, session/session_append.hip: a
+workgroup's 16 MFMA rows are T consecutive events of 16 / T slots), bitwise
+what a ``step`` per column leaves, appendable to a live slot, and with
+``reset=True`` a third way to open sessions from histories.
+``append_reference`` is its restatement as a column loop of ``step_reference``.
 """
 from __future__ import annotations
 
@@ -51,7 +58,8 @@ from ._lib import RecBLRNativeError
 from .recurrence import pad_prefix_state, pow2_pad_len
 
 __all__ = ["SessionState", "EncoderParams", "step", "step_reference", "prefill",
-           "capture_reference", "kernel_supports", "STEPPED", "NO_EVENT", "BAD_ITEM", "BAD_SLOT"]
+           "capture_reference", "append", "append_reference", "kernel_supports", "STEPPED",
+           "NO_EVENT", "BAD_ITEM", "BAD_SLOT"]
 
 _header = _lib._read(os.path.join(_lib._HERE, "session", "recblr_session.h"))
 STEPPED = _lib._define(_header, "RB_SESSION_STEPPED")
@@ -60,6 +68,7 @@ BAD_ITEM = _lib._define(_header, "RB_SESSION_BAD_ITEM")
 BAD_SLOT = _lib._define(_header, "RB_SESSION_BAD_SLOT")
 MAX_LAYERS = _lib._define(_header, "RB_SESSION_MAX_LAYERS")
 MAX_LDS = _lib._define(_header, "RB_SESSION_MAX_LDS")
+TILE = _lib._define(_header, "RB_SESSION_TILE")   # events per rb_session_append launch
 LN_EPS = 1e-12   # every LayerNorm of the model (RecBLR.py:45, :131, :216)
 
 _LAYER_FIELDS = ("w_in", "conv_w", "conv_b", "w_gate", "b_gate", "lam", "w_out", "ln_w", "ln_b",
@@ -282,13 +291,17 @@ def step_reference(model_or_params, state: SessionState, items, slots=None) -> t
     return y
 
 
+def _refuse_training(model) -> None:
+    if model.training:
+        raise ValueError("session step: the model is in training mode (dropout would be "
+                         "active); call model.eval()")
+
+
 def _refuse(model, p: EncoderParams, state: SessionState, hooks: bool = True) -> None:
     """What the fused step cannot honour is an error that names the cause.
     hooks=False: forward hooks are no obstacle (the caller runs the model's
     forward, which fires them)."""
-    if model.training:
-        raise ValueError("session step: the model is in training mode (dropout would be "
-                         "active); call model.eval()")
+    _refuse_training(model)
     if state.device.type != "cuda":
         raise RecBLRNativeError(f"session step: the state is on {state.device}; the HIP path "
                                 "needs a ROCm GPU (step_reference runs anywhere)")
@@ -368,6 +381,171 @@ def step(model, state: SessionState, items, slots=None) -> torch.Tensor:
         _step_kernel(p, state, _plan(p, state), items, slots, y, status)
     state.status = status
     return y
+
+
+def _append_rows(state: SessionState, item_seq, item_seq_len, slots):
+    """append's arguments on the state's device: items [B, W'] int64 with the
+    columns at or past a row's length zeroed, W' cut to the longest row where
+    the lengths are known on the host; slots (or None)."""
+    items = torch.as_tensor(item_seq, dtype=torch.int64)
+    if items.dim() == 1:
+        items = items[:, None]
+    if items.dim() != 2:
+        raise ValueError("item_seq must be [B, W] (or [B]: one event per row)")
+    B, W = items.shape
+    if B == 0:
+        raise ValueError("item_seq must hold at least one row")
+    items = items.to(state.device)
+    if item_seq_len is not None:
+        host_len = getattr(item_seq_len, "_recblr_host_lengths", None)
+        if host_len is None and not (isinstance(item_seq_len, torch.Tensor)
+                                     and item_seq_len.device.type != "cpu"):
+            host_len = torch.as_tensor(item_seq_len)
+        lens = torch.as_tensor(item_seq_len).to(state.device).reshape(-1, 1)
+        if lens.shape[0] != B:
+            raise ValueError("item_seq and item_seq_len must have the same number of rows")
+        if host_len is not None:        # known on the host: stop at the longest row
+            W = min(W, max(int(host_len.max()), 0))
+        items = items[:, :W]
+        items = torch.where(torch.arange(W, device=state.device)[None] < lens, items,
+                            torch.zeros_like(items))
+    if slots is None:
+        if B > state.capacity:
+            raise ValueError(f"{B} rows for a state of {state.capacity} slots")
+    else:
+        slots = _slot_tensor(slots, state)
+        if slots.numel() != B:
+            raise ValueError("item_seq and slots must have the same number of rows")
+    return items, slots, B, W
+
+
+def _stored_rows(state: SessionState, slots, B: int) -> torch.Tensor:
+    """The slots' stored out rows [B, d]; zeros for a slot outside the state."""
+    if slots is None:
+        return state.out[:B].clone()
+    y = state.out[slots.clamp(0, state.capacity - 1)]
+    y[(slots < 0) | (slots >= state.capacity)] = 0.0
+    return y
+
+
+def _first_status(seen, new):
+    """Per row the first status over the chunks that is not NO_EVENT."""
+    return new if seen is None else torch.where(seen == NO_EVENT, new, seen)
+
+
+@torch.no_grad()
+def append_reference(model_or_params, state: SessionState, item_seq, item_seq_len=None,
+                     slots=None, reset: bool = False, return_all: bool = False):
+    """``append`` as a column loop of ``step_reference``, on the state's
+    device: the checked restatement of rb_session_append, one 16-column chunk
+    after the other.  Within a chunk a row's events are the entries before its
+    first 0; a row with an event outside [0, V) among them is masked for the
+    whole chunk (BAD_ITEM: nothing of its slot is touched)."""
+    p = _params(model_or_params)
+    _match(p, state)
+    items, slots, B, W = _append_rows(state, item_seq, item_seq_len, slots)
+    if reset:
+        state.reset(slots if slots is not None else torch.arange(B))
+    y, status, cols = _stored_rows(state, slots, B), None, []
+    for c0 in range(0, W, TILE):
+        chunk = items[:, c0:c0 + TILE]
+        live = (chunk != 0).cumprod(1).bool()
+        bad = (live & ((chunk < 0) | (chunk >= p.V))).any(1)
+        fed = torch.where(live & ~bad[:, None], chunk, torch.zeros_like(chunk))
+        st = torch.full((B,), NO_EVENT, device=state.device, dtype=torch.int32)
+        for t in range(chunk.shape[1]):
+            y = step_reference(p, state, fed[:, t], slots)
+            if t == 0:
+                st = state.status.clone()          # STEPPED, NO_EVENT or BAD_SLOT
+            cols.append(torch.where((fed[:, t] != 0)[:, None] & (state.status == STEPPED)[:, None],
+                                    y, torch.zeros_like(y)))
+        st[bad & (st != BAD_SLOT)] = BAD_ITEM
+        status = _first_status(status, st)
+    if status is None:
+        status = torch.full((B,), NO_EVENT, device=state.device, dtype=torch.int32)
+        if slots is not None:
+            status[(slots < 0) | (slots >= state.capacity)] = BAD_SLOT
+    state.status = status
+    if not return_all:
+        return y
+    y_all = torch.stack(cols, 1) if cols else y.new_zeros((B, 0, p.d))
+    return y, y_all
+
+
+def _append_kernel(p: EncoderParams, state: SessionState, layers, items, slots, y, y_all,
+                   status) -> None:
+    """One launch (rb_session_append): items [B, T], T events per row."""
+    t = p.t
+    B, T = items.shape
+    _lib.call_session(
+        "rb_session_append", ctypes.addressof(layers), p.num_layers,
+        t["item_embedding.weight"].data_ptr(), t["layer_norm.weight"].data_ptr(),
+        t["layer_norm.bias"].data_ptr(), LN_EPS, items.data_ptr(),
+        slots.data_ptr() if slots is not None else None, state.count.data_ptr(),
+        state.out.data_ptr(), y.data_ptr(), y_all.data_ptr() if y_all is not None else None,
+        status.data_ptr(), B, T, state.capacity, p.V, p.d, p.H, p.K, int(not p.use_conv),
+        int(not p.use_ffn), kernels._stream(y))
+
+
+@torch.no_grad()
+def append(model, state: SessionState, item_seq, item_seq_len=None, slots=None,
+           reset: bool = False, return_all: bool = False):
+    """Append row b's events item_seq[b, :] to slot slots[b] (slots None: slot
+    b), 16 columns per launch, and return the slots' seq_output [B, d]
+    afterwards; with return_all=True ``(y, y_all [B, W', d])``, the output
+    after every event (zeros where a row has none), W' the columns processed.
+
+    item_seq: int64 [B, W] right-padded with 0 (or [B]: W = 1).  With
+    item_seq_len the columns at or past a row's length are zeroed; lengths
+    known on the host (a list, a CPU tensor, attach_host_lengths) also stop
+    the loop at the longest row, lengths on the device cost no sync and all W
+    columns are processed.  Each chunk of 16 columns is one rb_session_append
+    launch; a last chunk of r < 16 columns is zero-padded to the smallest T of
+    1, 2, 4, 8, 16 that holds it (a workgroup carries 16 / T rows).  A slot is
+    left bitwise as a ``step`` per column would leave it, past the window too.
+
+    reset=True resets the rows' slots first: ceil(L / 16) launches open
+    sessions from L-item histories.  ``state.status`` holds per row the first
+    status over the chunks that is not NO_EVENT.  A row with an id outside
+    [0, V) among a chunk's events is masked for that chunk (BAD_ITEM) and keeps
+    the events of the chunks before it: a launch is atomic per row, the call
+    is not.  slots, the refusals and the fallback are ``step``'s: a shape the
+    kernel refuses (kernel_supports) or a state on the CPU runs
+    append_reference."""
+    p = _params(model)
+    _refuse_training(model)
+    if state.device.type != "cuda":
+        return append_reference(p, state, item_seq, item_seq_len, slots, reset, return_all)
+    _refuse(model, p, state)
+    _match(p, state)
+    if not kernel_supports(p.d, p.H, p.K, p.num_layers):
+        return append_reference(p, state, item_seq, item_seq_len, slots, reset, return_all)
+    items, slots, B, W = _append_rows(state, item_seq, item_seq_len, slots)
+    if reset:
+        state.reset(slots if slots is not None else torch.arange(B))
+    kw = dict(device=state.device, dtype=torch.float32)
+    y, status, cols = (torch.empty((B, p.d), **kw) if W else None), None, []
+    with torch.cuda.device(state.device):
+        layers = _plan(p, state)
+        for c0 in range(0, W, TILE):
+            r = min(TILE, W - c0)
+            T = 1 << (r - 1).bit_length()
+            chunk = F.pad(items[:, c0:c0 + r], (0, T - r)).contiguous()
+            y_all = torch.empty((B, T, p.d), **kw) if return_all else None
+            st = torch.empty((B,), device=state.device, dtype=torch.int32)
+            _append_kernel(p, state, layers, chunk, slots, y, y_all, st)
+            status = _first_status(status, st)
+            if return_all:
+                cols.append(y_all[:, :r])
+    if y is None:                       # no column at all
+        y = _stored_rows(state, slots, B)
+        status = torch.full((B,), NO_EVENT, device=state.device, dtype=torch.int32)
+        if slots is not None:
+            status[(slots < 0) | (slots >= state.capacity)] = BAD_SLOT
+    state.status = status
+    if not return_all:
+        return y
+    return y, (torch.cat(cols, 1) if cols else y.new_zeros((B, 0, p.d)))
 
 
 @torch.no_grad()

@@ -1,9 +1,9 @@
 /* recblr_session.h — stateful session inference (libdmrecblr_session.so).
  *
  * rb_session_step advances the whole RecBLR encoder by one event per session
- * slot in one launch; rb_session_capture reads a layer's session state off
- * its forward over stored histories (python:
- * datamining_recblr_amd/session.py).  Its own
+ * slot in one launch, rb_session_append by up to 16 consecutive events per
+ * slot; rb_session_capture reads a layer's session state off its forward
+ * over stored histories (python: datamining_recblr_amd/session.py).  Its own
  * library, beside the product library, as the probe and experimental
  * libraries are ("Stateful sessions").  Same conventions as the
  * boundary (include/recblr_hip.h): raw device pointers, int status (0 = ok,
@@ -23,7 +23,7 @@ extern "C" {
 #define RB_SESSION_TILE 16
 /* the LDS of one gfx950 compute unit: the step kernel's budget */
 #define RB_SESSION_MAX_LDS 163840
-/* row status written by rb_session_step */
+/* row status written by rb_session_step and rb_session_append */
 #define RB_SESSION_NO_EVENT 0
 #define RB_SESSION_STEPPED 1
 #define RB_SESSION_BAD_ITEM (-1)
@@ -88,6 +88,29 @@ int rb_session_step(const rb_session_layer* layers, int64_t n_layers, const floa
                     const int64_t* slots, int64_t* count, float* out, float* y,
                     int32_t* status, int64_t B, int64_t N, int64_t V, int64_t d, int64_t H,
                     int64_t K, int disable_conv1d, int disable_ffn, void* stream);
+
+/* Up to T consecutive events per row in one launch.  items [B, T] int64,
+ * row-major, right-padded: row b's events are the n_b entries before its
+ * first 0 (entries after it are ignored).  T is 1, 2, 4, 8 or 16; a workgroup
+ * owns 16 / T consecutive rows, tile row r being event r % T of call row
+ * r / T.  Row b's slot (slots as for the step: unique, NULL = slot b) is left
+ * as n_b successive rb_session_step calls with items[b, 0 .. n_b) would
+ * leave it, bit for bit: h, conv_state, out, and count += n_b; the state is
+ * written once, after the last event.  y [B, d] (optional) receives the
+ * slot's out afterwards (the stored one when n_b == 0; zeros for a bad
+ * slot), y_all [B, T, d] (optional) the output after each event, zeros at
+ * positions >= n_b and for masked rows, status [B] (optional)
+ * RB_SESSION_STEPPED when n_b >= 1, NO_EVENT when items[b, 0] == 0, BAD_SLOT
+ * for a slot outside [0, N), BAD_ITEM when any of the n_b events lies outside
+ * [0, V).  A BAD_ITEM row is masked as a whole: nothing of its slot is
+ * touched.  Every id is range-checked before an address is formed from it.
+ * The other arguments and their limits are rb_session_step's; y_all 16-byte
+ * aligned when given. */
+int rb_session_append(const rb_session_layer* layers, int64_t n_layers, const float* emb,
+                      const float* ln_w, const float* ln_b, float eps, const int64_t* items,
+                      const int64_t* slots, int64_t* count, float* out, float* y, float* y_all,
+                      int32_t* status, int64_t B, int64_t T, int64_t N, int64_t V, int64_t d,
+                      int64_t H, int64_t K, int disable_conv1d, int disable_ffn, void* stream);
 
 /* The state of one layer after each of B packed sequences' last position,
  * read off that layer's forward (one launch per layer; python:

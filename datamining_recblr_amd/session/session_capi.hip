@@ -1,6 +1,6 @@
 // session_capi.hip — the extern "C" entry points of the session library
-// (recblr_session.h): argument checks, then the launchers in session_step.hip
-// and session_capture.hip.
+// (recblr_session.h): argument checks, then the launchers in session_step.hip,
+// session_append.hip and session_capture.hip.
 // Built with hidden visibility, so its error helpers (rb::fail,
 // rb::launch_status) are its own and never interpose the product library's.
 #include "../csrc/common.h"
@@ -34,6 +34,11 @@ int launch_session_step(const rb_session_layer* layers, int n_layers, const floa
                         const int64_t* slots, int64_t* count, float* out, float* y,
                         int32_t* status, int64_t B, int64_t N, int64_t V, int d, int H, int K,
                         bool use_conv, bool use_ffn, hipStream_t st);
+int launch_session_append(const rb_session_layer* layers, int n_layers, const float* emb,
+                          const float* ln_w, const float* ln_b, float eps, const int64_t* items,
+                          const int64_t* slots, int64_t* count, float* out, float* y,
+                          float* y_all, int32_t* status, int64_t B, int T, int64_t N, int64_t V,
+                          int d, int H, int K, bool use_conv, bool use_ffn, hipStream_t st);
 int launch_session_capture(const float* u, int64_t u_rs, const float* xc, int64_t xc_rs,
                            const float* rg, int64_t rg_rs, const float* lam, const float* gate_b,
                            const float* carries, const int64_t* offs, const int64_t* slots,
@@ -57,43 +62,74 @@ RB_EXPORT int64_t rb_session_lds_bytes(int64_t d, int64_t H) {
   return session_lds_bytes(d, H);
 }
 
+// The checks rb_session_step and rb_session_append share; `who` prefixes the
+// message ("rb_session_step: ").
+static int check_encoder_args(const std::string& who, const rb_session_layer* layers,
+                              int64_t n_layers, const float* emb, const float* ln_w,
+                              const float* ln_b, float eps, const int64_t* items,
+                              const int64_t* count, const float* out, const float* y, int64_t B,
+                              int64_t N, int64_t V, int64_t d, int64_t H, int64_t K,
+                              bool use_conv, bool use_ffn) {
+  const auto no = [&](const char* what) { return fail((who + what).c_str()); };
+  if (!layers || !emb || !ln_w || !ln_b || !items || !count || !out) return no("null pointer");
+  if (n_layers < 1 || n_layers > RB_SESSION_MAX_LAYERS) return no("n_layers must be in [1, 8]");
+  if (K < 1 || K > 8) return no("conv kernel size K must be in [1, 8]");
+  if (d <= 0 || H <= 0 || d % 16 || H % 16 || d > (1 << 20) || H > (1 << 20))
+    return no("d and H must be positive multiples of 16");
+  if (B <= 0 || N <= 0 || V <= 0) return no("B, N and V must be positive");
+  if (B >= (1LL << 31) || N >= (1LL << 31) || V >= (1LL << 31))
+    return no("B, N and V must be < 2^31");
+  if (session_lds_bytes(d, H) > RB_SESSION_MAX_LDS)
+    return no("shape needs more LDS than a compute unit has (160 KiB)");
+  if (!(eps > 0.0f)) return no("eps must be positive");
+  // every operand the MFMA streams is read 16 bytes per lane
+  if (!aligned16(emb) || !aligned16(out) || (y && !aligned16(y)))
+    return no("emb, out and y must be 16-byte aligned");
+  for (int64_t i = 0; i < n_layers; ++i) {
+    const rb_session_layer& L = layers[i];
+    if (!L.w_in || !L.w_gate || !L.b_gate || !L.lam || !L.w_out || !L.ln_w || !L.ln_b || !L.h)
+      return no("null pointer in a layer");
+    if (use_conv && (!L.conv_w || !L.conv_b || (K > 1 && !L.conv_state)))
+      return no("null conv pointer in a layer");
+    if (use_ffn && (!L.w1 || !L.b1 || !L.w2 || !L.b2 || !L.ffn_ln_w || !L.ffn_ln_b))
+      return no("null ffn pointer in a layer");
+    if (!aligned16(L.w_in) || !aligned16(L.w_gate) || !aligned16(L.w_out) ||
+        (use_ffn && (!aligned16(L.w1) || !aligned16(L.w2))))
+      return no("weight matrices must be 16-byte aligned");
+  }
+  return 0;
+}
+
 RB_EXPORT int rb_session_step(const rb_session_layer* layers, int64_t n_layers, const float* emb,
                     const float* ln_w, const float* ln_b, float eps, const int64_t* items,
                     const int64_t* slots, int64_t* count, float* out, float* y,
                     int32_t* status, int64_t B, int64_t N, int64_t V, int64_t d, int64_t H,
                     int64_t K, int disable_conv1d, int disable_ffn, void* stream) {
-  if (!layers || !emb || !ln_w || !ln_b || !items || !count || !out)
-    return fail("rb_session_step: null pointer");
-  if (n_layers < 1 || n_layers > RB_SESSION_MAX_LAYERS)
-    return fail("rb_session_step: n_layers must be in [1, 8]");
-  if (K < 1 || K > 8) return fail("rb_session_step: conv kernel size K must be in [1, 8]");
-  if (d <= 0 || H <= 0 || d % 16 || H % 16 || d > (1 << 20) || H > (1 << 20))
-    return fail("rb_session_step: d and H must be positive multiples of 16");
-  if (B <= 0 || N <= 0 || V <= 0) return fail("rb_session_step: B, N and V must be positive");
-  if (B >= (1LL << 31) || N >= (1LL << 31) || V >= (1LL << 31))
-    return fail("rb_session_step: B, N and V must be < 2^31");
-  if (session_lds_bytes(d, H) > RB_SESSION_MAX_LDS)
-    return fail("rb_session_step: shape needs more LDS than a compute unit has (160 KiB)");
-  if (!(eps > 0.0f)) return fail("rb_session_step: eps must be positive");
   const bool use_conv = !disable_conv1d, use_ffn = !disable_ffn;
-  // every operand the MFMA streams is read 16 bytes per lane
-  if (!aligned16(emb) || !aligned16(out) || (y && !aligned16(y)))
-    return fail("rb_session_step: emb, out and y must be 16-byte aligned");
-  for (int64_t i = 0; i < n_layers; ++i) {
-    const rb_session_layer& L = layers[i];
-    if (!L.w_in || !L.w_gate || !L.b_gate || !L.lam || !L.w_out || !L.ln_w || !L.ln_b || !L.h)
-      return fail("rb_session_step: null pointer in a layer");
-    if (use_conv && (!L.conv_w || !L.conv_b || (K > 1 && !L.conv_state)))
-      return fail("rb_session_step: null conv pointer in a layer");
-    if (use_ffn && (!L.w1 || !L.b1 || !L.w2 || !L.b2 || !L.ffn_ln_w || !L.ffn_ln_b))
-      return fail("rb_session_step: null ffn pointer in a layer");
-    if (!aligned16(L.w_in) || !aligned16(L.w_gate) || !aligned16(L.w_out) ||
-        (use_ffn && (!aligned16(L.w1) || !aligned16(L.w2))))
-      return fail("rb_session_step: weight matrices must be 16-byte aligned");
-  }
+  if (int rc = check_encoder_args("rb_session_step: ", layers, n_layers, emb, ln_w, ln_b, eps,
+                                  items, count, out, y, B, N, V, d, H, K, use_conv, use_ffn))
+    return rc;
   return launch_session_step(layers, (int)n_layers, emb, ln_w, ln_b, eps, items, slots, count,
                              out, y, status, B, N, V, (int)d, (int)H, (int)K, use_conv, use_ffn,
                              reinterpret_cast<hipStream_t>(stream));
+}
+
+RB_EXPORT int rb_session_append(const rb_session_layer* layers, int64_t n_layers, const float* emb,
+                      const float* ln_w, const float* ln_b, float eps, const int64_t* items,
+                      const int64_t* slots, int64_t* count, float* out, float* y, float* y_all,
+                      int32_t* status, int64_t B, int64_t T, int64_t N, int64_t V, int64_t d,
+                      int64_t H, int64_t K, int disable_conv1d, int disable_ffn, void* stream) {
+  const bool use_conv = !disable_conv1d, use_ffn = !disable_ffn;
+  if (int rc = check_encoder_args("rb_session_append: ", layers, n_layers, emb, ln_w, ln_b, eps,
+                                  items, count, out, y, B, N, V, d, H, K, use_conv, use_ffn))
+    return rc;
+  if (T != 1 && T != 2 && T != 4 && T != 8 && T != 16)
+    return fail("rb_session_append: T must be 1, 2, 4, 8 or 16");
+  if (y_all && !aligned16(y_all))
+    return fail("rb_session_append: y_all must be 16-byte aligned");
+  return launch_session_append(layers, (int)n_layers, emb, ln_w, ln_b, eps, items, slots, count,
+                               out, y, y_all, status, B, (int)T, N, V, (int)d, (int)H, (int)K,
+                               use_conv, use_ffn, reinterpret_cast<hipStream_t>(stream));
 }
 
 RB_EXPORT int rb_session_capture(const float* u, int64_t u_rs, const float* xc, int64_t xc_rs,

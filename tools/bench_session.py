@@ -14,8 +14,14 @@ are prefilled with the L items and their rows compared with forward's.
 A second leg times opening the B sessions from their histories:
 session_prefill(method="steps"), L step launches, against
 session_prefill(method="forward"), one packed forward plus one capture launch
-per layer; same windows, alternating, with the largest deviation of the two
-states' h, conv history and out (prefill_rows).
+per layer, and session_append(reset=True), ceil(L / 16) append launches; same
+windows, alternating, with the largest deviation of the forward-built state's
+h, conv history and out from the step-built one and whether the append-built
+one equals it bitwise (prefill_rows).
+
+A third leg times 16 new events per live session: one session_append call
+(one launch) against 16 session_step calls, the only way without it
+(append_rows).
 
 Prints one JSON line; --out also writes it to a file."""
 from __future__ import annotations
@@ -53,29 +59,76 @@ def prefill_leg(model, B: int, seq, lens, windows: int) -> dict:
     step per column (method="steps", the default) against one packed forward
     plus a capture launch per layer (method="forward"), alternating window by
     window; and how far the two states are apart."""
-    by_steps, by_fwd = model.session_open(B), model.session_open(B)
+    by_steps, by_fwd, by_app = (model.session_open(B) for _ in range(3))
     steps = lambda: model.session_prefill(by_steps, seq, lens)                    # noqa: E731
     fwd = lambda: model.session_prefill(by_fwd, seq, lens, method="forward")      # noqa: E731
+    app = lambda: model.session_append(by_app, seq, lens, reset=True)             # noqa: E731
     steps_calls = 2                       # 2 x 200 step launches, as the step leg's window
     fwd_calls = 20 if B <= 64 else 5      # as the forward leg's window
+    app_calls = 20 if B <= 64 else 5      # 13 append launches a call
     for _ in range(2):
         window_ms(steps, steps_calls)
         window_ms(fwd, fwd_calls)
-    ts, tf = [], []
+        window_ms(app, app_calls)
+    ts, tf, ta = [], [], []
     for _ in range(windows):
         ts.append(window_ms(steps, steps_calls))
         tf.append(window_ms(fwd, fwd_calls))
-    s, f = statistics.median(ts), statistics.median(tf)
+        ta.append(window_ms(app, app_calls))
+    s, f, a = statistics.median(ts), statistics.median(tf), statistics.median(ta)
     dev = lambda a, b: max((x - y).abs().max().item() for x, y in zip(a, b))     # noqa: E731
     return dict(B=B, steps_ms=round(s, 4), steps_ms_min=round(min(ts), 4),
                 steps_ms_max=round(max(ts), 4), forward_ms=round(f, 4),
                 forward_ms_min=round(min(tf), 4), forward_ms_max=round(max(tf), 4),
-                steps_over_forward=round(s / f, 1),
+                append_ms=round(a, 4), append_ms_min=round(min(ta), 4),
+                append_ms_max=round(max(ta), 4),
+                steps_over_forward=round(s / f, 1), steps_over_append=round(s / a, 2),
+                append_over_forward=round(a / f, 2),
+                append_equals_steps=bool(same_state(by_app, by_steps)),
                 h_max_abs_dev=dev(by_fwd.h, by_steps.h),
                 conv_max_abs_dev=dev(by_fwd.conv, by_steps.conv),
                 out_max_abs_dev=dev([by_fwd.out], [by_steps.out]),
                 h_max_abs=max(h.abs().max().item() for h in by_steps.h),
                 count_equal=bool(torch.equal(by_fwd.count, by_steps.count)))
+
+
+def same_state(a, b) -> bool:
+    return all(torch.equal(x, y) for x, y in zip([*a.h, *a.conv, a.count, a.out],
+                                                 [*b.h, *b.conv, b.count, b.out]))
+
+
+def append_leg(model, B: int, seq, lens, g, windows: int) -> dict:
+    """16 new events for each of B live sessions (opened from their L-item
+    histories): one session_append call against 16 session_step calls,
+    alternating window by window."""
+    by_step, by_app = model.session_open(B), model.session_open(B)
+    for st in (by_step, by_app):
+        model.session_append(st, seq, lens, reset=True)
+    events = torch.randint(1, N_ITEMS, (B, 16), generator=g).to(seq.device)
+    cols = events.t().contiguous()
+
+    def step16():
+        for t in range(16):
+            model.session_step(by_step, cols[t])
+
+    app16 = lambda: model.session_append(by_app, events)                          # noqa: E731
+    step16()
+    app16()
+    equal = same_state(by_app, by_step)
+    step_calls = 12 if B <= 64 else 4     # 16 step launches a call
+    app_calls = 100 if B <= 64 else 10
+    for _ in range(2):
+        window_ms(step16, step_calls)
+        window_ms(app16, app_calls)
+    ts, ta = [], []
+    for _ in range(windows):
+        ts.append(window_ms(step16, step_calls))
+        ta.append(window_ms(app16, app_calls))
+    s, a = statistics.median(ts), statistics.median(ta)
+    return dict(B=B, events=16, steps16_ms=round(s, 4), steps16_ms_min=round(min(ts), 4),
+                steps16_ms_max=round(max(ts), 4), append_ms=round(a, 4),
+                append_ms_min=round(min(ta), 4), append_ms_max=round(max(ta), 4),
+                steps16_over_append=round(s / a, 2), append_equals_steps=bool(equal))
 
 
 def main() -> None:
@@ -92,7 +145,7 @@ def main() -> None:
                MAX_ITEM_LIST_LENGTH=L)
     torch.manual_seed(2020)
     model = RecBLR(cfg, SyntheticDataset(N_ITEMS)).to(dev).eval()
-    rows, prefill_rows = [], []
+    rows, prefill_rows, append_rows = [], [], []
     with torch.no_grad():
         for B in args.batches:
             g = torch.Generator().manual_seed(B)
@@ -123,8 +176,10 @@ def main() -> None:
                              forward_over_step=round(f / s, 1),
                              prefill_vs_forward_max_abs_err=err))
             prefill_rows.append(prefill_leg(model, B, seq, lens, args.windows))
+            append_rows.append(append_leg(model, B, seq, lens, g, args.windows))
     line = json.dumps(dict(bench="session_step", d=128, layers=2, K=4, L=L, n_items=N_ITEMS,
-                           windows=args.windows, rows=rows, prefill_rows=prefill_rows))
+                           windows=args.windows, rows=rows, prefill_rows=prefill_rows,
+                           append_rows=append_rows))
     print(line)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
