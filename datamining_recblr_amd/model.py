@@ -464,13 +464,16 @@ class RecBLR(SequentialRecommender):
                          exclude=item_seq if exclude_seen else None)
 
     # ---- stateful session inference (session.py) ----------------------------
-    def session_open(self, capacity: int, seq_len: int | None = None):
+    def session_open(self, capacity: int, seq_len: int | None = None, history: int = 0):
         """A session.SessionState of `capacity` slots for the window seq_len
         (default max_seq_length): after t <= seq_len appended items a slot's
-        output equals forward() on the right-padded row of those items."""
+        output equals forward() on the right-padded row of those items.
+        history = S > 0: the slots also remember their last S item ids on the
+        device (state.items, state.history(); session_recommend's seen-item
+        lists)."""
         from .session import SessionState
 
-        return SessionState(self, capacity, seq_len)
+        return SessionState(self, capacity, seq_len, history)
 
     def session_step(self, state, items, slots=None):
         """Append one item per row (0 = no event) and return the rows'
@@ -496,3 +499,12 @@ class RecBLR(SequentialRecommender):
         from .session import prefill
 
         return prefill(self, state, item_seq, item_seq_len, slots, reset, method)
+
+    def session_recommend(self, state, items=None, slots=None, k: int = 10,
+                          exclude_seen: bool = True, first_item: int = 1):
+        """(ids, scores) [B, k]: the rows' k best items after one step (items
+        [B]) or append (items [B, W]), or from the slots' stored outputs (items
+        None), the slots' own last S item ids excluded (session.recommend)."""
+        from .session import recommend
+
+        return recommend(self, state, items, slots, k, exclude_seen, first_item)

@@ -44,6 +44,14 @@ workgroup's 16 MFMA rows are T consecutive events of 16 / T slots), bitwise
 what a ``step`` per column leaves, appendable to a live slot, and with
 ``reset=True`` a third way to open sessions from histories.
 ``append_reference`` is its restatement as a column loop of ``step_reference``.
+
+A state opened with ``history=S`` also remembers, on the device, the last S
+item ids each slot consumed (``SessionState.items [N, S]``, a ring positioned
+by ``count``; rb_session_record, session/session_record.hip: one small launch
+per call, before the encoder launches).  ``state.history()`` reads it oldest
+first, and ``recommend`` is the serving call it is for: a step or an append,
+then ``scoring.top_items`` with the slots' rings as the seen-item lists.
+``record_reference`` is that kernel's restatement in torch ops.
 """
 from __future__ import annotations
 
@@ -58,8 +66,8 @@ from ._lib import RecBLRNativeError
 from .recurrence import pad_prefix_state, pow2_pad_len
 
 __all__ = ["SessionState", "EncoderParams", "step", "step_reference", "prefill",
-           "capture_reference", "append", "append_reference", "kernel_supports", "STEPPED",
-           "NO_EVENT", "BAD_ITEM", "BAD_SLOT"]
+           "capture_reference", "append", "append_reference", "record_reference", "recommend",
+           "kernel_supports", "STEPPED", "NO_EVENT", "BAD_ITEM", "BAD_SLOT"]
 
 _header = _lib._read(os.path.join(_lib._HERE, "session", "recblr_session.h"))
 STEPPED = _lib._define(_header, "RB_SESSION_STEPPED")
@@ -147,12 +155,19 @@ class SessionState:
     """The carried state of ``capacity`` session slots of one model, for the
     window ``seq_len`` (see the module doc).  ``h[i] [N, H]``, ``conv[i]
     [N, K-1, H]`` (None without a conv history), ``count [N]`` int64,
-    ``out [N, d]``, ``h0[i] [H]``; ``status``: the last call's row statuses."""
+    ``out [N, d]``, ``h0[i] [H]``; ``status``: the last call's row statuses.
+    ``history = S > 0`` adds ``items [N, S]`` int64, the ring of the last S item
+    ids each slot consumed: event e of a slot since its reset (e from 0) at
+    ``items[slot, e % S]``, -1 where nothing was written; ``count`` is its only
+    position.  ``history = 0`` (the default): no ring, ``items is None``."""
 
-    def __init__(self, model_or_params, capacity: int, seq_len: int | None = None):
+    def __init__(self, model_or_params, capacity: int, seq_len: int | None = None,
+                 history: int = 0):
         p = _params(model_or_params)
         if capacity <= 0:
             raise ValueError("SessionState: capacity must be positive")
+        if history < 0:
+            raise ValueError("SessionState: history must be >= 0 (0: no item ring)")
         if seq_len is None:
             seq_len = getattr(model_or_params, "max_seq_length", None)
         if seq_len is None or seq_len <= 0:
@@ -170,6 +185,8 @@ class SessionState:
         self.count = torch.empty((N,), device=p.device, dtype=torch.int64)
         self.out = torch.empty((N, p.d), **kw)
         self.status = torch.zeros((0,), device=p.device, dtype=torch.int32)
+        self.items = (torch.empty((N, int(history)), device=p.device, dtype=torch.int64)
+                      if history else None)
         self._plan = None
         self.reset()
 
@@ -196,6 +213,29 @@ class SessionState:
                 conv[idx] = 0.0
         self.count[idx] = 0
         self.out[idx] = 0.0
+        if self.items is not None:
+            self.items[idx] = -1
+
+    @torch.no_grad()
+    def history(self, slots=None):
+        """The slots' recorded item ids (all slots by default), oldest first:
+        ``(ids [n, S] int64, n_valid [n] int64)``, row i holding the slot's last
+        ``n_valid[i] = min(count, S)`` events and -1 to the right of them.
+        Torch ops on the state's device, no host sync."""
+        if self.items is None:
+            raise ValueError("SessionState.history: the state was opened without an item ring "
+                             "(history=0)")
+        S = self.items.shape[1]
+        ring, count = self.items, self.count
+        if slots is not None:
+            idx = _slot_tensor(slots, self)
+            ring, count = ring[idx], count[idx]
+        n_valid = count.clamp(0, S)
+        # a full ring starts at its oldest entry, count % S; a partial one at 0
+        start = torch.where(count >= S, count % S, torch.zeros_like(count))
+        col = torch.arange(S, device=self.device)[None]
+        ids = ring.gather(1, (start[:, None] + col) % S)
+        return torch.where(col < n_valid[:, None], ids, torch.full_like(ids, -1)), n_valid
 
 
 def _slot_tensor(slots, state: SessionState) -> torch.Tensor:
@@ -241,12 +281,98 @@ def _ln(p: EncoderParams, prefix: str, x):
 
 
 @torch.no_grad()
-def step_reference(model_or_params, state: SessionState, items, slots=None) -> torch.Tensor:
-    """``step`` in plain torch ops (RecBLR.py:75-84 / :140-145 / :170-207 /
-    :218-227 at one position), on the state's device."""
-    p = _params(model_or_params)
+def record_reference(state: SessionState, items, slots=None, want_seen: bool = False):
+    """rb_session_record in plain torch ops, on the state's device: write the
+    events the encoder is about to consume into the state's item ring, and
+    with want_seen return ``seen [B, S]``, the rows' rings as they stand
+    afterwards (all -1 for a slot outside the state).  Call it before the
+    encoder advances ``state.count``.
+
+    items: int64 [B, W] right-padded with 0 (or [B]: W = 1), W >= 0; slots: int64
+    [B], unique (None: slot b); a slot outside [0, N) is masked, not refused.
+    The rule is the encoder kernels' masking, per row: cut the row into chunks
+    of 16 columns (``TILE``); a chunk's events are its entries before its first
+    0; a chunk with an event outside [0, V) contributes nothing; a bad slot
+    records nothing.  Event j of the row's n recorded events goes to
+    ``items[slot, (count[slot] + j) % S]``; when n > S only the last S are
+    written."""
+    ring = state.items
+    if ring is None:
+        raise ValueError("record_reference: the state was opened without an item ring "
+                         "(history=0)")
+    dev, (N, S), V = state.device, ring.shape, state.shape[0]
+    items = torch.as_tensor(items, dtype=torch.int64).to(dev)
+    if items.dim() == 1:
+        items = items[:, None]
+    if items.dim() != 2 or items.shape[0] == 0:
+        raise ValueError("items must be [B, W] (or [B]) with at least one row")
+    B, W = items.shape
+    if slots is None:
+        if B > N:
+            raise ValueError(f"{B} rows for a state of {N} slots")
+        slots = torch.arange(B, device=dev)
+    else:
+        slots = torch.as_tensor(slots, dtype=torch.int64).reshape(-1).to(dev)
+        if slots.numel() != B:
+            raise ValueError("items and slots must have the same number of rows")
+    slot_ok = (slots >= 0) & (slots < N)
+    safe = slots.clamp(0, N - 1)
+    nc = -(-W // TILE)
+    chunks = F.pad(items, (0, nc * TILE - W)).reshape(B, nc, TILE)
+    live = (chunks != 0).cumprod(-1).bool()
+    bad = (live & ((chunks < 0) | (chunks >= V))).any(-1, keepdim=True)
+    event = (live & ~bad & slot_ok[:, None, None]).reshape(B, nc * TILE)
+    j = event.cumsum(1) - 1                                   # the event's number in its row
+    keep = event & (j >= event.sum(1, keepdim=True) - S)      # the last S events
+    pos = (state.count[safe][:, None] + j) % S
+    # kept positions are distinct within a row; everything else lands in a
+    # spare column S that is cut off again
+    rows = torch.cat([ring[safe], ring.new_zeros((B, 1))], 1)
+    rows.scatter_(1, torch.where(keep, pos, torch.full_like(pos, S)),
+                  chunks.reshape(B, nc * TILE))
+    rows = rows[:, :S]
+    ring[slots[slot_ok]] = rows[slot_ok]
+    if not want_seen:
+        return None
+    return torch.where(slot_ok[:, None], rows, torch.full_like(rows, -1))
+
+
+def _record_kernel(state: SessionState, items, slots, seen) -> None:
+    """One launch (rb_session_record): items [B, W] int64, contiguous."""
+    B, W = items.shape
+    N, S = state.items.shape
+    _lib.call_session(
+        "rb_session_record", items.data_ptr() if W else None, B, W,
+        slots.data_ptr() if slots is not None else None, state.count.data_ptr(),
+        state.items.data_ptr(), seen.data_ptr() if seen is not None else None, N, S,
+        state.shape[0], kernels._stream(state.items))
+
+
+def _record(state: SessionState, items, slots, want_seen: bool = False):
+    """Record a call's [B, W] items on a GPU state before its encoder launches
+    (they advance count): one rb_session_record launch; returns seen [B, S] or
+    None.  Nothing at all for a state without a ring."""
+    if state.items is None:
+        return None
+    B, W = items.shape
+    if W == 0 and not want_seen:
+        return None
+    seen = (torch.empty((B, state.items.shape[1]), device=state.device, dtype=torch.int64)
+            if want_seen else None)
+    with torch.cuda.device(state.device):
+        _record_kernel(state, items.contiguous(), slots, seen)
+    return seen
+
+
+def _step_reference(p: EncoderParams, state: SessionState, items, slots, record: bool = True,
+                    want_seen: bool = False):
+    """step_reference's body: (y, seen).  record=False: the caller has
+    recorded the call's items already (append_reference's column loop)."""
     _match(p, state)
     items, slots, B = _rows(state, items, slots)
+    seen = None
+    if record and state.items is not None:
+        seen = record_reference(state, items, slots, want_seen)
     if slots is None:
         slots = torch.arange(B, device=state.device)
     slot_ok = (slots >= 0) & (slots < state.capacity)
@@ -288,7 +414,15 @@ def step_reference(model_or_params, state: SessionState, items, slots=None) -> t
         state.count[idx] += 1
     y = state.out[slots.clamp(0, state.capacity - 1)]
     y[~slot_ok] = 0.0
-    return y
+    return y, seen
+
+
+@torch.no_grad()
+def step_reference(model_or_params, state: SessionState, items, slots=None) -> torch.Tensor:
+    """``step`` in plain torch ops (RecBLR.py:75-84 / :140-145 / :170-207 /
+    :218-227 at one position), on the state's device; a state with an item
+    ring records through record_reference."""
+    return _step_reference(_params(model_or_params), state, items, slots)[0]
 
 
 def _refuse_training(model) -> None:
@@ -368,19 +502,26 @@ def step(model, state: SessionState, items, slots=None) -> torch.Tensor:
     [B], list or tensor; 0 = no event for that row.  slots must be unique: a
     list or CPU tensor is checked, for a device tensor it is a precondition
     (no sync on the hot path).  A shape the kernel refuses (kernel_supports)
-    runs step_reference instead."""
+    runs step_reference instead.  A state with an item ring records the items
+    first (one rb_session_record launch)."""
+    return _step(model, state, items, slots)[0]
+
+
+def _step(model, state: SessionState, items, slots, want_seen: bool = False):
+    """step's body: (y, seen [B, S] or None)."""
     p = _params(model)
     _refuse(model, p, state)
     _match(p, state)
     if not kernel_supports(p.d, p.H, p.K, p.num_layers):
-        return step_reference(p, state, items, slots)
+        return _step_reference(p, state, items, slots, want_seen=want_seen)
     items, slots, B = _rows(state, items, slots)
+    seen = _record(state, items[:, None], slots, want_seen)
     y = torch.empty((B, p.d), device=state.device, dtype=torch.float32)
     status = torch.empty((B,), device=state.device, dtype=torch.int32)
     with torch.cuda.device(state.device):
         _step_kernel(p, state, _plan(p, state), items, slots, y, status)
     state.status = status
-    return y
+    return y, seen
 
 
 def _append_rows(state: SessionState, item_seq, item_seq_len, slots):
@@ -440,12 +581,22 @@ def append_reference(model_or_params, state: SessionState, item_seq, item_seq_le
     device: the checked restatement of rb_session_append, one 16-column chunk
     after the other.  Within a chunk a row's events are the entries before its
     first 0; a row with an event outside [0, V) among them is masked for the
-    whole chunk (BAD_ITEM: nothing of its slot is touched)."""
-    p = _params(model_or_params)
+    whole chunk (BAD_ITEM: nothing of its slot is touched).  A state with an
+    item ring records the whole [B, W'] once, through record_reference."""
+    return _append_reference(_params(model_or_params), state, item_seq, item_seq_len, slots,
+                             reset, return_all)[0]
+
+
+def _append_reference(p: EncoderParams, state: SessionState, item_seq, item_seq_len, slots,
+                      reset: bool, return_all: bool, want_seen: bool = False):
+    """append_reference's body: (its result, seen [B, S] or None)."""
     _match(p, state)
     items, slots, B, W = _append_rows(state, item_seq, item_seq_len, slots)
     if reset:
         state.reset(slots if slots is not None else torch.arange(B))
+    seen = None
+    if state.items is not None and (W or want_seen):
+        seen = record_reference(state, items, slots, want_seen)
     y, status, cols = _stored_rows(state, slots, B), None, []
     for c0 in range(0, W, TILE):
         chunk = items[:, c0:c0 + TILE]
@@ -454,7 +605,7 @@ def append_reference(model_or_params, state: SessionState, item_seq, item_seq_le
         fed = torch.where(live & ~bad[:, None], chunk, torch.zeros_like(chunk))
         st = torch.full((B,), NO_EVENT, device=state.device, dtype=torch.int32)
         for t in range(chunk.shape[1]):
-            y = step_reference(p, state, fed[:, t], slots)
+            y = _step_reference(p, state, fed[:, t], slots, record=False)[0]
             if t == 0:
                 st = state.status.clone()          # STEPPED, NO_EVENT or BAD_SLOT
             cols.append(torch.where((fed[:, t] != 0)[:, None] & (state.status == STEPPED)[:, None],
@@ -467,9 +618,9 @@ def append_reference(model_or_params, state: SessionState, item_seq, item_seq_le
             status[(slots < 0) | (slots >= state.capacity)] = BAD_SLOT
     state.status = status
     if not return_all:
-        return y
+        return y, seen
     y_all = torch.stack(cols, 1) if cols else y.new_zeros((B, 0, p.d))
-    return y, y_all
+    return (y, y_all), seen
 
 
 def _append_kernel(p: EncoderParams, state: SessionState, layers, items, slots, y, y_all,
@@ -511,18 +662,29 @@ def append(model, state: SessionState, item_seq, item_seq_len=None, slots=None,
     the events of the chunks before it: a launch is atomic per row, the call
     is not.  slots, the refusals and the fallback are ``step``'s: a shape the
     kernel refuses (kernel_supports) or a state on the CPU runs
-    append_reference."""
+    append_reference.  A state with an item ring records the whole [B, W']
+    first: one rb_session_record launch per call, after the reset and before
+    the first encoder launch."""
+    return _append(model, state, item_seq, item_seq_len, slots, reset, return_all)[0]
+
+
+def _append(model, state: SessionState, item_seq, item_seq_len, slots, reset: bool,
+            return_all: bool, want_seen: bool = False):
+    """append's body: (its result, seen [B, S] or None)."""
     p = _params(model)
     _refuse_training(model)
     if state.device.type != "cuda":
-        return append_reference(p, state, item_seq, item_seq_len, slots, reset, return_all)
+        return _append_reference(p, state, item_seq, item_seq_len, slots, reset, return_all,
+                                 want_seen)
     _refuse(model, p, state)
     _match(p, state)
     if not kernel_supports(p.d, p.H, p.K, p.num_layers):
-        return append_reference(p, state, item_seq, item_seq_len, slots, reset, return_all)
+        return _append_reference(p, state, item_seq, item_seq_len, slots, reset, return_all,
+                                 want_seen)
     items, slots, B, W = _append_rows(state, item_seq, item_seq_len, slots)
     if reset:
         state.reset(slots if slots is not None else torch.arange(B))
+    seen = _record(state, items, slots, want_seen)
     kw = dict(device=state.device, dtype=torch.float32)
     y, status, cols = (torch.empty((B, p.d), **kw) if W else None), None, []
     with torch.cuda.device(state.device):
@@ -544,8 +706,8 @@ def append(model, state: SessionState, item_seq, item_seq_len=None, slots=None,
             status[(slots < 0) | (slots >= state.capacity)] = BAD_SLOT
     state.status = status
     if not return_all:
-        return y
-    return y, (torch.cat(cols, 1) if cols else y.new_zeros((B, 0, p.d)))
+        return y, seen
+    return (y, (torch.cat(cols, 1) if cols else y.new_zeros((B, 0, p.d)))), seen
 
 
 @torch.no_grad()
@@ -666,6 +828,9 @@ def _prefill_forward(model, state: SessionState, item_seq, item_seq_len, slots, 
     seq = (seq[:, :L] if T >= L else F.pad(seq, (0, L - T))).clamp(0, p.V - 1).contiguous()
     lens = attach_host_lengths(lens_h.to(dev), lens_h)
     K = p.K if p.use_conv else 1
+    if state.items is not None:     # the rows the forward consumes, before count moves
+        _record(state, torch.where(torch.arange(L, device=dev)[None] < lens[:, None], seq,
+                                   torch.zeros_like(seq)), slots)
     packed_slots = []
 
     def sink(i, packed, u, xc, rg, carries):
@@ -742,3 +907,71 @@ def prefill(model, state: SessionState, item_seq, item_seq_len, slots=None,
     if y is None:
         y = state.out[slots if slots is not None else slice(0, B)].clone()
     return y
+
+
+@torch.no_grad()
+def recommend(model, state: SessionState, items=None, slots=None, k: int = 10,
+              exclude_seen: bool = True, first_item: int = 1):
+    """Click in, recommendation list out: ``(ids int64 [B, k], scores fp32
+    [B, k])``, each row's k best items by ``scoring.top_items`` for its slot's
+    seq_output after the call's events.
+
+    items None: no event, the slots' stored ``out`` rows (slots None: every
+    slot of the state).  items [B]: one ``step`` first; items [B, W]: one
+    ``append`` first (right-padded with 0).  With exclude_seen the slot's item
+    ring as it stands after those events (its last S item ids, ``history=S``) is
+    the seen-item list: the record launch of the step or append writes the
+    [B, S] rows ``top_items`` excludes, so nothing is gathered or copied from
+    the host.  A state opened without a ring cannot exclude: ValueError.
+
+    A row whose slot lies outside the state, or whose slot has consumed no
+    event yet (count == 0: its ``out`` is the zero row), returns id -1 and score
+    -inf in every position (masked on the device, no sync).  slots, the
+    refusals and the fallbacks are ``step``'s; a state on the CPU runs the
+    whole call in torch ops.  ``state.status`` is left as the step or append
+    left it."""
+    from .scoring import top_items
+
+    if exclude_seen and state.items is None:
+        raise ValueError("recommend(exclude_seen=True) needs the slots' item ring: open the "
+                         "state with history=S (session_open(capacity, history=S)), or pass "
+                         "exclude_seen=False")
+    p = _params(model)
+    on_gpu = state.device.type == "cuda"
+    if items is None:
+        _refuse_training(model)
+        if on_gpu:
+            _refuse(model, p, state)
+        _match(p, state)
+        if slots is not None:
+            slots = _slot_tensor(slots, state)
+        B = state.capacity if slots is None else slots.numel()
+        if B == 0:
+            raise ValueError("slots must name at least one row")
+        y, seen = _stored_rows(state, slots, B), None
+        if exclude_seen:
+            none = torch.empty((B, 0), device=state.device, dtype=torch.int64)
+            seen = (_record(state, none, slots, True) if on_gpu
+                    else record_reference(state, none, slots, True))
+    else:
+        items = torch.as_tensor(items, dtype=torch.int64)
+        if items.dim() == 1 and on_gpu:
+            y, seen = _step(model, state, items, slots, exclude_seen)
+        elif items.dim() == 1:
+            _refuse_training(model)
+            y, seen = _step_reference(p, state, items, slots, want_seen=exclude_seen)
+        else:
+            y, seen = _append(model, state, items, None, slots, False, False, exclude_seen)
+        B = y.shape[0]
+        if slots is not None:
+            slots = _slot_tensor(slots, state)
+    if slots is None:
+        dead = state.count[:B] == 0
+    else:
+        dead = ((slots < 0) | (slots >= state.capacity)
+                | (state.count[slots.clamp(0, state.capacity - 1)] == 0))
+    ids, scores = top_items(y, p.t["item_embedding.weight"], k, first_item,
+                            exclude=seen if exclude_seen else None)
+    ids.masked_fill_(dead[:, None], -1)
+    scores.masked_fill_(dead[:, None], float("-inf"))
+    return ids, scores

@@ -3,7 +3,8 @@
  * rb_session_step advances the whole RecBLR encoder by one event per session
  * slot in one launch, rb_session_append by up to 16 consecutive events per
  * slot; rb_session_capture reads a layer's session state off its forward
- * over stored histories (python: datamining_recblr_amd/session.py).  Its own
+ * over stored histories; rb_session_record keeps the ring of the last item
+ * ids a slot consumed (python: datamining_recblr_amd/session.py).  Its own
  * library, beside the product library, as the probe and experimental
  * libraries are ("Stateful sessions").  Same conventions as the
  * boundary (include/recblr_hip.h): raw device pointers, int status (0 = ok,
@@ -140,6 +141,39 @@ int rb_session_capture(const float* u, int64_t u_rs, const float* xc, int64_t xc
                        const float* carries, const int64_t* seq_offsets, const int64_t* slots,
                        float* h, float* conv_state, int64_t B, int64_t L, int64_t N, int64_t H,
                        int64_t K, void* stream);
+
+/* The item ring: ring [N, S] int64 holds per slot the last min(count, S) item
+ * ids the encoder kernels consumed, event e of a slot since its reset (e from
+ * 0: count before the event) at ring[slot, e % S]; entries never written hold
+ * what the caller initialised them to (python: -1).  The ring has no counter
+ * of its own: count [N] is read, never written, so this kernel MUST be
+ * launched on the same stream BEFORE the rb_session_step / rb_session_append
+ * launches that consume the same items (they advance count), once per call
+ * over the call's whole matrix.
+ * items [B, W] int64, row-major, right-padded with 0: the matrix whose
+ * RB_SESSION_TILE-column chunks the caller feeds to rb_session_append one
+ * launch each (W = 1: the items of one rb_session_step).  W may be 0 (items
+ * may then be NULL): nothing is recorded and only seen is written.  slots as
+ * for the step (unique; NULL = slot b).  What is recorded is the encoder
+ * kernels' own masking rule, restated per row from items, slots, N and V
+ * alone.  Cut the row into chunks of RB_SESSION_TILE columns; a chunk's
+ * events are its entries before its first 0; if any of them lies outside
+ * [0, V) the chunk contributes nothing (the launch's BAD_ITEM), otherwise its
+ * events are recorded in order; a slot outside [0, N) records nothing.  With
+ * the row's recorded events numbered j = 0 .. n - 1, event j goes to
+ * ring[slot, (count[slot] + j) % S]; when n > S only the last S are written,
+ * and every ring entry is written at most once per launch (two passes over
+ * the row: count, then write), so no result rests on the order of two stores.
+ * seen [B, S] (optional): row b receives the slot's ring as it stands after
+ * this call's events, in ring order, built from the old ring values and the
+ * call's events (the launch's own stores are not read back); all -1 for a
+ * slot outside [0, N).  It is the exclusion list rb_item_topk takes.
+ * Every id and slot is range-checked before an address is formed from it.
+ * One wave per call row; no atomics, LDS or scratch.  B, N, S, V >= 1,
+ * W >= 0, all < 2^31. */
+int rb_session_record(const int64_t* items, int64_t B, int64_t W, const int64_t* slots,
+                      const int64_t* count, int64_t* ring, int64_t* seen,
+                      int64_t N, int64_t S, int64_t V, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 // session_capi.hip — the extern "C" entry points of the session library
 // (recblr_session.h): argument checks, then the launchers in session_step.hip,
-// session_append.hip and session_capture.hip.
+// session_append.hip, session_capture.hip and session_record.hip.
 // Built with hidden visibility, so its error helpers (rb::fail,
 // rb::launch_status) are its own and never interpose the product library's.
 #include "../csrc/common.h"
@@ -44,6 +44,9 @@ int launch_session_capture(const float* u, int64_t u_rs, const float* xc, int64_
                            const float* carries, const int64_t* offs, const int64_t* slots,
                            float* h, float* conv_state, int64_t B, int L, int64_t N, int H, int K,
                            hipStream_t st);
+int launch_session_record(const int64_t* items, int64_t B, int64_t W, const int64_t* slots,
+                          const int64_t* count, int64_t* ring, int64_t* seen, int64_t N, int S,
+                          int64_t V, hipStream_t st);
 }  // namespace rb
 
 using namespace rb;
@@ -160,6 +163,20 @@ RB_EXPORT int rb_session_capture(const float* u, int64_t u_rs, const float* xc, 
   return launch_session_capture(u, u_rs, xc, xc_rs, rg, rg_rs, lam, gate_b, carries, seq_offsets,
                                 slots, h, conv_state, B, (int)L, N, (int)H, (int)K,
                                 reinterpret_cast<hipStream_t>(stream));
+}
+
+RB_EXPORT int rb_session_record(const int64_t* items, int64_t B, int64_t W, const int64_t* slots,
+                      const int64_t* count, int64_t* ring, int64_t* seen, int64_t N, int64_t S,
+                      int64_t V, void* stream) {
+  if (W < 0) return fail("rb_session_record: W must be >= 0");
+  if ((!items && W > 0) || !count || !ring) return fail("rb_session_record: null pointer");
+  if (B <= 0 || N <= 0 || S <= 0 || V <= 0)
+    return fail("rb_session_record: B, N, S and V must be positive");
+  if (B >= (1LL << 31) || N >= (1LL << 31) || S >= (1LL << 31) || V >= (1LL << 31) ||
+      W >= (1LL << 31))
+    return fail("rb_session_record: B, W, N, S and V must be < 2^31");
+  return launch_session_record(items, B, W, slots, count, ring, seen, N, (int)S, V,
+                               reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
