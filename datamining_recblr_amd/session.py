@@ -253,19 +253,86 @@ def _slot_tensor(slots, state: SessionState) -> torch.Tensor:
     return host.to(state.device)
 
 
-def _rows(state: SessionState, items, slots):
-    items = torch.as_tensor(items, dtype=torch.int64).reshape(-1).to(state.device).contiguous()
-    B = items.numel()
-    if B == 0:
-        raise ValueError("items must hold at least one row")
+def _host_lengths(lengths, sync: bool = False):
+    """The lengths as a host tensor, or None where they are known on the device
+    only.  attach_host_lengths' copy wins; a list or CPU tensor counts as host
+    lengths; a device tensor does not, unless sync (one device-to-host copy,
+    as forward() pays)."""
+    from .model import HOST_LENGTHS
+
+    host = getattr(lengths, HOST_LENGTHS, None)
+    if host is None and (sync or not (isinstance(lengths, torch.Tensor)
+                                      and lengths.device.type != "cpu")):
+        host = torch.as_tensor(lengths).to("cpu")
+    return host
+
+
+def _rows(state: SessionState, items, lengths=None, slots=None, name: str = "items",
+          check_slots: bool = True, empty_ok: bool = False):
+    """A call's rows on the state's device: ``(items [B, W'] int64, slots [B]
+    or None, B, W')``.  items: [B, W] or [B] (W = 1).  With lengths the columns
+    at or past a row's length are zeroed, and W' is cut to the longest row
+    where the lengths are known on the host (_host_lengths).  slots go through
+    _slot_tensor; check_slots=False only moves them (record_reference masks a
+    bad slot, it refuses none).  name: what the messages call items."""
+    items = torch.as_tensor(items, dtype=torch.int64)
+    if items.dim() == 1:
+        items = items[:, None]
+    if items.dim() != 2:
+        raise ValueError(f"{name} must be [B, W] (or [B]: one event per row)")
+    B, W = items.shape
+    if B == 0 and not empty_ok:
+        raise ValueError(f"{name} must hold at least one row")
+    items = items.to(state.device)
+    if lengths is not None:
+        host_len = _host_lengths(lengths)
+        lens = torch.as_tensor(lengths).to(state.device).reshape(-1, 1)
+        if lens.shape[0] != B:
+            raise ValueError(f"{name} and item_seq_len must have the same number of rows")
+        if host_len is not None:        # known on the host: stop at the longest row
+            W = min(W, max(int(host_len.max()), 0)) if B else 0
+        items = items[:, :W]
+        items = torch.where(torch.arange(W, device=state.device)[None] < lens, items,
+                            torch.zeros_like(items))
     if slots is None:
         if B > state.capacity:
             raise ValueError(f"{B} rows for a state of {state.capacity} slots")
     else:
-        slots = _slot_tensor(slots, state)
+        slots = (_slot_tensor(slots, state) if check_slots else
+                 torch.as_tensor(slots, dtype=torch.int64).reshape(-1).to(state.device))
         if slots.numel() != B:
-            raise ValueError("items and slots must have the same length")
-    return items, slots, B
+            raise ValueError(f"{name} and slots must have the same length")
+    return items.contiguous(), slots, B, W
+
+
+def _bad_slot(state: SessionState, slots) -> torch.Tensor:
+    return (slots < 0) | (slots >= state.capacity)
+
+
+def _stored_rows(state: SessionState, slots, B: int) -> torch.Tensor:
+    """The slots' stored out rows [B, d]; zeros for a slot outside the state."""
+    if slots is None:
+        return state.out[:B].clone()
+    y = state.out[slots.clamp(0, state.capacity - 1)]
+    y[_bad_slot(state, slots)] = 0.0
+    return y
+
+
+def _idle_status(state: SessionState, slots, B: int) -> torch.Tensor:
+    """The statuses of a call without a column: NO_EVENT, BAD_SLOT for a slot
+    outside the state."""
+    status = torch.full((B,), NO_EVENT, device=state.device, dtype=torch.int32)
+    if slots is not None:
+        status[_bad_slot(state, slots)] = BAD_SLOT
+    return status
+
+
+def _chunk_events(chunks, V: int):
+    """The encoder kernel's masking rule for chunks [..., <= 16] of item ids:
+    ``(live, bad)``.  live: the entries before a chunk's first 0, its events;
+    bad [..., 1]: one of them lies outside [0, V), which masks the chunk."""
+    live = (chunks != 0).cumprod(-1).bool()
+    return live, (live & ((chunks < 0) | (chunks >= V))).any(-1, keepdim=True)
 
 
 def _match(p: EncoderParams, state: SessionState) -> None:
@@ -300,27 +367,15 @@ def record_reference(state: SessionState, items, slots=None, want_seen: bool = F
     if ring is None:
         raise ValueError("record_reference: the state was opened without an item ring "
                          "(history=0)")
-    dev, (N, S), V = state.device, ring.shape, state.shape[0]
-    items = torch.as_tensor(items, dtype=torch.int64).to(dev)
-    if items.dim() == 1:
-        items = items[:, None]
-    if items.dim() != 2 or items.shape[0] == 0:
-        raise ValueError("items must be [B, W] (or [B]) with at least one row")
-    B, W = items.shape
+    (N, S), V = ring.shape, state.shape[0]
+    items, slots, B, W = _rows(state, items, None, slots, check_slots=False)
     if slots is None:
-        if B > N:
-            raise ValueError(f"{B} rows for a state of {N} slots")
-        slots = torch.arange(B, device=dev)
-    else:
-        slots = torch.as_tensor(slots, dtype=torch.int64).reshape(-1).to(dev)
-        if slots.numel() != B:
-            raise ValueError("items and slots must have the same number of rows")
-    slot_ok = (slots >= 0) & (slots < N)
+        slots = torch.arange(B, device=state.device)
+    slot_ok = ~_bad_slot(state, slots)
     safe = slots.clamp(0, N - 1)
     nc = -(-W // TILE)
     chunks = F.pad(items, (0, nc * TILE - W)).reshape(B, nc, TILE)
-    live = (chunks != 0).cumprod(-1).bool()
-    bad = (live & ((chunks < 0) | (chunks >= V))).any(-1, keepdim=True)
+    live, bad = _chunk_events(chunks, V)
     event = (live & ~bad & slot_ok[:, None, None]).reshape(B, nc * TILE)
     j = event.cumsum(1) - 1                                   # the event's number in its row
     keep = event & (j >= event.sum(1, keepdim=True) - S)      # the last S events
@@ -369,13 +424,13 @@ def _step_reference(p: EncoderParams, state: SessionState, items, slots, record:
     """step_reference's body: (y, seen).  record=False: the caller has
     recorded the call's items already (append_reference's column loop)."""
     _match(p, state)
-    items, slots, B = _rows(state, items, slots)
+    items, stored, B, _ = _rows(state, torch.as_tensor(items).reshape(-1), None, slots)
     seen = None
     if record and state.items is not None:
-        seen = record_reference(state, items, slots, want_seen)
-    if slots is None:
-        slots = torch.arange(B, device=state.device)
-    slot_ok = (slots >= 0) & (slots < state.capacity)
+        seen = record_reference(state, items, stored, want_seen)
+    items = items[:, 0]
+    slots = stored if stored is not None else torch.arange(B, device=state.device)
+    slot_ok = ~_bad_slot(state, slots)
     item_ok = (items >= 0) & (items < p.V)
     valid = slot_ok & item_ok & (items != 0)
     status = torch.full((B,), NO_EVENT, device=state.device, dtype=torch.int32)
@@ -412,9 +467,7 @@ def _step_reference(p: EncoderParams, state: SessionState, items, slots, record:
     if x is not None:
         state.out[idx] = x
         state.count[idx] += 1
-    y = state.out[slots.clamp(0, state.capacity - 1)]
-    y[~slot_ok] = 0.0
-    return y, seen
+    return _stored_rows(state, stored, B), seen
 
 
 @torch.no_grad()
@@ -483,16 +536,24 @@ def _plan(p: EncoderParams, state: SessionState):
     return arr
 
 
-def _step_kernel(p: EncoderParams, state: SessionState, layers, items, slots, y, status) -> None:
-    """The one launch (rb_session_step)."""
+def _encoder_args(p: EncoderParams, state: SessionState, layers, items, slots, y):
+    """The arguments rb_session_step and rb_session_append share: ``(head,
+    tail)``, layers .. y and N .. stream; between them stand the entry's own
+    ([y_all,] status, B [, T])."""
     t = p.t
-    _lib.call_session(
-        "rb_session_step", ctypes.addressof(layers), p.num_layers,
-        t["item_embedding.weight"].data_ptr(), t["layer_norm.weight"].data_ptr(),
-        t["layer_norm.bias"].data_ptr(), LN_EPS, items.data_ptr(),
-        slots.data_ptr() if slots is not None else None, state.count.data_ptr(),
-        state.out.data_ptr(), y.data_ptr(), status.data_ptr(), items.numel(), state.capacity,
-        p.V, p.d, p.H, p.K, int(not p.use_conv), int(not p.use_ffn), kernels._stream(y))
+    head = (ctypes.addressof(layers), p.num_layers, t["item_embedding.weight"].data_ptr(),
+            t["layer_norm.weight"].data_ptr(), t["layer_norm.bias"].data_ptr(), LN_EPS,
+            items.data_ptr(), slots.data_ptr() if slots is not None else None,
+            state.count.data_ptr(), state.out.data_ptr(), y.data_ptr())
+    tail = (state.capacity, p.V, p.d, p.H, p.K, int(not p.use_conv), int(not p.use_ffn),
+            kernels._stream(y))
+    return head, tail
+
+
+def _step_kernel(p: EncoderParams, state: SessionState, layers, items, slots, y, status) -> None:
+    """The one launch (rb_session_step): items [B] (or [B, 1]), one event per row."""
+    head, tail = _encoder_args(p, state, layers, items, slots, y)
+    _lib.call_session("rb_session_step", *head, status.data_ptr(), items.numel(), *tail)
 
 
 @torch.no_grad()
@@ -514,59 +575,14 @@ def _step(model, state: SessionState, items, slots, want_seen: bool = False):
     _match(p, state)
     if not kernel_supports(p.d, p.H, p.K, p.num_layers):
         return _step_reference(p, state, items, slots, want_seen=want_seen)
-    items, slots, B = _rows(state, items, slots)
-    seen = _record(state, items[:, None], slots, want_seen)
+    items, slots, B, _ = _rows(state, torch.as_tensor(items).reshape(-1), None, slots)
+    seen = _record(state, items, slots, want_seen)
     y = torch.empty((B, p.d), device=state.device, dtype=torch.float32)
     status = torch.empty((B,), device=state.device, dtype=torch.int32)
     with torch.cuda.device(state.device):
         _step_kernel(p, state, _plan(p, state), items, slots, y, status)
     state.status = status
     return y, seen
-
-
-def _append_rows(state: SessionState, item_seq, item_seq_len, slots):
-    """append's arguments on the state's device: items [B, W'] int64 with the
-    columns at or past a row's length zeroed, W' cut to the longest row where
-    the lengths are known on the host; slots (or None)."""
-    items = torch.as_tensor(item_seq, dtype=torch.int64)
-    if items.dim() == 1:
-        items = items[:, None]
-    if items.dim() != 2:
-        raise ValueError("item_seq must be [B, W] (or [B]: one event per row)")
-    B, W = items.shape
-    if B == 0:
-        raise ValueError("item_seq must hold at least one row")
-    items = items.to(state.device)
-    if item_seq_len is not None:
-        host_len = getattr(item_seq_len, "_recblr_host_lengths", None)
-        if host_len is None and not (isinstance(item_seq_len, torch.Tensor)
-                                     and item_seq_len.device.type != "cpu"):
-            host_len = torch.as_tensor(item_seq_len)
-        lens = torch.as_tensor(item_seq_len).to(state.device).reshape(-1, 1)
-        if lens.shape[0] != B:
-            raise ValueError("item_seq and item_seq_len must have the same number of rows")
-        if host_len is not None:        # known on the host: stop at the longest row
-            W = min(W, max(int(host_len.max()), 0))
-        items = items[:, :W]
-        items = torch.where(torch.arange(W, device=state.device)[None] < lens, items,
-                            torch.zeros_like(items))
-    if slots is None:
-        if B > state.capacity:
-            raise ValueError(f"{B} rows for a state of {state.capacity} slots")
-    else:
-        slots = _slot_tensor(slots, state)
-        if slots.numel() != B:
-            raise ValueError("item_seq and slots must have the same number of rows")
-    return items, slots, B, W
-
-
-def _stored_rows(state: SessionState, slots, B: int) -> torch.Tensor:
-    """The slots' stored out rows [B, d]; zeros for a slot outside the state."""
-    if slots is None:
-        return state.out[:B].clone()
-    y = state.out[slots.clamp(0, state.capacity - 1)]
-    y[(slots < 0) | (slots >= state.capacity)] = 0.0
-    return y
 
 
 def _first_status(seen, new):
@@ -591,7 +607,7 @@ def _append_reference(p: EncoderParams, state: SessionState, item_seq, item_seq_
                       reset: bool, return_all: bool, want_seen: bool = False):
     """append_reference's body: (its result, seen [B, S] or None)."""
     _match(p, state)
-    items, slots, B, W = _append_rows(state, item_seq, item_seq_len, slots)
+    items, slots, B, W = _rows(state, item_seq, item_seq_len, slots, "item_seq")
     if reset:
         state.reset(slots if slots is not None else torch.arange(B))
     seen = None
@@ -600,9 +616,8 @@ def _append_reference(p: EncoderParams, state: SessionState, item_seq, item_seq_
     y, status, cols = _stored_rows(state, slots, B), None, []
     for c0 in range(0, W, TILE):
         chunk = items[:, c0:c0 + TILE]
-        live = (chunk != 0).cumprod(1).bool()
-        bad = (live & ((chunk < 0) | (chunk >= p.V))).any(1)
-        fed = torch.where(live & ~bad[:, None], chunk, torch.zeros_like(chunk))
+        live, bad = _chunk_events(chunk, p.V)
+        fed = torch.where(live & ~bad, chunk, torch.zeros_like(chunk))
         st = torch.full((B,), NO_EVENT, device=state.device, dtype=torch.int32)
         for t in range(chunk.shape[1]):
             y = _step_reference(p, state, fed[:, t], slots, record=False)[0]
@@ -610,13 +625,9 @@ def _append_reference(p: EncoderParams, state: SessionState, item_seq, item_seq_
                 st = state.status.clone()          # STEPPED, NO_EVENT or BAD_SLOT
             cols.append(torch.where((fed[:, t] != 0)[:, None] & (state.status == STEPPED)[:, None],
                                     y, torch.zeros_like(y)))
-        st[bad & (st != BAD_SLOT)] = BAD_ITEM
+        st[bad[:, 0] & (st != BAD_SLOT)] = BAD_ITEM
         status = _first_status(status, st)
-    if status is None:
-        status = torch.full((B,), NO_EVENT, device=state.device, dtype=torch.int32)
-        if slots is not None:
-            status[(slots < 0) | (slots >= state.capacity)] = BAD_SLOT
-    state.status = status
+    state.status = status if status is not None else _idle_status(state, slots, B)
     if not return_all:
         return y, seen
     y_all = torch.stack(cols, 1) if cols else y.new_zeros((B, 0, p.d))
@@ -626,16 +637,10 @@ def _append_reference(p: EncoderParams, state: SessionState, item_seq, item_seq_
 def _append_kernel(p: EncoderParams, state: SessionState, layers, items, slots, y, y_all,
                    status) -> None:
     """One launch (rb_session_append): items [B, T], T events per row."""
-    t = p.t
-    B, T = items.shape
-    _lib.call_session(
-        "rb_session_append", ctypes.addressof(layers), p.num_layers,
-        t["item_embedding.weight"].data_ptr(), t["layer_norm.weight"].data_ptr(),
-        t["layer_norm.bias"].data_ptr(), LN_EPS, items.data_ptr(),
-        slots.data_ptr() if slots is not None else None, state.count.data_ptr(),
-        state.out.data_ptr(), y.data_ptr(), y_all.data_ptr() if y_all is not None else None,
-        status.data_ptr(), B, T, state.capacity, p.V, p.d, p.H, p.K, int(not p.use_conv),
-        int(not p.use_ffn), kernels._stream(y))
+    head, tail = _encoder_args(p, state, layers, items, slots, y)
+    _lib.call_session("rb_session_append", *head,
+                      y_all.data_ptr() if y_all is not None else None, status.data_ptr(),
+                      *items.shape, *tail)
 
 
 @torch.no_grad()
@@ -681,7 +686,7 @@ def _append(model, state: SessionState, item_seq, item_seq_len, slots, reset: bo
     if not kernel_supports(p.d, p.H, p.K, p.num_layers):
         return _append_reference(p, state, item_seq, item_seq_len, slots, reset, return_all,
                                  want_seen)
-    items, slots, B, W = _append_rows(state, item_seq, item_seq_len, slots)
+    items, slots, B, W = _rows(state, item_seq, item_seq_len, slots, "item_seq")
     if reset:
         state.reset(slots if slots is not None else torch.arange(B))
     seen = _record(state, items, slots, want_seen)
@@ -700,10 +705,7 @@ def _append(model, state: SessionState, item_seq, item_seq_len, slots, reset: bo
             if return_all:
                 cols.append(y_all[:, :r])
     if y is None:                       # no column at all
-        y = _stored_rows(state, slots, B)
-        status = torch.full((B,), NO_EVENT, device=state.device, dtype=torch.int32)
-        if slots is not None:
-            status[(slots < 0) | (slots >= state.capacity)] = BAD_SLOT
+        y, status = _stored_rows(state, slots, B), _idle_status(state, slots, B)
     state.status = status
     if not return_all:
         return y, seen
@@ -774,23 +776,18 @@ def _capture_ok(H: int, K: int, u, xc, rg, *aligned) -> bool:
         and all(t.data_ptr() % 16 == 0 for t in (u, xc, rg))
 
 
-def _prefill_forward(model, state: SessionState, item_seq, item_seq_len, slots, reset):
+def _prefill_forward(model, state: SessionState, item_seq, item_seq_len, slots):
     """prefill(method="forward"), see prefill."""
-    from .model import HOST_LENGTHS, attach_host_lengths
+    from .model import attach_host_lengths
 
-    if not reset:
-        raise ValueError('prefill(method="forward") needs reset=True: the forward starts from '
-                         'the empty history (method="steps" appends to a slot)')
-    item_seq = torch.as_tensor(item_seq, dtype=torch.int64)
-    if item_seq.dim() != 2:
-        raise ValueError("item_seq must be [B, T]")
-    B, T = item_seq.shape
-    host_len = getattr(item_seq_len, HOST_LENGTHS, None)
-    if host_len is None:           # lengths only on the device: one sync, as forward()
-        host_len = torch.as_tensor(item_seq_len).to("cpu")
-    host_len = host_len.to(torch.int64).reshape(-1)
+    # lengths only on the device: one sync, as forward()
+    host_len = _host_lengths(item_seq_len, sync=True).to(torch.int64).reshape(-1)
+    # no lengths for _rows: the forward reads none of the columns past a
+    # length, and zeroing them measurably slowed a host-bound call
+    seq, slots, B, T = _rows(state, item_seq, None, slots, "item_seq", empty_ok=True)
     if host_len.numel() != B:
         raise ValueError("item_seq and item_seq_len must have the same number of rows")
+    dev, lens_h = state.device, host_len
     longest = int(host_len.max()) if B else 0
     if longest > state.seq_len:
         raise ValueError(f'prefill(method="forward"): a history of {longest} items is longer '
@@ -802,15 +799,8 @@ def _prefill_forward(model, state: SessionState, item_seq, item_seq_len, slots, 
     p = _params(model)
     _refuse(model, p, state, hooks=False)
     _match(p, state)
-    dev = state.device
     if slots is None:
-        if B > state.capacity:
-            raise ValueError(f"{B} rows for a state of {state.capacity} slots")
         slots = torch.arange(B, device=dev)
-    else:
-        slots = _slot_tensor(slots, state)
-        if slots.numel() != B:
-            raise ValueError("item_seq and slots must have the same number of rows")
     state.reset(slots)
     status = torch.full((B,), NO_EVENT, device=dev, dtype=torch.int32)
     y = torch.zeros((B, p.d), device=dev, dtype=torch.float32)
@@ -818,7 +808,6 @@ def _prefill_forward(model, state: SessionState, item_seq, item_seq_len, slots, 
     rows_h = torch.nonzero(host_len > 0).reshape(-1)    # a row of length 0 stays reset
     if rows_h.numel() == 0:
         return y
-    seq, lens_h = item_seq.to(dev), host_len
     if rows_h.numel() < B:
         rows = rows_h.to(dev)
         seq, slots, lens_h = seq.index_select(0, rows), slots.index_select(0, rows), host_len[rows_h]
@@ -878,35 +867,25 @@ def prefill(model, state: SessionState, item_seq, item_seq_len, slots=None,
     row of length 0 is reset and returns its zero row.  The state agrees with
     the step-built one to rounding (the forward's f16x3 projections against
     the step's fp32 MFMA), not bitwise."""
-    if method == "forward":
-        return _prefill_forward(model, state, item_seq, item_seq_len, slots, reset)
-    if method != "steps":
+    if method not in ("steps", "forward"):
         raise ValueError(f'prefill: method must be "steps" or "forward", got {method!r}')
+    if method == "forward" and not reset:
+        raise ValueError('prefill(method="forward") needs reset=True: the forward starts from '
+                         'the empty history (method="steps" appends to a slot)')
     item_seq = torch.as_tensor(item_seq, dtype=torch.int64)
     if item_seq.dim() != 2:
         raise ValueError("item_seq must be [B, T]")
-    host_len = getattr(item_seq_len, "_recblr_host_lengths", None)
-    if host_len is None and not (isinstance(item_seq_len, torch.Tensor)
-                                 and item_seq_len.device.type != "cpu"):
-        host_len = torch.as_tensor(item_seq_len)
-    B, T = item_seq.shape
-    if host_len is not None:        # known on the host: stop at the longest row
-        T = min(T, int(host_len.max())) if B else 0
-    item_seq = item_seq.to(state.device)
-    lens = torch.as_tensor(item_seq_len).to(state.device).reshape(-1, 1)
-    cols = torch.where(torch.arange(item_seq.shape[1], device=state.device)[None] < lens,
-                       item_seq, torch.zeros_like(item_seq)).t().contiguous()
-    if slots is not None:
-        slots = _slot_tensor(slots, state)
+    if method == "forward":
+        return _prefill_forward(model, state, item_seq, item_seq_len, slots)
+    items, slots, B, T = _rows(state, item_seq, item_seq_len, slots, "item_seq", empty_ok=True)
+    cols = items.t().contiguous()
     if reset:
         state.reset(slots if slots is not None else torch.arange(B))
     fn = step if state.device.type == "cuda" else step_reference
     y = None
     for t in range(T):
         y = fn(model, state, cols[t], slots)
-    if y is None:
-        y = state.out[slots if slots is not None else slice(0, B)].clone()
-    return y
+    return y if y is not None else _stored_rows(state, slots, B)
 
 
 @torch.no_grad()
@@ -943,14 +922,10 @@ def recommend(model, state: SessionState, items=None, slots=None, k: int = 10,
         if on_gpu:
             _refuse(model, p, state)
         _match(p, state)
-        if slots is not None:
-            slots = _slot_tensor(slots, state)
-        B = state.capacity if slots is None else slots.numel()
-        if B == 0:
-            raise ValueError("slots must name at least one row")
+        B = state.capacity if slots is None else torch.as_tensor(slots).numel()
+        none, slots, B, _ = _rows(state, torch.empty((B, 0)), None, slots, "slots")
         y, seen = _stored_rows(state, slots, B), None
         if exclude_seen:
-            none = torch.empty((B, 0), device=state.device, dtype=torch.int64)
             seen = (_record(state, none, slots, True) if on_gpu
                     else record_reference(state, none, slots, True))
     else:
@@ -968,8 +943,7 @@ def recommend(model, state: SessionState, items=None, slots=None, k: int = 10,
     if slots is None:
         dead = state.count[:B] == 0
     else:
-        dead = ((slots < 0) | (slots >= state.capacity)
-                | (state.count[slots.clamp(0, state.capacity - 1)] == 0))
+        dead = _bad_slot(state, slots) | (state.count[slots.clamp(0, state.capacity - 1)] == 0)
     ids, scores = top_items(y, p.t["item_embedding.weight"], k, first_item,
                             exclude=seen if exclude_seen else None)
     ids.masked_fill_(dead[:, None], -1)
