@@ -536,7 +536,8 @@ int rb_item_ce_fwd_h(const void* seq_img, const int* seq_exp, const void* item_i
   if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
   if (!target || !lse || !loss || !workspace) return fail("rb_item_ce_fwd_h: null pointer");
   return launch_item_ce_fwd_h(seq_img, seq_exp, item_img, item_exp, target, B, V, d, lse, loss,
-                              workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+                              workspace, workspace_bytes, false, 0.0f, 0,
+                              reinterpret_cast<hipStream_t>(stream));
 }
 
 int rb_item_ce_probs_h(const void* seq_img, const int* seq_exp, const void* item_img,
@@ -547,7 +548,7 @@ int rb_item_ce_probs_h(const void* seq_img, const int* seq_exp, const void* item
   if (!target || !lse || !dloss || !probs) return fail("rb_item_ce_probs_h: null pointer");
   if (ld < V) return fail("rb_item_ce_probs_h: ld < V");
   return launch_item_ce_probs_h(seq_img, seq_exp, item_img, item_exp, target, lse, dloss, B, V, d,
-                                item_offset, probs, ld, nullptr, nullptr, 0, nullptr,
+                                item_offset, probs, ld, nullptr, nullptr, 0, nullptr, 0.0f,
                                 reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -561,7 +562,7 @@ int rb_item_ce_probs_h_t(const void* seq_img, const int* seq_exp, const void* it
   if (ldt < B || ldt % 4 || reinterpret_cast<uintptr_t>(probs_t) % 16)
     return fail("rb_item_ce_probs_h_t: probs_t must be 16-B aligned with ldt >= B, ldt % 4 == 0");
   return launch_item_ce_probs_h(seq_img, seq_exp, item_img, item_exp, target, lse, dloss, B, V, d,
-                                item_offset, probs_t, ldt, group_max, nullptr, 0, nullptr,
+                                item_offset, probs_t, ldt, group_max, nullptr, 0, nullptr, 0.0f,
                                 reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -579,7 +580,73 @@ int rb_item_ce_probs_h_both(const void* seq_img, const int* seq_exp, const void*
     return fail("rb_item_ce_probs_h_both: probs_t must be 16-B aligned with ldt >= B, ldt % 4 == 0");
   return launch_item_ce_probs_h(seq_img, seq_exp, item_img, item_exp, target, lse, dloss, B, V, d,
                                 item_offset, probs_t, ldt, item_group_max, probs, ld,
-                                row_group_max, reinterpret_cast<hipStream_t>(stream));
+                                row_group_max, 0.0f, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- include/recblr_dense.h: the all-position training loss -------------------------
+namespace {
+// the rows variants' normaliser: 1 / (live rows of the whole call)
+int check_inv_n(const char* fn, float inv_n) {
+  if (!(inv_n > 0.0f) || !(inv_n <= 1.0f)) return fail(fn, "inv_n must be in (0, 1]");
+  return 0;
+}
+}  // namespace
+
+int rb_item_ce_fwd_h_rows(const void* seq_img, const int* seq_exp, const void* item_img,
+                          const int* item_exp, const int64_t* target, int64_t B, int64_t V,
+                          int64_t d, float inv_n, int accumulate, float* lse, float* loss,
+                          void* workspace, int64_t workspace_bytes, void* stream) {
+  if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
+  if (!target || !lse || !loss || !workspace) return fail("rb_item_ce_fwd_h_rows: null pointer");
+  if (int rc = check_inv_n("rb_item_ce_fwd_h_rows", inv_n)) return rc;
+  if (accumulate != 0 && accumulate != 1)
+    return fail("rb_item_ce_fwd_h_rows: accumulate must be 0 or 1");
+  return launch_item_ce_fwd_h(seq_img, seq_exp, item_img, item_exp, target, B, V, d, lse, loss,
+                              workspace, workspace_bytes, true, inv_n, accumulate,
+                              reinterpret_cast<hipStream_t>(stream));
+}
+
+int rb_item_ce_probs_h_rows(const void* seq_img, const int* seq_exp, const void* item_img,
+                            const int* item_exp, const int64_t* target, const float* lse,
+                            const float* dloss, float inv_n, int64_t B, int64_t V, int64_t d,
+                            int64_t item_offset, float* probs, int64_t ld, void* stream) {
+  if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
+  if (!target || !lse || !dloss || !probs) return fail("rb_item_ce_probs_h_rows: null pointer");
+  if (int rc = check_inv_n("rb_item_ce_probs_h_rows", inv_n)) return rc;
+  if (ld < V) return fail("rb_item_ce_probs_h_rows: ld < V");
+  return launch_item_ce_probs_h(seq_img, seq_exp, item_img, item_exp, target, lse, dloss, B, V, d,
+                                item_offset, probs, ld, nullptr, nullptr, 0, nullptr, inv_n,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+int rb_item_ce_probs_h_both_rows(const void* seq_img, const int* seq_exp, const void* item_img,
+                                 const int* item_exp, const int64_t* target, const float* lse,
+                                 const float* dloss, float inv_n, int64_t B, int64_t V, int64_t d,
+                                 int64_t item_offset, float* probs, int64_t ld, float* probs_t,
+                                 int64_t ldt, float* row_group_max, float* item_group_max,
+                                 void* stream) {
+  if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
+  if (!target || !lse || !dloss || !probs || !probs_t || !row_group_max || !item_group_max)
+    return fail("rb_item_ce_probs_h_both_rows: null pointer");
+  if (int rc = check_inv_n("rb_item_ce_probs_h_both_rows", inv_n)) return rc;
+  if (ld < V) return fail("rb_item_ce_probs_h_both_rows: ld < V");
+  if (ldt < B || ldt % 4 || reinterpret_cast<uintptr_t>(probs_t) % 16)
+    return fail("rb_item_ce_probs_h_both_rows: probs_t must be 16-B aligned with ldt >= B, "
+                "ldt % 4 == 0");
+  return launch_item_ce_probs_h(seq_img, seq_exp, item_img, item_exp, target, lse, dloss, B, V, d,
+                                item_offset, probs_t, ldt, item_group_max, probs, ld,
+                                row_group_max, inv_n, reinterpret_cast<hipStream_t>(stream));
+}
+
+int rb_next_item_targets(const int64_t* ids, const int64_t* seq_offsets, const int64_t* order,
+                         const int64_t* pos_items, int64_t B, int64_t ntok, int64_t m_pad,
+                         int64_t* targets, void* stream) {
+  if (!ids || !seq_offsets || !order || !pos_items || !targets)
+    return fail("rb_next_item_targets: null pointer");
+  if (B < 1 || ntok < 1 || m_pad < ntok) return fail("rb_next_item_targets: need B, ntok >= 1 and m_pad >= ntok");
+  if ((m_pad + 255) / 256 > 0x7fffffffLL) return fail("rb_next_item_targets: grid too large");
+  return launch_next_item_targets(ids, seq_offsets, order, pos_items, B, ntok, m_pad, targets,
+                                  reinterpret_cast<hipStream_t>(stream));
 }
 
 int rb_group_absmax(const float* x, int64_t n, int64_t c, int64_t ld, float* out, void* stream) {

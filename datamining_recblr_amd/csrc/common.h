@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "../../include/recblr_hip.h"
+#include "../../include/recblr_dense.h"
 
 namespace rb {
 
@@ -341,6 +342,9 @@ DropSpec make_drop(const uint8_t* mask, uint64_t seed, float p);
 int launch_pack_plan(const int64_t* seq, int64_t seq_rs, const int64_t* offs,
                      const int64_t* order, int64_t B, int64_t* ids, int64_t* pos, int64_t* inv,
                      int64_t* last, hipStream_t st);
+int launch_next_item_targets(const int64_t* ids, const int64_t* offs, const int64_t* order,
+                             const int64_t* pos_items, int64_t B, int64_t ntok, int64_t m_pad,
+                             int64_t* tgt, hipStream_t st);
 // the recurrence launchers exist for T = float and T = bf16_t activation
 // storage (explicit instantiations in scan_rows.hip, conv_silu.hip, gate_scan.hip)
 template <typename T>
@@ -521,11 +525,13 @@ int launch_item_split_h(const float* X, int64_t N, int64_t D, void* img, int* ex
                         hipStream_t st);
 int launch_item_ce_fwd_h(const void* Ei, const int* Ee, const void* Wi, const int* We,
                          const int64_t* tgt, int64_t B, int64_t V, int64_t D, float* lse,
-                         float* loss, void* ws, int64_t ws_bytes, hipStream_t st);
+                         float* loss, void* ws, int64_t ws_bytes, bool rows_mode, float inv_n,
+                         int accumulate, hipStream_t st);
 int launch_item_ce_probs_h(const void* Ei, const int* Ee, const void* Wi, const int* We,
                            const int64_t* tgt, const float* lse, const float* dloss, int64_t B,
                            int64_t V, int64_t D, int64_t v_off, float* out, int64_t ld,
-                           float* gmax, float* out2, int64_t ld2, float* bmax, hipStream_t st);
+                           float* gmax, float* out2, int64_t ld2, float* bmax, float rows_inv_n,
+                           hipStream_t st);
 int launch_group_absmax(const float* x, int64_t n, int64_t c, int64_t ld, float* out,
                         hipStream_t st);
 int launch_pad_prefix_fwd(const float* conv_b, const float* gw, const float* gb,

@@ -375,6 +375,11 @@ __global__ __launch_bounds__(256) void k_ce_fwd(const float* __restrict__ E,
 // per-row loss lse - score(target) (NaN for an out-of-range target, which
 // k_ce_fwd never matches), and - in the workgroup that finishes last - the
 // batch mean in a fixed order.  `ticket` is zeroed by k_ce_fwd.
+// ROWS (the row-chunked CE with ignorable rows, rb_item_ce_fwd_h_rows): a
+// target of -1 is an ignored row (loss 0, lse still written), and loss[0] is
+// the sum of the rows' losses times the caller's inv_n, added to what loss[0]
+// holds when `accumulate` (the chunks of one call run in stream order).
+template <bool ROWS>
 __global__ __launch_bounds__(256) void k_ce_rows(const float* __restrict__ m_part,
                                                  const float* __restrict__ s_part, int64_t S,
                                                  const float* __restrict__ ts,
@@ -382,7 +387,8 @@ __global__ __launch_bounds__(256) void k_ce_rows(const float* __restrict__ m_par
                                                  int64_t V, float* __restrict__ lse,
                                                  float* __restrict__ loss_rows,
                                                  unsigned* __restrict__ ticket,
-                                                 float* __restrict__ loss) {
+                                                 float* __restrict__ loss, float inv_n,
+                                                 int accumulate) {
   // 64 rows per workgroup, one per lane; wave w merges splits w, w + 4, ...
   // in order (coalesced: a wave reads 64 consecutive rows of a split), then
   // the four waves' states merge in wave order
@@ -403,7 +409,7 @@ __global__ __launch_bounds__(256) void k_ce_rows(const float* __restrict__ m_par
     const float l = m + logf(s);
     const int64_t t = tgt[b];
     lse[b] = l;
-    loss_rows[b] = (t < 0 || t >= V) ? NAN : l - ts[b];
+    loss_rows[b] = (ROWS && t == -1) ? 0.0f : (t < 0 || t >= V) ? NAN : l - ts[b];
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -422,7 +428,8 @@ __global__ __launch_bounds__(256) void k_ce_rows(const float* __restrict__ m_par
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    loss[0] = red[0] / (float)B;
+    if constexpr (ROWS) loss[0] = (accumulate ? loss[0] : 0.0f) + red[0] * inv_n;
+    else loss[0] = red[0] / (float)B;
     *ticket = 0u;
   }
 }
@@ -1085,7 +1092,10 @@ __global__ __launch_bounds__(256) void k_ce_fwd_h(const _Float16* __restrict__ E
 // out2 [B, ld2]), gmax and every 32-row group's max |P| (bmax, atomicMax) —
 // the operands of both input gradients as rb_gemm_tn_h products
 // (scoring._bwd_f16).
-template <int D, int MODE>
+// ROWS (rb_item_ce_probs_h_rows / _both_rows): a target of -1 is an ignored
+// row; its lse is taken as +inf, so exp(x - lse) = 0 for its finite logits and
+// its P entries are exactly 0 (nothing added to either group maximum).
+template <int D, int MODE, bool ROWS = false>
 __global__ __launch_bounds__(256) void k_ce_probs_h(const _Float16* __restrict__ Ei,
                                                     const int* __restrict__ Ee,
                                                     const _Float16* __restrict__ Wi,
@@ -1114,8 +1124,9 @@ __global__ __launch_bounds__(256) void k_ce_probs_h(const _Float16* __restrict__
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
     const int64_t row = min(b0 + crow(r, h), B - 1);
-    lr[r] = lse[row];
-    const int64_t tv = tgt[row] - v_off;
+    const int64_t t = tgt[row];
+    lr[r] = (ROWS && t == -1) ? INFINITY : lse[row];
+    const int64_t tv = t - v_off;
     tr[r] = (tv >= 0 && tv < V) ? (int)tv : -1;
     er[r] = Ee[row] - 2 * kTS;
   }
@@ -1344,8 +1355,17 @@ template <int D>
 void probs_h_t(const void* Ei, const int* Ee, const void* Wi, const int* We, int64_t B, int64_t V,
                const Grid2& g, float* out, int64_t ld, const float* lse, const int64_t* tgt,
                const float* dloss, float inv_n, int64_t v_off, float* gmax, float* out2,
-               int64_t ld2, float* bmax, hipStream_t st) {
-  if (out2)
+               int64_t ld2, float* bmax, bool rows_mode, hipStream_t st) {
+  if (rows_mode && out2)
+    hipLaunchKernelGGL((k_ce_probs_h<D, 2, true>), dim3(g.wgs()), dim3(256), 0, st,
+                       (const _Float16*)Ei, Ee, (const _Float16*)Wi, We, B, V, g.per, g.blocks,
+                       g.splits, out, ld, lse, tgt, dloss, inv_n, v_off, gmax, out2, ld2, bmax);
+  else if (rows_mode)   // row-major P only (the launcher rejects P^T alone)
+    hipLaunchKernelGGL((k_ce_probs_h<D, 0, true>), dim3(g.wgs()), dim3(256), 0, st,
+                       (const _Float16*)Ei, Ee, (const _Float16*)Wi, We, B, V, g.per, g.blocks,
+                       g.splits, out, ld, lse, tgt, dloss, inv_n, v_off, nullptr, nullptr,
+                       (int64_t)0, nullptr);
+  else if (out2)
     hipLaunchKernelGGL((k_ce_probs_h<D, 2>), dim3(g.wgs()), dim3(256), 0, st,
                        (const _Float16*)Ei, Ee, (const _Float16*)Wi, We, B, V, g.per, g.blocks,
                        g.splits, out, ld, lse, tgt, dloss, inv_n, v_off, gmax, out2, ld2, bmax);
@@ -1390,8 +1410,8 @@ int launch_item_ce_fwd(const float* E, const float* W, const int64_t* tgt, int64
   const Grid2 g = plan(B, ntiles(V));
   unsigned* ticket = reinterpret_cast<unsigned*>(w + L.ticket);
   RB_ITEM_DISPATCH(D, ce_fwd_t, E, W, tgt, B, V, g, m, s, ts, ticket, st);
-  hipLaunchKernelGGL(k_ce_rows, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, m,
-                     s, g.splits, ts, tgt, B, V, lse, rows, ticket, loss);
+  hipLaunchKernelGGL(k_ce_rows<false>, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, m,
+                     s, g.splits, ts, tgt, B, V, lse, rows, ticket, loss, 0.0f, 0);
   return launch_status("rb_item_ce_fwd");
 }
 
@@ -1475,11 +1495,16 @@ int launch_item_split_h(const float* X, int64_t N, int64_t D, void* img, int* ex
   return launch_status("rb_item_split_h");
 }
 
+// rows: rb_item_ce_fwd_h_rows (target -1 = ignored row, loss = sum * inv_n,
+// added to loss[0] when accumulate); else rb_item_ce_fwd_h (inv_n unused)
 int launch_item_ce_fwd_h(const void* Ei, const int* Ee, const void* Wi, const int* We,
                          const int64_t* tgt, int64_t B, int64_t V, int64_t D, float* lse,
-                         float* loss, void* ws, int64_t ws_bytes, hipStream_t st) {
+                         float* loss, void* ws, int64_t ws_bytes, bool rows_mode, float inv_n,
+                         int accumulate, hipStream_t st) {
   const CeWs L = ce_layout(B, V, D);
-  if (ws_bytes < (int64_t)L.total) return fail("rb_item_ce_fwd_h: workspace too small");
+  if (ws_bytes < (int64_t)L.total)
+    return fail(rows_mode ? "rb_item_ce_fwd_h_rows: workspace too small"
+                          : "rb_item_ce_fwd_h: workspace too small");
   char* w = static_cast<char*>(ws);
   float* ts = reinterpret_cast<float*>(w + L.ts);
   float* m = reinterpret_cast<float*>(w + L.m);
@@ -1488,19 +1513,30 @@ int launch_item_ce_fwd_h(const void* Ei, const int* Ee, const void* Wi, const in
   const Grid2 g = plan(B, ntiles(V));
   unsigned* ticket = reinterpret_cast<unsigned*>(w + L.ticket);
   RB_ITEM_DISPATCH(D, ce_fwd_h_t, Ei, Ee, Wi, We, tgt, B, V, g, m, s, ts, ticket, st);
-  hipLaunchKernelGGL(k_ce_rows, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, m,
-                     s, g.splits, ts, tgt, B, V, lse, rows, ticket, loss);
+  if (rows_mode) {
+    hipLaunchKernelGGL(k_ce_rows<true>, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, m, s,
+                       g.splits, ts, tgt, B, V, lse, rows, ticket, loss, inv_n, accumulate);
+    return launch_status("rb_item_ce_fwd_h_rows");
+  }
+  hipLaunchKernelGGL(k_ce_rows<false>, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, m,
+                     s, g.splits, ts, tgt, B, V, lse, rows, ticket, loss, 0.0f, 0);
   return launch_status("rb_item_ce_fwd_h");
 }
 
 int launch_item_ce_probs_h(const void* Ei, const int* Ee, const void* Wi, const int* We,
                            const int64_t* tgt, const float* lse, const float* dloss, int64_t B,
                            int64_t V, int64_t D, int64_t v_off, float* out, int64_t ld,
-                           float* gmax, float* out2, int64_t ld2, float* bmax, hipStream_t st) {
+                           float* gmax, float* out2, int64_t ld2, float* bmax, float rows_inv_n,
+                           hipStream_t st) {
+  // rows_inv_n > 0: the rows variants (ignorable rows, the caller's
+  // normaliser); 0: the batch mean of the entry points without them
+  const bool rows_mode = rows_inv_n > 0.0f;
+  if (rows_mode && gmax && !out2) return fail("rb_item_ce_probs_h_rows: no transposed-only form");
   const Grid2 g = plan(B, ntiles(V));
-  const float inv_n = 1.0f / (float)B;
+  const float inv_n = rows_mode ? rows_inv_n : 1.0f / (float)B;
   RB_ITEM_DISPATCH(D, probs_h_t, Ei, Ee, Wi, We, B, V, g, out, ld, lse, tgt, dloss, inv_n, v_off,
-                   gmax, out2, ld2, bmax, st);
+                   gmax, out2, ld2, bmax, rows_mode, st);
+  if (rows_mode) return launch_status(out2 ? "rb_item_ce_probs_h_both_rows" : "rb_item_ce_probs_h_rows");
   return launch_status(out2 ? "rb_item_ce_probs_h_both"
                             : gmax ? "rb_item_ce_probs_h_t" : "rb_item_ce_probs_h");
 }

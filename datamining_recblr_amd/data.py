@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 __all__ = ["load_atomic", "kcore_filter", "remap_tokens", "SequentialData", "build_sequential",
-           "build_batch", "SequentialLoader", "write_atomic", "from_atomic_file"]
+           "build_batch", "dense_windows", "SequentialLoader", "write_atomic", "from_atomic_file"]
 
 
 def load_atomic(path: str, columns=("user_id", "item_id", "timestamp")) -> dict:
@@ -172,15 +172,53 @@ def build_batch(data: SequentialData, desc: torch.Tensor) -> dict:
             "user_id": data.user_of[tpos]}
 
 
+def dense_windows(desc: torch.Tensor, max_len: int) -> torch.Tensor:
+    """Row descriptors [R, 2] (window start, last target position) for
+    all-position training from the prefix-sample descriptors desc [S, 2] of
+    the train split (a user's samples: run start s, target positions s + 1
+    .. s + K).  One row per user holds the K items s .. s + K - 1 and, through
+    build_batch, the target s + K of its last position as item_id; position t
+    of the row trains on target s + t + 1, so the row's loss covers exactly
+    the user's K train samples.  K > max_len: the run is cut into consecutive
+    windows of max_len items counted from its end (targets s + K - max_len +
+    1 .. s + K last, the first window the shortest).  Every target still
+    appears exactly once, but a position in such a window sees a history cut
+    at the window's start, where the prefix samples slide (each sees its own
+    last max_len items)."""
+    d = desc.detach().cpu().numpy()
+    if len(d) == 0:
+        return torch.zeros((0, 2), dtype=torch.int64, device=desc.device)
+    d = d[np.argsort(d[:, 0], kind="stable")]
+    starts, first = np.unique(d[:, 0], return_index=True)
+    tmax = np.maximum.reduceat(d[:, 1], first)   # each user's last train target
+    rows = []
+    for s, t in zip(starts.tolist(), tmax.tolist()):
+        while t - s > max_len:
+            rows.append((t - max_len, t))
+            t -= max_len
+        rows.append((s, t))
+    out = np.asarray(rows, dtype=np.int64)
+    out = out[np.lexsort((out[:, 1], out[:, 0]))]
+    return torch.from_numpy(out).to(desc.device)
+
+
 class SequentialLoader:
     """Batches of one split.  shuffle: a fresh permutation per epoch from
     (seed, epoch), identical on every rank; rank r takes positions r, r+W, ...
-    (DistributedSampler); drop_last keeps per-rank batch counts equal."""
+    (DistributedSampler); drop_last keeps per-rank batch counts equal.
+    dense (train split only): one row per user window for all-position
+    training (dense_windows; RecBLR.calculate_loss_dense) instead of one row
+    per prefix sample."""
 
     def __init__(self, data: SequentialData, split: str = "train", batch_size: int = 2048,
                  shuffle: bool = True, seed: int = 2020, rank: int = 0, world: int = 1,
-                 drop_last: bool = False):
+                 drop_last: bool = False, dense: bool = False):
         self.data, self.desc = data, getattr(data, split)
+        self.dense = bool(dense)
+        if self.dense:
+            if split != "train":
+                raise ValueError("dense rows are built from the train split's samples")
+            self.desc = dense_windows(self.desc, data.max_len)
         self.batch_size, self.shuffle, self.seed = batch_size, shuffle, seed
         self.rank, self.world, self.drop_last = rank, world, drop_last
         self.epoch = 0

@@ -21,6 +21,8 @@ __all__ = [
     "item_ce_fwd", "item_ce_bwd", "item_ce_probs", "item_rank", "item_scores",
     "item_topk", "SplitRows", "item_split_h", "item_ce_fwd_h", "item_ce_probs_h",
     "embedding_bwd", "embedding_plan",
+    "item_ce_fwd_h_rows", "item_ce_probs_h_rows", "item_ce_probs_h_both_rows",
+    "next_item_targets", "next_item_targets_reference",
 ]
 
 
@@ -214,7 +216,7 @@ class Packed:
     offsets[b] .. offsets[b+1] of a 2-D [ntok, C] activation (RecBole's
     right-padded batch without the padding; include/recblr_hip.h)."""
     __slots__ = ("offsets", "B", "L", "ntok", "pos", "last", "inv", "order", "pieces", "G",
-                 "max_tiles")
+                 "max_tiles", "ids")
 
     def __init__(self, offsets: torch.Tensor, L: int, ntok: int,
                  pos: torch.Tensor | None = None):
@@ -240,6 +242,8 @@ class Packed:
         self.pieces = None
         self.G = 0
         self.max_tiles = 0          # 64-row tiles of the longest work list
+        # optional (RecBLR.forward_all): the packed item ids [ntok]
+        self.ids = None
 
 
 def _layout(t: torch.Tensor, name: str, C: int, seq: "Packed | None"):
@@ -686,7 +690,9 @@ def embedding_plan(idx, num_rows, d, stream=None):
 # MFMA roofline).
 FLOP_KERNELS = frozenset({"rb_item_ce_fwd", "rb_item_ce_bwd", "rb_item_ce_probs", "rb_item_rank",
                           "rb_item_scores", "rb_item_topk", "rb_item_ce_fwd_h", "rb_item_ce_probs_h",
-                          "rb_item_ce_probs_h_t", "rb_item_ce_probs_h_both"})
+                          "rb_item_ce_probs_h_t", "rb_item_ce_probs_h_both",
+                          "rb_item_ce_fwd_h_rows", "rb_item_ce_probs_h_rows",
+                          "rb_item_ce_probs_h_both_rows"})
 
 
 def f16_split_kernel(name: str) -> bool:
@@ -897,6 +903,89 @@ def item_ce_probs_h_both(seq: SplitRows, items: SplitRows, target, lse, dloss, i
     return p, pt, bmax, gmax
 
 
+# ---- the same three with ignorable rows (include/recblr_dense.h) -------------------
+def _check_inv_n(inv_n: float) -> float:
+    inv_n = float(inv_n)
+    if not 0.0 < inv_n <= 1.0:
+        raise ValueError(f"inv_n = {inv_n} must be in (0, 1]: 1 / (live rows of the call)")
+    return inv_n
+
+
+_ce_ws = {}
+
+
+def _ce_workspace(B: int, V: int, d: int, dev) -> torch.Tensor:
+    """rb_item_ce_workspace(B, V, d) bytes, one buffer per (shape, device,
+    stream): the chunks of a call run in order on one stream and reuse it."""
+    key = (B, V, d, dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _ce_ws.get(key)
+    if ws is None:
+        if len(_ce_ws) > 16:
+            _ce_ws.clear()
+        n = int(_lib.load().rb_item_ce_workspace(B, V, d))
+        ws = _ce_ws[key] = torch.empty((n,), device=dev, dtype=torch.uint8)
+    return ws
+
+
+def item_ce_fwd_h_rows(seq: SplitRows, items: SplitRows, target, inv_n: float, lse, loss,
+                       accumulate: bool = False) -> None:
+    """rb_item_ce_fwd_h_rows on one row chunk: target -1 = ignored row; writes
+    lse [B] and loss[0] (+)= inv_n * sum of the chunk's live rows' losses."""
+    B, V, d, target = _split_operands(seq, items, target)
+    _check(lse, "lse")
+    _check(loss, "loss")
+    if lse.shape != (B,) or not lse.is_contiguous() or loss.numel() != 1:
+        raise ValueError("lse must be contiguous [B] and loss one element")
+    ws = _ce_workspace(B, V, d, seq.img.device)
+    _launch("rb_item_ce_fwd_h_rows", 2 * B * V * d, seq.img.data_ptr(), seq.exps.data_ptr(),
+            items.img.data_ptr(), items.exps.data_ptr(), target.data_ptr(), B, V, d,
+            _check_inv_n(inv_n), int(bool(accumulate)), lse.data_ptr(), loss.data_ptr(),
+            ws.data_ptr(), ws.numel(), _stream(seq.img), _flops=True)
+
+
+def item_ce_probs_h_rows(seq: SplitRows, items: SplitRows, target, lse, dloss, inv_n: float,
+                         item_offset=0, out=None):
+    """item_ce_probs_h with ignorable rows and the caller's normaliser
+    (rb_item_ce_probs_h_rows): an ignored row's P is exactly 0."""
+    B, V, d, target = _split_operands(seq, items, target)
+    _check(lse, "lse")
+    _check(dloss, "dloss")
+    if out is None:
+        out = torch.empty((B, V), device=seq.img.device, dtype=torch.float32)
+    _check(out, "probs")
+    if out.shape != (B, V) or out.stride(1) != 1:
+        raise ValueError("probs must be [B, V] with unit column stride")
+    _launch("rb_item_ce_probs_h_rows", 2 * B * V * d, seq.img.data_ptr(), seq.exps.data_ptr(),
+            items.img.data_ptr(), items.exps.data_ptr(), target.data_ptr(),
+            lse.contiguous().data_ptr(), dloss.reshape(1).contiguous().data_ptr(),
+            _check_inv_n(inv_n), B, V, d, int(item_offset), out.data_ptr(), out.stride(0),
+            _stream(seq.img), _flops=True)
+    return out
+
+
+def item_ce_probs_h_both_rows(seq: SplitRows, items: SplitRows, target, lse, dloss, inv_n: float,
+                              item_offset=0, pad_to: int = 1):
+    """item_ce_probs_h_both with ignorable rows and the caller's normaliser
+    (rb_item_ce_probs_h_both_rows): (P [B, Vp], P^T [V, B], bmax, gmax), an
+    ignored row exactly 0 in both layouts and in both group maxima."""
+    B, V, d, target = _split_operands(seq, items, target)
+    _check(lse, "lse")
+    _check(dloss, "dloss")
+    dev = seq.img.device
+    Vp = (V + pad_to - 1) // pad_to * pad_to
+    p = torch.empty((B, Vp), device=dev, dtype=torch.float32)   # pad columns zeroed in-kernel
+    ldt = (B + 3) // 4 * 4
+    pt = torch.empty((V, ldt), device=dev, dtype=torch.float32)[:, :B]
+    maxes = torch.zeros((B + 31) // 32 + (V + 31) // 32, device=dev, dtype=torch.float32)
+    bmax, gmax = maxes[:(B + 31) // 32], maxes[(B + 31) // 32:]
+    _launch("rb_item_ce_probs_h_both_rows", 2 * B * V * d, seq.img.data_ptr(),
+            seq.exps.data_ptr(), items.img.data_ptr(), items.exps.data_ptr(), target.data_ptr(),
+            lse.contiguous().data_ptr(), dloss.reshape(1).contiguous().data_ptr(),
+            _check_inv_n(inv_n), B, V, d, int(item_offset), p.data_ptr(), Vp, pt.data_ptr(), ldt,
+            bmax.data_ptr(), gmax.data_ptr(), _stream(seq.img), _flops=True)
+    return p, pt, bmax, gmax
+
+
 def group_absmax(x: torch.Tensor) -> torch.Tensor:
     """[ceil(n/32)] max |x| over each 32-row group of a 2-D x (rb_group_absmax)."""
     _check(x, "x")
@@ -1045,6 +1134,38 @@ def pack_plan(item_seq: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor
               order.data_ptr(), B, L, ids.data_ptr(), pos.data_ptr(), inv.data_ptr(),
               last.data_ptr(), _stream(item_seq))
     return ids, pos, inv, last
+
+
+def next_item_targets(ids: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor,
+                      pos_items: torch.Tensor, m_pad: int | None = None) -> torch.Tensor:
+    """rb_next_item_targets: the all-position training targets [m_pad] of the
+    packed rows (pack_plan's ids / offsets / order; pos_items [B] in batch-row
+    order): ids[r + 1] inside a sequence, pos_items[order[s]] at its last row,
+    -1 for the rows past ntok = len(ids)."""
+    for t, n in ((ids, "ids"), (offsets, "offsets"), (order, "order"), (pos_items, "pos_items")):
+        _check(t, n, torch.int64)
+    B, ntok = order.numel(), ids.numel()
+    m_pad = ntok if m_pad is None else int(m_pad)
+    if ids.dim() != 1 or offsets.shape != (B + 1,) or pos_items.shape != (B,):
+        raise ValueError("ids must be [ntok], offsets [B + 1], order and pos_items [B]")
+    if m_pad < ntok:
+        raise ValueError(f"m_pad = {m_pad} < ntok = {ntok}")
+    out = torch.empty(m_pad, device=ids.device, dtype=torch.int64)
+    _lib.call("rb_next_item_targets", ids.contiguous().data_ptr(), offsets.contiguous().data_ptr(),
+              order.contiguous().data_ptr(), pos_items.contiguous().data_ptr(), B, ntok, m_pad,
+              out.data_ptr(), _stream(ids))
+    return out
+
+
+def next_item_targets_reference(ids: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor,
+                                pos_items: torch.Tensor, m_pad: int | None = None) -> torch.Tensor:
+    """next_item_targets in torch ops, any device (sequences of length >= 1)."""
+    ntok = ids.numel()
+    m_pad = ntok if m_pad is None else int(m_pad)
+    out = torch.full((m_pad,), -1, dtype=torch.int64, device=ids.device)
+    out[:ntok - 1] = ids[1:]
+    out[offsets[1:] - 1] = pos_items[order]
+    return out
 
 
 class _SplitJob(ctypes.Structure):

@@ -31,13 +31,14 @@ from torch import nn
 from ._lib import RecBLRNativeError
 from .blocks import (ResidualGrad, add_dropout_layer_norm, embed_dropout_layer_norm,
                      feed_forward, linear_add_dropout_layer_norm)
-from .kernels import Packed, grl_max_tiles, grl_pieces, pack_plan
+from .kernels import Packed, grl_max_tiles, grl_pieces, next_item_targets, pack_plan
 from .linear import HipLinearForward, fire_hooks, has_hooks, linear
 from .recbole_compat import BPRLoss, SequentialRecommender, install_interaction_hook
 from .recurrence import bd_lru, fused_ok, pow2_pad_len, row_pad_lens
 
 
-from .scoring import full_sort_scores, item_cross_entropy, target_ranks, top_items
+from .scoring import (full_sort_scores, item_cross_entropy, item_cross_entropy_rows,
+                      target_ranks, top_items)
 
 # RECBLR_CONV_ROWS=0: packed conv forward per sequence instead of per row tile
 _CONV_ROWS = os.environ.get("RECBLR_CONV_ROWS", "1") != "0"
@@ -281,6 +282,16 @@ class RecBLR(SequentialRecommender):
         self.bd_lru_only = config["bd_lru_only"]
         self.disable_conv1d = config["disable_conv1d"]
         self.disable_ffn = config["disable_ffn"]
+        # train on every position of a row instead of its last one
+        # (calculate_loss_dense; the rows then come from a dense loader,
+        # data.SequentialLoader(dense=True)); not a reference key, default off
+        try:
+            self.train_all_positions = bool(config["train_all_positions"])
+        except (KeyError, TypeError):
+            self.train_all_positions = False
+        if self.train_all_positions and self.loss_type == "BPR":
+            raise ValueError("train_all_positions needs loss_type 'CE': the BPR loss has one "
+                             "sampled negative per row, not per position")
         if self.bd_lru_only:  # RecBLR.py:33-35
             self.disable_conv1d = True
             self.disable_ffn = True
@@ -360,8 +371,10 @@ class RecBLR(SequentialRecommender):
             return [None] * (n + 1)
         return [ResidualGrad(last_rows if i == n - 1 else None) for i in range(n)] + [None]
 
-    def _forward_packed(self, item_seq, item_seq_len, pad, capture=None):
-        """capture: optional callable (layer index, seq, x, xc, rg, carries)
+    def _forward_packed(self, item_seq, item_seq_len, pad, capture=None, all_rows=False):
+        """all_rows: the last layer on full rows too, returns (h [ntok, d], seq)
+        (forward_all) instead of the rows gather_indexes picks.
+        capture: optional callable (layer index, seq, x, xc, rg, carries)
         run once per layer with the packed layout (kernels.Packed: offsets,
         order) and that layer's scan inputs and tile carries
         (recurrence.bd_lru); session.prefill(method="forward") reads the
@@ -410,20 +423,81 @@ class RecBLR(SequentialRecommender):
         if pad is not None:
             pad = pad.index_select(0, order)
         n = len(self.recurrent_layers)
-        slots = self._residual_slots(last if self.gather_last_layer else None)
+        gather = self.gather_last_layer and not all_rows
+        slots = self._residual_slots(last if gather else None)
+        seq.ids = ids
         h = embed_dropout_layer_norm(ids, self.item_embedding, self.dropout, self.layer_norm,
                                      self.training, slots[0])
         for i, layer in enumerate(self.recurrent_layers):
             cap = None if capture is None else functools.partial(capture, i, seq)
-            if i == n - 1 and self.gather_last_layer:
+            if i == n - 1 and gather:
                 return layer(h, pad, last, seq, slot=slots[i], capture=cap)
             h = layer(h, pad, seq=seq, slot=slots[i], out_addend=slots[i + 1], capture=cap)
+        if all_rows:
+            return h, seq
         return h.index_select(0, last)
+
+    def forward_all(self, item_seq, item_seq_len):
+        """(h [ntok, d], seq): forward() at every valid position.  The encoder
+        is causal and its pow2 pad prefix depends only on L, so row
+        seq.offsets[s] + t holds what forward() returns for the prefix
+        item_seq[seq.order[s], :t + 1] right-padded to L — the representation
+        the reference computes for RecBole's augmented sample items[:t+1] ->
+        items[t+1].  seq is the call's kernels.Packed (offsets, order, inv,
+        last, ntok, and ids: the packed item ids); rows are in packed order,
+        longest sequence first, and h[seq.last] equals forward().  The last
+        layer runs on full rows like every other layer; gradients, dropout
+        and hooks as in forward()."""
+        if self.pack_sequences:
+            return self._forward_packed(item_seq, item_seq_len, None, all_rows=True)
+        # the dense [B, L] batch without the gather, its valid positions
+        # selected into the packed order: one contract for both modes
+        B, L = item_seq.shape
+        dev = item_seq.device
+        host = getattr(item_seq_len, HOST_LENGTHS, None)
+        if host is None or host.shape != item_seq_len.shape:
+            host = item_seq_len.to("cpu")
+        lens_h = host.to(torch.int64).clamp(1, L)
+        order_h = torch.argsort(lens_h, descending=True, stable=True)
+        offs_h = torch.zeros(B + 1, dtype=torch.int64)
+        torch.cumsum(lens_h[order_h], 0, out=offs_h[1:])
+        ntok = int(offs_h[-1])
+        both = _host_ring.stage(torch.cat([offs_h, order_h]), dev)
+        offsets, order = both[:B + 1], both[B + 1:]
+        ids, pos, inv, last = pack_plan(item_seq.to(torch.int64), offsets, order, ntok)
+        seq = Packed(offsets, L, ntok, pos)
+        seq.last, seq.inv, seq.order, seq.ids = last, inv, order, ids
+        slots = self._residual_slots(None)
+        h = embed_dropout_layer_norm(item_seq, self.item_embedding, self.dropout, self.layer_norm,
+                                     self.training, slots[0])
+        for i, layer in enumerate(self.recurrent_layers):
+            h = layer(h, None, slot=slots[i], out_addend=slots[i + 1])
+        row_of = torch.repeat_interleave(order, offsets[1:] - offsets[:-1], output_size=ntok)
+        return h.reshape(B * L, -1).index_select(0, row_of * L + pos), seq
 
     def _scores_all(self, seq_output):
         return full_sort_scores(seq_output, self.item_embedding.weight)
 
+    def calculate_loss_dense(self, interaction):
+        """The CE loss at every valid position of every row: the mean over all
+        ntok positions of -log softmax(h_t . items)[next item], the next item
+        of a row's last position being POS_ITEM_ID.  Equals calculate_loss on
+        the batch expanded to one right-padded row per prefix (RecBole's
+        augmentation) with one encoder pass over the rows as they are."""
+        if self.loss_type != "CE":
+            raise ValueError("calculate_loss_dense needs loss_type 'CE'")
+        h, seq = self.forward_all(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN])
+        pos_items = interaction[self.POS_ITEM_ID].to(torch.int64)
+        m_pad = -(-seq.ntok // 256) * 256
+        target = next_item_targets(seq.ids, seq.offsets, seq.order, pos_items, m_pad)
+        if m_pad != seq.ntok:   # the loss's padding rows: zeros, target -1
+            h = F.pad(h, (0, 0, 0, m_pad - seq.ntok))
+        # every packed row is live (ntok from the host lengths: no sync)
+        return item_cross_entropy_rows(h, self.item_embedding.weight, target, n_live=seq.ntok)
+
     def calculate_loss(self, interaction):
+        if self.train_all_positions:
+            return self.calculate_loss_dense(interaction)
         seq_output = self.forward(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN])
         pos_items = interaction[self.POS_ITEM_ID]
         if self.loss_type == "BPR":

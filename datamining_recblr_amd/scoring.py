@@ -12,6 +12,9 @@ RECBLR_CE_PIPE), ranking and scores on the fp32 pipe:
   * item_cross_entropy: forward computes the per-row log-sum-exp tile by
     tile; backward recomputes the logits and forms dseq = P W and
     ditems = P^T seq from P = softmax - onehot in registers;
+  * item_cross_entropy_rows: the same loss over many rows (every position
+    of the packed batch, RecBLR.calculate_loss_dense) in row chunks, rows
+    with target -1 ignored; at most one chunk's P is ever stored;
   * target_ranks: per row, the number of items scoring above / equal to the
     target, from which Hit@k, MRR@k and NDCG@k follow exactly;
   * full_sort_scores: the score matrix itself when a caller needs it;
@@ -27,7 +30,7 @@ import torch.nn.functional as F
 
 from . import kernels
 
-__all__ = ["item_cross_entropy", "full_sort_scores", "target_ranks", "rank_metrics",
+__all__ = ["item_cross_entropy", "item_cross_entropy_rows", "full_sort_scores", "target_ranks", "rank_metrics",
            "top_items", "supported"]
 
 
@@ -228,6 +231,129 @@ def item_cross_entropy(seq: torch.Tensor, table: torch.Tensor,
     if not supported(seq, table):
         return F.cross_entropy(seq @ table.t(), target)
     return _ItemCE.apply(seq, table, target)
+
+
+# ---- the same loss over many rows, some of them ignored ----------------------------
+CE_ROWS_ALIGN = 256   # rb_gemm_tn_h's N: a chunk's rows are a multiple of it
+
+
+def _rows_f16_ok(seq, table, chunk_rows: int) -> bool:
+    """Both of a chunk's products on rb_gemm_tn_h (_bwd_f16's conditions with B
+    = chunk_rows); other supported d: one library GEMM pair per chunk."""
+    from . import linear
+    d, V = seq.shape[1], table.shape[0]
+    return (CE_GRADS == "f16" and linear.gemm_format() == "f16x3" and d % 128 == 0
+            and table.data_ptr() % 16 == 0 and 8 * chunk_rows * V <= 2 * PROBS_SLICE_BYTES
+            and (V + 255) // 256 * 256 <= GEMM_TN_MAX_N)
+
+
+class _ItemCERows(torch.autograd.Function):
+    """seq [Mp, d] (Mp a multiple of 256, padding rows zero with target -1),
+    table [V, d], target [Mp] in [0, V) or -1; inv_n = 1 / live rows."""
+
+    @staticmethod
+    def forward(ctx, seq, table, target, chunk_rows, inv_n):
+        seq, table = seq.contiguous(), table.contiguous()
+        Mp = seq.shape[0]
+        s_seq = kernels.item_split_h(seq, group_max=True)
+        s_tab = kernels.item_split_h(table, group_max=True)   # once for every chunk
+        lse = torch.empty((Mp,), device=seq.device, dtype=torch.float32)
+        loss = torch.empty((), device=seq.device, dtype=torch.float32)
+        # the chunks' partial sums are added to loss in chunk order (stream order)
+        for r0 in range(0, Mp, chunk_rows):
+            r1 = min(r0 + chunk_rows, Mp)
+            kernels.item_ce_fwd_h_rows(s_seq.rows(r0, r1), s_tab, target[r0:r1], inv_n,
+                                       lse[r0:r1], loss, accumulate=r0 > 0)
+        ctx.split = (s_seq, s_tab)
+        ctx.chunk_rows, ctx.inv_n = chunk_rows, inv_n
+        ctx.save_for_backward(seq, table, target, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        from .linear import _timed
+
+        seq, table, target, lse = ctx.saved_tensors
+        want_seq, want_items = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        s_seq, s_tab = ctx.split
+        ctx.split = None
+        chunk, inv_n = ctx.chunk_rows, ctx.inv_n
+        Mp, d = seq.shape
+        V = table.shape[0]
+        dloss = dloss.float()
+        f16 = _rows_f16_ok(seq, table, chunk)
+        dseq = torch.empty_like(seq) if want_seq else None
+        dtable = None
+        # chunk by chunk in row order: P of one chunk at a time, dtable summed
+        # in that fixed order
+        for r0 in range(0, Mp, chunk):
+            r1 = min(r0 + chunk, Mp)
+            n = r1 - r0
+            rows, tgt, l = seq[r0:r1], target[r0:r1], lse[r0:r1]
+            sr = kernels.SplitRows(s_seq.img[r0:r1], s_seq.exps[r0:r1])
+            fl = 2 * n * V * d
+            if f16:
+                p, pt, bmax, gmax = kernels.item_ce_probs_h_both_rows(sr, s_tab, tgt, l, dloss,
+                                                                      inv_n, pad_to=256)
+                if want_items:
+                    Vp = p.shape[1]
+                    S1 = _round_splits(seq.device, (Vp // 256) * (d // 128), n)
+                    parts = _timed("gemm", fl, kernels.gemm_tn_h, p, rows, bmax,
+                                   s_seq.gmax[r0 // 32:r1 // 32], S1)
+                    dt = kernels.colsum(parts.view(S1, -1)).view(Vp, d)[:V]
+                    dtable = dt.contiguous() if dtable is None else dtable.add_(dt)
+                if want_seq:
+                    S2 = _tn_splits8(seq.device, (n // 256) * (d // 128), div=2)
+                    parts = _timed("gemm", fl, kernels.gemm_tn_h, pt, table, gmax, s_tab.gmax, S2)
+                    dseq[r0:r1] = kernels.colsum(parts.view(S2, -1)).view(n, d)
+            else:
+                p = kernels.item_ce_probs_h_rows(sr, s_tab, tgt, l, dloss, inv_n)
+                if want_seq:
+                    _timed("gemm", fl, torch.mm, p, table, out=dseq[r0:r1])
+                if want_items:
+                    dtable = (_timed("gemm", fl, torch.mm, p.t(), rows) if dtable is None
+                              else _timed("gemm", fl, dtable.addmm_, p.t(), rows))
+        return dseq, dtable, None, None, None
+
+
+def item_cross_entropy_rows(seq: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
+                            chunk_rows: int = 2048, n_live: int | None = None) -> torch.Tensor:
+    """F.cross_entropy(seq @ table.T, target, ignore_index=-1) for many rows
+    without the [M, V] logits: the mean of lse - target score over the live
+    rows (target in [0, V)); a row with target -1 is ignored (no loss, zero
+    gradient; its seq values must be finite); any other target gives NaN.
+
+    The rows are walked in chunks of chunk_rows (a multiple of 256; 2048 is
+    the shape the CE kernels are measured at) on the f16-pipe CE kernels'
+    rows variants; the backward stores one chunk's P at a time and sums the
+    table's gradient over the chunks in row order (deterministic).  With d a
+    multiple of 128 and the f16x3 GEMM format both products of a chunk run on
+    rb_gemm_tn_h (no library GEMM); other d in kernels.ITEM_DIMS use one
+    library GEMM pair per chunk.  M is padded to a multiple of 256 with zero
+    rows and -1 targets; a caller that already holds such a buffer
+    (RecBLR.forward_all) passes it as it is and nothing is copied.
+    n_live: the number of live rows when the caller knows it on the host (no
+    sync); otherwise it is counted on the device (one sync).  No live row:
+    loss 0 and zero gradients.  CPU tensors, other dtypes and other d take
+    the plain torch expression above."""
+    chunk_rows = int(chunk_rows)
+    if chunk_rows < CE_ROWS_ALIGN or chunk_rows % CE_ROWS_ALIGN:
+        raise ValueError(f"chunk_rows = {chunk_rows} must be a positive multiple of {CE_ROWS_ALIGN}")
+    if seq.dim() != 2 or target.shape != (seq.shape[0],):
+        raise ValueError(f"seq [M, d] and target [M] required, got {tuple(seq.shape)} and "
+                         f"{tuple(target.shape)}")
+    if n_live is None:
+        n_live = int((target != -1).sum())
+    if n_live <= 0:   # nothing to average: 0 with zero gradients
+        return (seq.sum() + table.sum()) * 0.0
+    if not supported(seq, table):
+        return F.cross_entropy(seq @ table.t(), target, ignore_index=-1)
+    M = seq.shape[0]
+    pad = -M % CE_ROWS_ALIGN
+    if pad:
+        seq = F.pad(seq, (0, 0, 0, pad))
+        target = F.pad(target, (0, pad), value=-1)
+    return _ItemCERows.apply(seq, table, target.contiguous(), chunk_rows, 1.0 / n_live)
 
 
 def full_sort_scores(seq: torch.Tensor, table: torch.Tensor) -> torch.Tensor:

@@ -62,15 +62,21 @@ def evaluate_split(model, data, split: str, env: DistEnv, batch_size: int = 4096
 def fit(model, data, env: DistEnv, epochs: int = 100, batch_size: int = 2048,
         lr: float = 1e-3, weight_decay: float = 0.0, eval_step: int = 1,
         stopping_step: int = 10, valid_metric: str = "ndcg@10", seed: int = 2020,
-        log=print) -> dict:
-    """Train with early stopping; returns best valid / test metrics."""
+        log=print, dense: bool = False) -> dict:
+    """Train with early stopping; returns best valid / test metrics.
+    dense: all-position training — the loader yields one row per user window
+    (SequentialLoader(dense=True)) and the model, built with
+    train_all_positions, takes the loss at every position of it."""
+    if dense and not getattr(model, "train_all_positions", False):
+        raise ValueError("fit(dense=True) needs a model built with train_all_positions=True")
     step = wrap_ddp(model, env)
     # RecBole's learner 'adam' (torch.optim.Adam semantics): one native launch,
     # or torch.optim.Adam (RECBLR_ADAM=torch, or parameters it cannot take)
     from .optim import make_adam
     opt = make_adam(model.parameters(), lr=lr, weight_decay=weight_decay)
     loader = SequentialLoader(data, "train", batch_size=batch_size, shuffle=True, seed=seed,
-                              rank=env.rank, world=env.world_size, drop_last=env.distributed)
+                              rank=env.rank, world=env.world_size, drop_last=env.distributed,
+                              dense=dense)
     best, best_state, bad, history = -1.0, None, 0, []
     for ep in range(epochs):
         model.train()

@@ -49,6 +49,8 @@
  * double (everything else through a pointer); returns of those types or
  * const char*; integer constants as one-line #defines.  A new entry point is
  * declared here and defined in csrc/capi.hip, and RB_ABI_VERSION is bumped.
+ * The all-position training loss's entry points (the same library, the same
+ * version) are declared in recblr_dense.h.
  */
 #ifndef RECBLR_HIP_H
 #define RECBLR_HIP_H
@@ -72,7 +74,7 @@ typedef uint16_t rb_bf16;
 #define RB_TILE 16
 
 /* ABI version; bumped on any signature change.  rb_version() returns it. */
-#define RB_ABI_VERSION 45
+#define RB_ABI_VERSION 46
 int rb_version(void);
 
 /* Human-readable description of the last error on the calling thread. */
