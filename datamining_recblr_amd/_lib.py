@@ -94,6 +94,9 @@ SIGNATURES = parse_header(_header)
 # the same product library, typed with it by load()
 DENSE_SIGNATURES = parse_header(_read(os.path.join(os.path.dirname(HEADER_PATH),
                                                    "recblr_dense.h")))
+# the sampled pairwise loss (include/recblr_pairs.h): likewise
+PAIR_SIGNATURES = parse_header(_read(os.path.join(os.path.dirname(HEADER_PATH),
+                                                  "recblr_pairs.h")))
 # the experimental library (experimental/recblr_exp.h: opt-in kernels that
 # measured slower than the default path; never loaded unless requested)
 EXP_SIGNATURES = parse_header(_read(os.path.join(_HERE, "experimental", "recblr_exp.h")))
@@ -134,7 +137,8 @@ def _load(path, signatures, missing, version=None, mismatch=None, cache=True,
 def load(path: str | None = None) -> ctypes.CDLL:
     """Load (once) and return the native library with typed prototypes.  An
     explicit path is loaded afresh and not cached."""
-    return _load(path or LIB_PATH, {**SIGNATURES, **DENSE_SIGNATURES}, "HIP extension not built",
+    return _load(path or LIB_PATH, {**SIGNATURES, **DENSE_SIGNATURES, **PAIR_SIGNATURES},
+                 "HIP extension not built",
                  "rb_version",
                  "ABI mismatch: library {} vs binding {}; rebuild", cache=path is None,
                  hint=" (hipcc --offload-arch=gfx950)")

@@ -649,6 +649,83 @@ int rb_next_item_targets(const int64_t* ids, const int64_t* seq_offsets, const i
                                   reinterpret_cast<hipStream_t>(stream));
 }
 
+// ---- the sampled pairwise loss (include/recblr_pairs.h) ---------------------------
+int rb_sample_negatives(const int64_t* item_seq, int64_t seq_rs, const int64_t* lengths,
+                        const int64_t* pos_items, const int64_t* offsets, const int64_t* inv,
+                        int64_t B, int64_t L, int64_t n_neg, int64_t first_item, int64_t V,
+                        uint64_t seed, int64_t ntok, int64_t m_pad, int64_t* neg, void* stream) {
+  const char* fn = "rb_sample_negatives";
+  if (!item_seq || !lengths || !pos_items || !neg) return fail(fn, "null pointer");
+  if ((offsets == nullptr) != (inv == nullptr))
+    return fail(fn, "offsets and inv must be given together");
+  if (B < 1 || L < 1 || L > 8191 || seq_rs < L) return fail(fn, "need B >= 1, 1 <= L <= 8191, seq_rs >= L");
+  if (n_neg < 1 || n_neg > 16) return fail(fn, "n_neg must be in [1, 16]");
+  if (first_item < 0 || V <= first_item || V >= (int64_t(1) << 31))
+    return fail(fn, "need 0 <= first_item < V < 2^31");
+  if (offsets ? (ntok < 1 || m_pad < ntok || ntok > B * L) : (ntok != B || m_pad != B))
+    return fail(fn, "need 1 <= ntok <= m_pad (packed rows), or ntok = m_pad = B (last position only)");
+  if (B >= (int64_t(1) << 31) || B + ((m_pad - ntok) * n_neg + 255) / 256 > 0x7fffffffLL)
+    return fail(fn, "grid too large");
+  return launch_sample_negatives(item_seq, seq_rs, lengths, pos_items, offsets, inv, B, L, n_neg,
+                                 first_item, V, seed, ntok, m_pad, neg, as_stream(stream));
+}
+
+int64_t rb_pair_loss_workspace(int64_t M) { return M <= 0 ? 0 : pair_loss_workspace_bytes(M); }
+
+namespace {
+int check_pairs(const char* fn, int64_t M, int64_t d, int64_t V, int64_t n_neg, float gamma) {
+  if (M < 1 || V < 1) return fail(fn, "M and V must be positive");
+  if (d < 4 || d > 512 || d % 4) return fail(fn, "d must be a multiple of 4 in [4, 512]");
+  if (n_neg < 1 || n_neg > 16) return fail(fn, "n_neg must be in [1, 16]");
+  if (!(gamma >= 0.0f)) return fail(fn, "gamma must be >= 0");
+  if (M >= (int64_t(1) << 31) || V >= (int64_t(1) << 31)) return fail(fn, "M or V too large");
+  return 0;
+}
+}  // namespace
+
+int rb_pair_loss_fwd(const float* h, int64_t ldh, const float* table, const int64_t* pos,
+                     const int64_t* neg, int64_t M, int64_t d, int64_t V, int64_t n_neg,
+                     float gamma, float* diff, float* loss, int64_t* n_live, void* workspace,
+                     int64_t workspace_bytes, void* stream) {
+  const char* fn = "rb_pair_loss_fwd";
+  if (!h || !table || !pos || !neg || !diff || !loss || !n_live || !workspace)
+    return fail(fn, "null pointer");
+  if (int rc = check_pairs(fn, M, d, V, n_neg, gamma)) return rc;
+  if (ldh < d || ldh % 4 || !aligned16(h) || !aligned16(table))
+    return fail(fn, "h and table must be 16-B aligned with ldh >= d, ldh % 4 == 0");
+  if (workspace_bytes < pair_loss_workspace_bytes(M) || !aligned16(workspace))
+    return fail(fn, "workspace too small or misaligned");
+  return launch_pair_loss_fwd(h, ldh, table, pos, neg, M, d, V, n_neg, gamma, diff, loss, n_live,
+                              workspace, as_stream(stream));
+}
+
+int rb_pair_loss_bwd(const float* table, const int64_t* pos, const int64_t* neg,
+                     const float* diff, const float* dloss, const int64_t* n_live, int64_t M,
+                     int64_t d, int64_t V, int64_t n_neg, float gamma, float* dh, float* coef,
+                     void* stream) {
+  const char* fn = "rb_pair_loss_bwd";
+  if (!table || !pos || !neg || !diff || !dloss || !n_live || !dh || !coef)
+    return fail(fn, "null pointer");
+  if (int rc = check_pairs(fn, M, d, V, n_neg, gamma)) return rc;
+  if (!aligned16(table) || !aligned16(dh)) return fail(fn, "table and dh must be 16-B aligned");
+  return launch_pair_loss_bwd(table, pos, neg, diff, dloss, n_live, M, d, V, n_neg, gamma, dh,
+                              coef, as_stream(stream));
+}
+
+int rb_embedding_bwd_apply_scaled(const float* src, int64_t src_ld, int64_t src_rows,
+                                  const float* coef, int64_t M, int64_t d, int64_t V,
+                                  int64_t padding_idx, float* dweight, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+  const char* fn = "rb_embedding_bwd_apply_scaled";
+  if (!src || !coef || !dweight || !workspace) return fail(fn, "null pointer");
+  if (M <= 0 || d <= 0 || V <= 0) return fail(fn, "M, d, V must be positive");
+  if (M >= (int64_t(1) << 31) || V >= (int64_t(1) << 30)) return fail(fn, "M or V too large");
+  if (src_rows < 1 || src_rows >= (int64_t(1) << 31) || src_ld < d)
+    return fail(fn, "need 1 <= src_rows < 2^31 and src_ld >= d");
+  return launch_embedding_apply_scaled(src, src_ld, src_rows, coef, M, d, V, padding_idx, dweight,
+                                       workspace, workspace_bytes, as_stream(stream));
+}
+
 int rb_group_absmax(const float* x, int64_t n, int64_t c, int64_t ld, float* out, void* stream) {
   if (!x || !out) return fail("rb_group_absmax: null pointer");
   if (n <= 0 || c <= 0 || ld < c) return fail("rb_group_absmax: bad shape");

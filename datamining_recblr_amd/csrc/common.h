@@ -10,6 +10,7 @@
 
 #include "../../include/recblr_hip.h"
 #include "../../include/recblr_dense.h"
+#include "../../include/recblr_pairs.h"
 
 namespace rb {
 
@@ -500,6 +501,24 @@ int launch_embedding_apply(const float* grad, int64_t M, int64_t d, int64_t V,
                            hipStream_t st);
 int launch_embedding_bwd(const int64_t* idx, const float* grad, int64_t M, int64_t d, int64_t V,
                          int64_t padding_idx, float* dw, void* workspace, int64_t ws_bytes,
+                         hipStream_t st);
+int launch_embedding_apply_scaled(const float* src, int64_t src_ld, int64_t src_rows,
+                                  const float* coef, int64_t M, int64_t d, int64_t V,
+                                  int64_t padding_idx, float* dw, void* workspace,
+                                  int64_t ws_bytes, hipStream_t st);
+int launch_sample_negatives(const int64_t* item_seq, int64_t seq_rs, const int64_t* lengths,
+                            const int64_t* pos_items, const int64_t* offsets, const int64_t* inv,
+                            int64_t B, int64_t L, int64_t n_neg, int64_t first, int64_t V,
+                            uint64_t seed, int64_t ntok, int64_t m_pad, int64_t* neg,
+                            hipStream_t st);
+int64_t pair_loss_workspace_bytes(int64_t M);
+int launch_pair_loss_fwd(const float* h, int64_t ldh, const float* tab, const int64_t* pos,
+                         const int64_t* neg, int64_t M, int64_t d, int64_t V, int64_t n_neg,
+                         float gamma, float* diff, float* loss, int64_t* n_live, void* workspace,
+                         hipStream_t st);
+int launch_pair_loss_bwd(const float* tab, const int64_t* pos, const int64_t* neg,
+                         const float* diff, const float* dloss, const int64_t* n_live, int64_t M,
+                         int64_t d, int64_t V, int64_t n_neg, float gamma, float* dh, float* coef,
                          hipStream_t st);
 int64_t item_ce_workspace_bytes(int64_t B, int64_t V, int64_t D);
 int64_t item_rank_workspace_bytes(int64_t B, int64_t V);

@@ -23,6 +23,12 @@
 //   5. one wave per multi-chunk key adds its partials in chunk order.
 // Every sum has a fixed order, so the result is bitwise reproducible, and no
 // float atomics are used.
+//
+// SCALED (rb_embedding_bwd_apply_scaled): position p's gradient row is not
+// stored; the apply kernels read it as coef[p] * src[p mod src_rows] (one
+// fp32 multiply per element, then the same sums: bitwise the plain apply on
+// the materialised rows).  The pairwise loss's table gradient (pair_loss.hip)
+// has (1 + n) positions per row of h, all multiples of that one row.
 #include "common.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -35,10 +41,11 @@ constexpr int kChunk = 64;
 constexpr unsigned kEmbMergeLimit = 0;   // rocPRIM's default: 1 << 20
 
 __global__ void k_emb_prep(const int64_t* __restrict__ idx, int* __restrict__ keys,
-                           int* __restrict__ vals, int64_t M) {
+                           int* __restrict__ vals, int64_t M, int64_t V) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M;
        i += (int64_t)gridDim.x * blockDim.x) {
-    keys[i] = (int)idx[i];
+    const int64_t k = idx[i];
+    keys[i] = (k >= 0 && k < V) ? (int)k : (int)V;   // out of range: past every segment
     vals[i] = (int)i;
   }
 }
@@ -65,13 +72,27 @@ __global__ void k_emb_chunks(const int* __restrict__ seg, int V, int* __restrict
   }
 }
 
+// Position p's gradient row: grad[p] (row stride ld), or SCALED the row
+// sc.coef[p] * grad[p mod sc.rows]
+struct EmbScale {
+  const float* coef;
+  int rows;
+};
+
+template <bool SCALED>
+__device__ __forceinline__ float emb_elem(const float* __restrict__ grad, int64_t ld, EmbScale sc,
+                                          int p, int col) {
+  if constexpr (SCALED) return sc.coef[p] * grad[(int64_t)(p % sc.rows) * ld + col];
+  else return grad[(int64_t)p * ld + col];
+}
+
 // One wave per chunk.  choff = exclusive scan of nch (choff[V] = total).
-template <int NV>
+template <int NV, bool SCALED>
 __global__ void __launch_bounds__(256)
 k_emb_chunk_sum(const int* __restrict__ vals, const int* __restrict__ seg,
                 const int* __restrict__ nch, const int* __restrict__ choff,
                 const float* __restrict__ grad, int d, int V, int padding_idx,
-                float* __restrict__ dw, float* __restrict__ partial) {
+                float* __restrict__ dw, float* __restrict__ partial, int64_t ld, EmbScale sc) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int total = choff[V];
@@ -101,7 +122,7 @@ k_emb_chunk_sum(const int* __restrict__ vals, const int* __restrict__ seg,
 #pragma unroll
       for (int k = 0; k < NV; ++k) {
         const int col = lane + k * kWave;
-        x[u][k] = col < d ? grad[(int64_t)p[u] * d + col] : 0.0f;
+        x[u][k] = col < d ? emb_elem<SCALED>(grad, ld, sc, p[u], col) : 0.0f;
       }
 #pragma unroll
     for (int u = 0; u < 4; ++u)
@@ -113,7 +134,7 @@ k_emb_chunk_sum(const int* __restrict__ vals, const int* __restrict__ seg,
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const int col = lane + k * kWave;
-      acc[k] += col < d ? grad[(int64_t)p * d + col] : 0.0f;
+      acc[k] += col < d ? emb_elem<SCALED>(grad, ld, sc, p, col) : 0.0f;
     }
   }
   float* out = nch[v] == 1 ? dw + (int64_t)v * d : partial + c * d;
@@ -143,11 +164,12 @@ __global__ void k_emb_chunk_desc(const int* __restrict__ seg, const int* __restr
 // per lane), 16 rows per half-wave in flight.  Each half sums its rows in
 // position order and the halves are added (even rows + odd rows): a fixed
 // order, bitwise reproducible.
-template <int NV4>
+template <int NV4, bool SCALED>
 __global__ void __launch_bounds__(256)
 k_emb_chunk_sum4(const int* __restrict__ vals, const int* __restrict__ choff,
                  const int4* __restrict__ desc, const float* __restrict__ grad, int d, int V,
-                 int padding_idx, float* __restrict__ dw, float* __restrict__ partial) {
+                 int padding_idx, float* __restrict__ dw, float* __restrict__ partial, int64_t ld,
+                 EmbScale sc) {
   const int lane = threadIdx.x & (kWave - 1);
   const int hw = lane >> 5, l32 = lane & 31;
   const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -155,7 +177,12 @@ k_emb_chunk_sum4(const int* __restrict__ vals, const int* __restrict__ choff,
   const int4 dc = desc[c < total ? c : 0];
   if (c >= total || dc.x == padding_idx) return;   // the padding row: zeroed by k_emb_finish
   const int beg = dc.y, n = dc.z - dc.y;
-  const int pv = lane < n ? vals[beg + lane] : 0;
+  int pv = lane < n ? vals[beg + lane] : 0;
+  float cv = 1.0f;
+  if constexpr (SCALED) {   // the row's factor and its source row, once per row
+    cv = lane < n ? sc.coef[pv] : 0.0f;
+    pv %= sc.rows;
+  }
   const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   float4 acc[NV4];
 #pragma unroll
@@ -166,11 +193,16 @@ k_emb_chunk_sum4(const int* __restrict__ vals, const int* __restrict__ choff,
     for (int u = 0; u < 16; ++u) {
       const int r = r0 + 2 * u + hw;
       const int p = __shfl(pv, r & 63);
+      float c = 1.0f;
+      if constexpr (SCALED) c = __shfl(cv, r & 63);
 #pragma unroll
       for (int k = 0; k < NV4; ++k) {
         const int col = 4 * (l32 + 32 * k);
-        x[u][k] = (r < n && col < d) ? *reinterpret_cast<const float4*>(grad + (int64_t)p * d + col)
+        x[u][k] = (r < n && col < d) ? *reinterpret_cast<const float4*>(grad + (int64_t)p * ld + col)
                                      : zero;
+        if constexpr (SCALED) {
+          x[u][k].x *= c; x[u][k].y *= c; x[u][k].z *= c; x[u][k].w *= c;
+        }
       }
     }
 #pragma unroll
@@ -462,7 +494,7 @@ EmbWs emb_layout(int64_t M, int64_t V, int64_t d) {
   w.partial = take((size_t)max_chunks * d * 4);
   w.sort_bytes = 0;
   (void)rocprim::radix_sort_pairs<EmbSortCfg>(nullptr, w.sort_bytes, (const int*)nullptr, (int*)nullptr,
-                            (const int*)nullptr, (int*)nullptr, (size_t)M, 0, key_bits(V));
+                            (const int*)nullptr, (int*)nullptr, (size_t)M, 0, key_bits(V + 1));
   w.sort_tmp = take(w.sort_bytes);
   w.scan_bytes = 0;
   (void)rocprim::exclusive_scan(nullptr, w.scan_bytes, (const int*)nullptr, (int*)nullptr, 0,
@@ -475,9 +507,9 @@ EmbWs emb_layout(int64_t M, int64_t V, int64_t d) {
   return w;
 }
 
-template <int NV>
+template <int NV, bool SCALED>
 int emb_sums(const EmbWs& w, char* ws, const float* grad, int64_t M, int64_t d, int64_t V,
-             int64_t padding_idx, float* dw, hipStream_t st) {
+             int64_t padding_idx, float* dw, hipStream_t st, int64_t ld, EmbScale sc) {
   const int* vals = reinterpret_cast<const int*>(ws + w.vals_out);
   const int* seg = reinterpret_cast<const int*>(ws + w.seg);
   const int* nch = reinterpret_cast<const int*>(ws + w.nch);
@@ -486,23 +518,36 @@ int emb_sums(const EmbWs& w, char* ws, const float* grad, int64_t M, int64_t d, 
   const int4* desc = reinterpret_cast<const int4*>(ws + w.desc);
   const int64_t max_chunks = M / kChunk + V + 1;
   const unsigned cblocks = (unsigned)((max_chunks + 3) / 4);
-  if (d % 4 == 0 && aligned16(grad) && aligned16(dw)) {
+  if (d % 4 == 0 && ld % 4 == 0 && aligned16(grad) && aligned16(dw)) {
     if (d <= 128)
-      hipLaunchKernelGGL((k_emb_chunk_sum4<1>), dim3(cblocks), dim3(256), 0, st, vals, choff, desc,
-                         grad, (int)d, (int)V, (int)padding_idx, dw, partial);
+      hipLaunchKernelGGL((k_emb_chunk_sum4<1, SCALED>), dim3(cblocks), dim3(256), 0, st, vals,
+                         choff, desc, grad, (int)d, (int)V, (int)padding_idx, dw, partial, ld, sc);
     else if (d <= 256)
-      hipLaunchKernelGGL((k_emb_chunk_sum4<2>), dim3(cblocks), dim3(256), 0, st, vals, choff, desc,
-                         grad, (int)d, (int)V, (int)padding_idx, dw, partial);
+      hipLaunchKernelGGL((k_emb_chunk_sum4<2, SCALED>), dim3(cblocks), dim3(256), 0, st, vals,
+                         choff, desc, grad, (int)d, (int)V, (int)padding_idx, dw, partial, ld, sc);
     else
-      hipLaunchKernelGGL((k_emb_chunk_sum4<4>), dim3(cblocks), dim3(256), 0, st, vals, choff, desc,
-                         grad, (int)d, (int)V, (int)padding_idx, dw, partial);
+      hipLaunchKernelGGL((k_emb_chunk_sum4<4, SCALED>), dim3(cblocks), dim3(256), 0, st, vals,
+                         choff, desc, grad, (int)d, (int)V, (int)padding_idx, dw, partial, ld, sc);
   } else {
-    hipLaunchKernelGGL((k_emb_chunk_sum<NV>), dim3(cblocks), dim3(256), 0, st, vals, seg, nch,
-                       choff, grad, (int)d, (int)V, (int)padding_idx, dw, partial);
+    hipLaunchKernelGGL((k_emb_chunk_sum<NV, SCALED>), dim3(cblocks), dim3(256), 0, st, vals, seg,
+                       nch, choff, grad, (int)d, (int)V, (int)padding_idx, dw, partial, ld, sc);
   }
   hipLaunchKernelGGL((k_emb_finish<NV>), dim3((unsigned)V), dim3(256), 0, st, nch,
                      choff, partial, (int)d, (int)V, (int)padding_idx, dw);
   return launch_status("rb_embedding_bwd");
+}
+
+template <bool SCALED>
+int emb_apply(const float* grad, int64_t ld, EmbScale sc, int64_t M, int64_t d, int64_t V,
+              int64_t padding_idx, float* dw, void* workspace, int64_t ws_bytes, hipStream_t st) {
+  const EmbWs w = emb_layout(M, V, d);
+  if (ws_bytes < (int64_t)w.total) return fail("rb_embedding_bwd: workspace too small");
+  char* ws = static_cast<char*>(workspace);
+  if (d <= 64) return emb_sums<1, SCALED>(w, ws, grad, M, d, V, padding_idx, dw, st, ld, sc);
+  if (d <= 128) return emb_sums<2, SCALED>(w, ws, grad, M, d, V, padding_idx, dw, st, ld, sc);
+  if (d <= 256) return emb_sums<4, SCALED>(w, ws, grad, M, d, V, padding_idx, dw, st, ld, sc);
+  if (d <= 512) return emb_sums<8, SCALED>(w, ws, grad, M, d, V, padding_idx, dw, st, ld, sc);
+  return fail("rb_embedding_bwd: d must be <= 512");
 }
 
 }  // namespace
@@ -538,10 +583,10 @@ int launch_embedding_plan(const int64_t* idx, int64_t M, int64_t d, int64_t V, v
   }
   const int64_t pblocks = std::min<int64_t>(4096, (M + 255) / 256);
   hipLaunchKernelGGL(k_emb_prep, dim3((unsigned)pblocks), dim3(256), 0, st, idx, keys_in, vals_in,
-                     M);
+                     M, V);
   size_t sb = w.sort_bytes;
   if (rocprim::radix_sort_pairs<EmbSortCfg>(ws + w.sort_tmp, sb, keys_in, keys_out, vals_in, vals_out,
-                                (size_t)M, 0, key_bits(V), st) != hipSuccess)
+                                (size_t)M, 0, key_bits(V + 1), st) != hipSuccess)
     return fail("rb_embedding_bwd: radix sort failed");
   const unsigned vb = (unsigned)((V + 256) / 256);
   hipLaunchKernelGGL(k_emb_segments, dim3(vb), dim3(256), 0, st, keys_out, M, (int)V, seg);
@@ -558,14 +603,16 @@ int launch_embedding_plan(const int64_t* idx, int64_t M, int64_t d, int64_t V, v
 int launch_embedding_apply(const float* grad, int64_t M, int64_t d, int64_t V,
                            int64_t padding_idx, float* dw, void* workspace, int64_t ws_bytes,
                            hipStream_t st) {
-  const EmbWs w = emb_layout(M, V, d);
-  if (ws_bytes < (int64_t)w.total) return fail("rb_embedding_bwd: workspace too small");
-  char* ws = static_cast<char*>(workspace);
-  if (d <= 64) return emb_sums<1>(w, ws, grad, M, d, V, padding_idx, dw, st);
-  if (d <= 128) return emb_sums<2>(w, ws, grad, M, d, V, padding_idx, dw, st);
-  if (d <= 256) return emb_sums<4>(w, ws, grad, M, d, V, padding_idx, dw, st);
-  if (d <= 512) return emb_sums<8>(w, ws, grad, M, d, V, padding_idx, dw, st);
-  return fail("rb_embedding_bwd: d must be <= 512");
+  return emb_apply<false>(grad, d, EmbScale{nullptr, 1}, M, d, V, padding_idx, dw, workspace,
+                          ws_bytes, st);
+}
+
+int launch_embedding_apply_scaled(const float* src, int64_t src_ld, int64_t src_rows,
+                                  const float* coef, int64_t M, int64_t d, int64_t V,
+                                  int64_t padding_idx, float* dw, void* workspace,
+                                  int64_t ws_bytes, hipStream_t st) {
+  return emb_apply<true>(src, src_ld, EmbScale{coef, (int)src_rows}, M, d, V, padding_idx, dw,
+                         workspace, ws_bytes, st);
 }
 
 int launch_embedding_bwd(const int64_t* idx, const float* grad, int64_t M, int64_t d, int64_t V,

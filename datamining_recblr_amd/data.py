@@ -208,13 +208,19 @@ class SequentialLoader:
     (DistributedSampler); drop_last keeps per-rank batch counts equal.
     dense (train split only): one row per user window for all-position
     training (dense_windows; RecBLR.calculate_loss_dense) instead of one row
-    per prefix sample."""
+    per prefix sample.
+    negatives: every batch also carries neg_item_id [B], one sampled negative
+    per row for the reference's last-position BPR loss: uniform over the items
+    outside the row's window and target (RecBole rejects against the user's
+    whole history; a row here knows only its window), drawn by
+    kernels.sample_negatives on a GPU-resident SequentialData and by its host
+    reference on the CPU — the same ids — from (seed, epoch, batch)."""
 
     def __init__(self, data: SequentialData, split: str = "train", batch_size: int = 2048,
                  shuffle: bool = True, seed: int = 2020, rank: int = 0, world: int = 1,
-                 drop_last: bool = False, dense: bool = False):
+                 drop_last: bool = False, dense: bool = False, negatives: bool = False):
         self.data, self.desc = data, getattr(data, split)
-        self.dense = bool(dense)
+        self.dense, self.negatives = bool(dense), bool(negatives)
         if self.dense:
             if split != "train":
                 raise ValueError("dense rows are built from the train split's samples")
@@ -242,6 +248,14 @@ class SequentialLoader:
         n = len(self._indices())
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
+    def _negatives(self, batch: dict, b: int) -> torch.Tensor:
+        from . import kernels
+
+        seq, n, pos = batch["item_id_list"], batch["item_length"], batch["item_id"]
+        seed = ((self.seed * 1000003 + self.epoch) << 24) + (b << 4) + self.rank % 16
+        draw = kernels.sample_negatives if seq.is_cuda else kernels.sample_negatives_reference
+        return draw(seq, n, pos, 1, 1, self.data.n_items, seed)[:, 0].to(seq.device)
+
     def __iter__(self):
         from .model import attach_host_lengths
         idx_h = self._indices()
@@ -256,6 +270,8 @@ class SequentialLoader:
             dh = desc_h[idx_h[b * self.batch_size:(b + 1) * self.batch_size]]
             attach_host_lengths(batch["item_length"],
                                 torch.clamp(dh[:, 1] - dh[:, 0], max=self.data.max_len))
+            if self.negatives:
+                batch["neg_item_id"] = self._negatives(batch, b)
             yield batch
 
 

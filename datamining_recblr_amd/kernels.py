@@ -23,6 +23,8 @@ __all__ = [
     "embedding_bwd", "embedding_plan",
     "item_ce_fwd_h_rows", "item_ce_probs_h_rows", "item_ce_probs_h_both_rows",
     "next_item_targets", "next_item_targets_reference",
+    "sample_negatives", "sample_negatives_reference", "philox4x32_10", "pair_loss_fwd",
+    "pair_loss_bwd", "embedding_bwd_scaled", "pair_loss_supported",
 ]
 
 
@@ -1166,6 +1168,195 @@ def next_item_targets_reference(ids: torch.Tensor, offsets: torch.Tensor, order:
     out[:ntok - 1] = ids[1:]
     out[offsets[1:] - 1] = pos_items[order]
     return out
+
+
+# ---- sampled pairwise loss (csrc/pair_loss.hip, include/recblr_pairs.h) -----------
+MAX_NEGATIVES = 16
+SAMPLE_ATTEMPTS = 16
+PAIR_MAX_D = 512
+
+
+def pair_loss_supported(h: torch.Tensor, table: torch.Tensor) -> bool:
+    """The pair-loss kernels take fp32 GPU rows of d a multiple of 4 up to 512."""
+    return (h.is_cuda and h.dtype == torch.float32 and table.dtype == torch.float32
+            and h.dim() == 2 and h.shape[1] % 4 == 0 and 4 <= h.shape[1] <= PAIR_MAX_D)
+
+
+def sample_negatives(item_seq: torch.Tensor, lengths: torch.Tensor, pos_items: torch.Tensor,
+                     n_neg: int, first_item: int, num_items: int, seed: int,
+                     offsets: torch.Tensor | None = None, inv: torch.Tensor | None = None,
+                     ntok: int | None = None, m_pad: int | None = None) -> torch.Tensor:
+    """rb_sample_negatives: n_neg ids per position, uniform over [first_item,
+    num_items) minus the row's seen set item_seq[b, :len_b] + {pos_items[b]}
+    (the row's window, not the user's whole history); -1 when every id is
+    seen.  offsets [B + 1] / inv [B] / ntok (Packed.offsets / .inv / .ntok):
+    every valid position, [m_pad, n_neg] in packed order (m_pad defaults to
+    ntok; the rows past ntok are -1); without them [B, n_neg], each row's last
+    position — the dense call's rows at Packed.last.  The draw of (b, t,
+    j) depends only on (seed, b, t, j) and the row: see
+    sample_negatives_reference."""
+    for t, n in ((item_seq, "item_seq"), (lengths, "lengths"), (pos_items, "pos_items")):
+        _check(t, n, torch.int64)
+    if item_seq.dim() != 2 or item_seq.stride(1) != 1:
+        item_seq = item_seq.contiguous()
+    B, L = item_seq.shape
+    if lengths.shape != (B,) or pos_items.shape != (B,):
+        raise ValueError("lengths and pos_items must be [B]")
+    if (offsets is None) != (inv is None):
+        raise ValueError("offsets and inv are given together")
+    if offsets is not None:
+        _check(offsets, "offsets", torch.int64)
+        _check(inv, "inv", torch.int64)
+        if offsets.shape != (B + 1,) or inv.shape != (B,) or ntok is None:
+            raise ValueError("offsets must be [B + 1], inv [B], and ntok given")
+        ntok = int(ntok)
+        m_pad = ntok if m_pad is None else int(m_pad)
+        offsets, inv = offsets.contiguous(), inv.contiguous()
+    else:
+        ntok = m_pad = B
+    out = torch.empty((m_pad, int(n_neg)), device=item_seq.device, dtype=torch.int64)
+    _launch("rb_sample_negatives", 8 * (B * L + out.numel()), item_seq.data_ptr(),
+            item_seq.stride(0), lengths.contiguous().data_ptr(), pos_items.contiguous().data_ptr(),
+            offsets.data_ptr() if offsets is not None else None,
+            inv.data_ptr() if inv is not None else None, B, L, int(n_neg), int(first_item),
+            int(num_items), int(seed) & (2 ** 64 - 1), ntok, m_pad, out.data_ptr(),
+            _stream(item_seq))
+    return out
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11) on numpy uint64 arrays holding
+    32-bit words: counter (c0, c1, c2, c3), key (k0, k1) -> the four output
+    words.  The host restatement of the kernels' generator."""
+    import numpy as np
+
+    m32 = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(x, dtype=np.uint64) & m32 for x in counter]
+    k0, k1 = (np.asarray(x, dtype=np.uint64) & m32 for x in key)
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k1,
+             p0 & m32]
+        k0 = (k0 + np.uint64(0x9E3779B9)) & m32
+        k1 = (k1 + np.uint64(0xBB67AE85)) & m32
+    return c
+
+
+def sample_negatives_reference(item_seq, lengths, pos_items, n_neg, first_item, num_items, seed,
+                               offsets=None, inv=None, ntok=None, m_pad=None, stats=None):
+    """sample_negatives restated on the host (numpy, its own Philox): the
+    checked reference, and the CPU path of the data loader.  Same arguments;
+    returns a CPU int64 tensor.  stats: a dict
+    that receives how many draws were settled by the 16 attempts
+    ("attempts"), by the walk ("walk"), or found every id seen ("exhausted")."""
+    import numpy as np
+
+    seq = item_seq.detach().cpu().numpy().astype(np.int64)
+    B, L = seq.shape
+    lens = np.clip(lengths.detach().cpu().numpy().astype(np.int64), 1, L)
+    pos = pos_items.detach().cpu().numpy().astype(np.int64)
+    n_neg, first, V = int(n_neg), int(first_item), int(num_items)
+    R = V - first
+    seed = int(seed) & (2 ** 64 - 1)
+    key = (seed & 0xFFFFFFFF, seed >> 32)
+    dense = offsets is not None
+    if dense:
+        offs = offsets.detach().cpu().numpy()
+        inv_h = inv.detach().cpu().numpy()
+        rows = int(ntok) if m_pad is None else int(m_pad)
+    else:
+        rows = B
+    out = np.full((rows, n_neg), -1, dtype=np.int64)
+    count = {"attempts": 0, "walk": 0, "exhausted": 0}
+    for b in range(B):
+        n = int(lens[b])
+        seen = set(seq[b, :n].tolist()) | {int(pos[b])}
+        ts = np.arange(n) if dense else np.array([n - 1])
+        tt, jj = np.meshgrid(ts, np.arange(n_neg), indexing="ij")
+        tt, jj = tt.reshape(-1), jj.reshape(-1)
+        res = np.full(tt.shape, -2, dtype=np.int64)   # -2: not settled yet
+        cand = np.zeros(tt.shape, dtype=np.int64)
+        for a in range(SAMPLE_ATTEMPTS):
+            if a % 4 == 0:
+                words = philox4x32_10((np.full(tt.shape, b), tt, jj, np.full(tt.shape, a // 4)),
+                                      key)
+            cand = first + ((words[a % 4] * np.uint64(R)) >> np.uint64(32)).astype(np.int64)
+            free = (res == -2) & ~np.isin(cand, list(seen))
+            res[free] = cand[free]
+        count["attempts"] += int((res != -2).sum())
+        for i in np.flatnonzero(res == -2):   # the walk, upward from the 16th candidate
+            off, res[i] = int(cand[i]) - first, -1
+            for _ in range(R - 1):
+                off = (off + 1) % R
+                if first + off not in seen:
+                    res[i] = first + off
+                    break
+            count["walk" if res[i] >= 0 else "exhausted"] += 1
+        r = (int(offs[inv_h[b]]) + tt) if dense else np.full(tt.shape, b)
+        out[r, jj] = res
+    if stats is not None:
+        stats.update(count)
+    return torch.from_numpy(out)
+
+
+def pair_loss_fwd(h: torch.Tensor, table: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor,
+                  gamma: float):
+    """rb_pair_loss_fwd: (loss [], n_live [] int64, diff [M, n]) of h [M, d]
+    (unit-stride rows, any 16-B aligned row stride), table [V, d], pos [M] and
+    neg [M, n] int64 with -1 = ignored."""
+    _check(h, "h")
+    _check(table, "table")
+    _check(pos, "pos", torch.int64)
+    _check(neg, "neg", torch.int64)
+    M, d = h.shape
+    V, n = table.shape[0], neg.shape[1]
+    if pos.shape != (M,) or neg.shape != (M, n) or table.shape[1] != d:
+        raise ValueError("pair loss: h [M, d], table [V, d], pos [M], neg [M, n]")
+    dev = h.device
+    diff = torch.empty((M, n), device=dev, dtype=torch.float32)
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    n_live = torch.empty((), device=dev, dtype=torch.int64)
+    ws_bytes = int(_lib.load().rb_pair_loss_workspace(M))
+    ws = torch.empty((ws_bytes,), device=dev, dtype=torch.uint8)
+    _launch("rb_pair_loss_fwd", 4 * (2 + n) * M * d, h.data_ptr(), h.stride(0), table.data_ptr(),
+            pos.data_ptr(), neg.data_ptr(), M, d, V, n, float(gamma), diff.data_ptr(),
+            loss.data_ptr(), n_live.data_ptr(), ws.data_ptr(), ws_bytes, _stream(h))
+    return loss, n_live, diff
+
+
+def pair_loss_bwd(table: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, diff: torch.Tensor,
+                  dloss: torch.Tensor, n_live: torch.Tensor, gamma: float):
+    """rb_pair_loss_bwd: (dh [M, d], coef [(1 + n) * M]) — coef laid out as
+    [sum_j c_rj | -c_r0 | -c_r1 ...], one block of M per id column."""
+    M, n = neg.shape
+    V, d = table.shape
+    dh = torch.empty((M, d), device=table.device, dtype=torch.float32)
+    coef = torch.empty(((1 + n) * M,), device=table.device, dtype=torch.float32)
+    _launch("rb_pair_loss_bwd", 4 * (2 + n) * M * d, table.data_ptr(), pos.data_ptr(),
+            neg.data_ptr(), diff.data_ptr(), dloss.data_ptr(), n_live.data_ptr(), M, d, V, n,
+            float(gamma), dh.data_ptr(), coef.data_ptr(), _stream(table))
+    return dh, coef
+
+
+def embedding_bwd_scaled(coef: torch.Tensor, src: torch.Tensor, num_rows: int, plan: torch.Tensor,
+                         padding_idx=None):
+    """embedding_bwd with position p's gradient row read as coef[p] * src[p
+    mod len(src)] (rb_embedding_bwd_apply_scaled): the len(coef) rows are never
+    stored; bitwise embedding_bwd on them.  plan: embedding_plan of the
+    len(coef) ids."""
+    _check(coef, "coef")
+    _check(src, "src")
+    M = coef.numel()
+    rows, d = src.shape
+    if src.stride(1) != 1 or (d % 4 == 0 and (src.stride(0) % 4 or src.data_ptr() % 16)):
+        src = src.contiguous()   # the 16-B row loads, as the plain apply takes them
+    dw = torch.empty((num_rows, d), device=src.device, dtype=torch.float32)
+    pad = -1 if padding_idx is None else int(padding_idx)
+    _launch("rb_embedding_bwd_scaled", 4 * M * d + 4 * num_rows * d, src.data_ptr(), src.stride(0),
+            rows, coef.contiguous().data_ptr(), M, d, num_rows, pad, dw.data_ptr(),
+            plan.data_ptr(), plan.numel(), _stream(src), _fn="rb_embedding_bwd_apply_scaled")
+    return dw
 
 
 class _SplitJob(ctypes.Structure):

@@ -29,15 +29,16 @@ import torch.nn.functional as F
 from torch import nn
 
 from ._lib import RecBLRNativeError
-from .blocks import (ResidualGrad, add_dropout_layer_norm, embed_dropout_layer_norm,
+from .blocks import (ResidualGrad, add_dropout_layer_norm, draw_seed, embed_dropout_layer_norm,
                      feed_forward, linear_add_dropout_layer_norm)
-from .kernels import Packed, grl_max_tiles, grl_pieces, next_item_targets, pack_plan
+from .kernels import (MAX_NEGATIVES, Packed, grl_max_tiles, grl_pieces, next_item_targets,
+                      pack_plan, sample_negatives)
 from .linear import HipLinearForward, fire_hooks, has_hooks, linear
 from .recbole_compat import BPRLoss, SequentialRecommender, install_interaction_hook
 from .recurrence import bd_lru, fused_ok, pow2_pad_len, row_pad_lens
 
 
-from .scoring import (full_sort_scores, item_cross_entropy, item_cross_entropy_rows,
+from .scoring import (full_sort_scores, item_cross_entropy, item_cross_entropy_rows, pair_loss,
                       target_ranks, top_items)
 
 # RECBLR_CONV_ROWS=0: packed conv forward per sequence instead of per row tile
@@ -292,6 +293,18 @@ class RecBLR(SequentialRecommender):
         if self.train_all_positions and self.loss_type == "BPR":
             raise ValueError("train_all_positions needs loss_type 'CE': the BPR loss has one "
                              "sampled negative per row, not per position")
+        # all-position training with n sampled negatives per position in place
+        # of the full-vocabulary CE (calculate_loss_pairs); not a reference
+        # key, default 0 = off.  loss_type keeps the reference's meaning
+        try:
+            self.dense_negatives = int(config["dense_negatives"] or 0)
+        except (KeyError, TypeError):
+            self.dense_negatives = 0
+        if not 0 <= self.dense_negatives <= MAX_NEGATIVES:
+            raise ValueError(f"dense_negatives must be in [0, {MAX_NEGATIVES}]")
+        if self.dense_negatives and not self.train_all_positions:
+            raise ValueError("dense_negatives needs train_all_positions: True (the negatives "
+                             "are sampled at every position of a row)")
         if self.bd_lru_only:  # RecBLR.py:33-35
             self.disable_conv1d = True
             self.disable_ffn = True
@@ -495,8 +508,35 @@ class RecBLR(SequentialRecommender):
         # every packed row is live (ntok from the host lengths: no sync)
         return item_cross_entropy_rows(h, self.item_embedding.weight, target, n_live=seq.ntok)
 
+    def calculate_loss_pairs(self, interaction, negatives=None):
+        """The sampled pairwise (BPR) loss at every valid position of every
+        row: the mean over all positions t and negatives j of -log(1e-10 +
+        sigmoid(h_t . E[next item] - h_t . E[neg_tj])).  negatives: int64
+        [ntok or more rows, n] in packed order (forward_all's rows; -1 = no
+        pair), or None: dense_negatives (at least 1) ids per position drawn on
+        the device (kernels.sample_negatives, seeded from torch's generator
+        like the dropout), uniform over the items outside the row's own
+        window and target.  RecBole rejects against the user's whole history;
+        a row here knows only its window.  With one negative per position
+        this equals the reference's BPR calculate_loss on the batch expanded
+        to one row per prefix with those negatives as NEG_ITEM_ID."""
+        item_seq, lengths = interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN]
+        h, seq = self.forward_all(item_seq, lengths)
+        pos_items = interaction[self.POS_ITEM_ID].to(torch.int64)
+        target = next_item_targets(seq.ids, seq.offsets, seq.order, pos_items)
+        if negatives is None:
+            negatives = sample_negatives(item_seq.to(torch.int64), lengths.to(torch.int64),
+                                         pos_items, max(self.dense_negatives, 1), 1, self.n_items,
+                                         draw_seed(), seq.offsets, seq.inv, seq.ntok)
+        elif negatives.dim() != 2 or negatives.shape[0] < seq.ntok:
+            raise ValueError(f"negatives must be [{seq.ntok} or more rows, n] in packed order, "
+                             f"got {tuple(negatives.shape)}")
+        return pair_loss(h, self.item_embedding.weight, target, negatives[:seq.ntok])
+
     def calculate_loss(self, interaction):
         if self.train_all_positions:
+            if self.dense_negatives:
+                return self.calculate_loss_pairs(interaction)
             return self.calculate_loss_dense(interaction)
         seq_output = self.forward(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN])
         pos_items = interaction[self.POS_ITEM_ID]

@@ -15,6 +15,9 @@ RECBLR_CE_PIPE), ranking and scores on the fp32 pipe:
   * item_cross_entropy_rows: the same loss over many rows (every position
     of the packed batch, RecBLR.calculate_loss_dense) in row chunks, rows
     with target -1 ignored; at most one chunk's P is ever stored;
+  * pair_loss: the sampled pairwise (BPR) loss of many rows against each
+    row's target and its sampled negatives only (csrc/pair_loss.hip;
+    RecBLR.calculate_loss_pairs) — no sweep over the table at all;
   * target_ranks: per row, the number of items scoring above / equal to the
     target, from which Hit@k, MRR@k and NDCG@k follow exactly;
   * full_sort_scores: the score matrix itself when a caller needs it;
@@ -31,7 +34,7 @@ import torch.nn.functional as F
 from . import kernels
 
 __all__ = ["item_cross_entropy", "item_cross_entropy_rows", "full_sort_scores", "target_ranks", "rank_metrics",
-           "top_items", "supported"]
+           "top_items", "supported", "pair_loss", "pair_loss_reference"]
 
 
 def supported(seq: torch.Tensor, table: torch.Tensor) -> bool:
@@ -354,6 +357,85 @@ def item_cross_entropy_rows(seq: torch.Tensor, table: torch.Tensor, target: torc
         seq = F.pad(seq, (0, 0, 0, pad))
         target = F.pad(target, (0, pad), value=-1)
     return _ItemCERows.apply(seq, table, target.contiguous(), chunk_rows, 1.0 / n_live)
+
+
+def pair_loss_reference(h: torch.Tensor, table: torch.Tensor, pos: torch.Tensor,
+                        neg: torch.Tensor, gamma: float = 1e-10) -> torch.Tensor:
+    """pair_loss in torch ops, any device and dtype: the CPU path and the
+    fallback for a d the kernels refuse.  An id outside [-1, V) gives NaN."""
+    V = table.shape[0]
+    live = (pos >= 0)[:, None] & (neg >= 0)
+    bad = ((pos < -1) | (pos >= V))[:, None] | (neg < -1) | (neg >= V)
+    ps = (h * table[pos.clamp(0, V - 1)]).sum(-1)
+    ns = (h[:, None, :] * table[neg.clamp(0, V - 1)]).sum(-1)
+    l = -torch.log(gamma + torch.sigmoid(ps[:, None] - ns))
+    l = torch.where(live & ~bad, l, torch.zeros_like(l))
+    loss = l.sum() / live.sum().clamp(min=1)
+    return torch.where(bad.any(), torch.full_like(loss, float("nan")), loss)
+
+
+class _PairLoss(torch.autograd.Function):
+    """h [M, d], table [V, d], pos [M], neg [M, n]: the forward saves diff and
+    plans the table's scatter (index work only); the backward is the
+    coefficient kernel and the scaled apply."""
+
+    @staticmethod
+    def forward(ctx, h, table, pos, neg, gamma):
+        table = table.contiguous()
+        if h.stride(1) != 1 or h.stride(0) % 4 or h.data_ptr() % 16:
+            h = h.contiguous()
+        pos, neg = pos.contiguous(), neg.contiguous()
+        loss, n_live, diff = kernels.pair_loss_fwd(h, table, pos, neg, gamma)
+        ctx.plan = None
+        if ctx.needs_input_grad[1]:   # ids [pos | neg_0 | neg_1 ...], one block of M each
+            ids = torch.cat([pos, neg.t().reshape(-1)])
+            ctx.plan = kernels.embedding_plan(ids, table.shape[0], table.shape[1])
+        ctx.gamma = gamma
+        ctx.save_for_backward(h, table, pos, neg, diff, n_live)
+        ctx.mark_non_differentiable(n_live)
+        return loss, n_live
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        h, table, pos, neg, diff, n_live = ctx.saved_tensors
+        plan, ctx.plan = ctx.plan, None
+        dh, coef = kernels.pair_loss_bwd(table, pos, neg, diff, dloss.float().contiguous(),
+                                         n_live, ctx.gamma)
+        dtable = None
+        if plan is not None:
+            dtable = kernels.embedding_bwd_scaled(coef, h, table.shape[0], plan)
+        return (dh if ctx.needs_input_grad[0] else None), dtable, None, None, None
+
+
+def pair_loss(h: torch.Tensor, table: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor,
+              gamma: float = 1e-10, return_live: bool = False) -> torch.Tensor:
+    """The sampled pairwise (BPR) loss of rows h [M, d] against table [V, d]:
+    the mean over the live pairs (r, j) of
+
+        -log(gamma + sigmoid(h_r . table[pos_r] - h_r . table[neg_rj]))
+
+    with pos [M] and neg [M, n] int64; pos_r = -1 ignores row r and neg_rj =
+    -1 pair (r, j) (no loss, exactly zero gradient); any other id outside [0,
+    V) gives NaN.  No live pair: loss 0 and zero gradients.  With n = 1 and
+    every pair live this is RecBole's BPRLoss (gamma 1e-10) on the pairs.
+    Only (2 + n) rows of d floats are read per row of h; the table's gradient
+    goes through the embedding backward's deterministic plan with its
+    gradient rows formed on the fly (rb_embedding_bwd_apply_scaled), so the
+    result is bitwise reproducible.  return_live: also the live-pair count (a
+    device scalar, no sync).  CPU tensors, other dtypes and a d that is no
+    multiple of 4 up to 512 take pair_loss_reference."""
+    if h.dim() != 2 or pos.shape != (h.shape[0],) or neg.dim() != 2 or neg.shape[0] != h.shape[0]:
+        raise ValueError(f"h [M, d], pos [M] and neg [M, n] required, got {tuple(h.shape)}, "
+                         f"{tuple(pos.shape)} and {tuple(neg.shape)}")
+    n = neg.shape[1]
+    if not 1 <= n <= kernels.MAX_NEGATIVES:
+        raise ValueError(f"n = {n} negatives per row: expected 1 .. {kernels.MAX_NEGATIVES}")
+    pos, neg = pos.to(torch.int64), neg.to(torch.int64)
+    if not kernels.pair_loss_supported(h, table):
+        loss = pair_loss_reference(h, table, pos, neg, gamma)
+        return (loss, ((pos >= 0)[:, None] & (neg >= 0)).sum()) if return_live else loss
+    loss, n_live = _PairLoss.apply(h, table, pos, neg, float(gamma))
+    return (loss, n_live) if return_live else loss
 
 
 def full_sort_scores(seq: torch.Tensor, table: torch.Tensor) -> torch.Tensor:

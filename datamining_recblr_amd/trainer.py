@@ -66,7 +66,9 @@ def fit(model, data, env: DistEnv, epochs: int = 100, batch_size: int = 2048,
     """Train with early stopping; returns best valid / test metrics.
     dense: all-position training — the loader yields one row per user window
     (SequentialLoader(dense=True)) and the model, built with
-    train_all_positions, takes the loss at every position of it."""
+    train_all_positions, takes the loss at every position of it (the CE, or
+    with dense_negatives the sampled pairwise loss).  A loss_type 'BPR' model
+    gets one sampled negative per row from the loader (NEG_ITEM_ID)."""
     if dense and not getattr(model, "train_all_positions", False):
         raise ValueError("fit(dense=True) needs a model built with train_all_positions=True")
     step = wrap_ddp(model, env)
@@ -76,7 +78,8 @@ def fit(model, data, env: DistEnv, epochs: int = 100, batch_size: int = 2048,
     opt = make_adam(model.parameters(), lr=lr, weight_decay=weight_decay)
     loader = SequentialLoader(data, "train", batch_size=batch_size, shuffle=True, seed=seed,
                               rank=env.rank, world=env.world_size, drop_last=env.distributed,
-                              dense=dense)
+                              dense=dense,
+                              negatives=getattr(model, "loss_type", None) == "BPR")
     best, best_state, bad, history = -1.0, None, 0, []
     for ep in range(epochs):
         model.train()

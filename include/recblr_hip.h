@@ -50,7 +50,8 @@
  * const char*; integer constants as one-line #defines.  A new entry point is
  * declared here and defined in csrc/capi.hip, and RB_ABI_VERSION is bumped.
  * The all-position training loss's entry points (the same library, the same
- * version) are declared in recblr_dense.h.
+ * version) are declared in recblr_dense.h, its sampled pairwise loss's in
+ * recblr_pairs.h.
  */
 #ifndef RECBLR_HIP_H
 #define RECBLR_HIP_H
@@ -74,7 +75,7 @@ typedef uint16_t rb_bf16;
 #define RB_TILE 16
 
 /* ABI version; bumped on any signature change.  rb_version() returns it. */
-#define RB_ABI_VERSION 46
+#define RB_ABI_VERSION 47
 int rb_version(void);
 
 /* Human-readable description of the last error on the calling thread. */

@@ -1,0 +1,90 @@
+/*
+ * recblr_pairs.h — C-ABI of the sampled pairwise (BPR) loss of all-position
+ * training of the MI355X (gfx950) RecBLR encoder.  Part of the product
+ * library (libdmrecblr.so, RB_ABI_VERSION of recblr_hip.h); same conventions
+ * as recblr_hip.h: raw device pointers, int64 sizes, a hipStream_t passed as
+ * void*, nothing allocates or synchronises, arguments are checked before any
+ * HIP call, 0 / RB_EINVAL / hipError_t returns, rb_last_error_string() for
+ * the message.  Plain C declarations, one per ';' — the Python binding
+ * (datamining_recblr_amd/_lib.py) parses this header as it parses
+ * recblr_hip.h.  Defined in csrc/capi.hip; kernels in csrc/pair_loss.hip and
+ * csrc/embedding.hip.
+ *
+ * Every packed row (RecBLR.forward_all, recblr_dense.h) is scored against its
+ * target and n sampled negatives only: (2 + n) rows of d floats per position
+ * instead of a sweep over the item table.
+ */
+#ifndef RECBLR_PAIRS_H
+#define RECBLR_PAIRS_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Negative sampling.  item_seq [B, L] (row stride seq_rs) right-padded rows,
+ * lengths [B] (clamped to [1, L]), pos_items [B]; all device int64.  The seen
+ * set of row b is item_seq[b, :len_b] and pos_items[b] — the row's window,
+ * not the user's whole history.  The negative of (b, t, j), j < n_neg, is
+ * uniform over [first_item, V) minus that set:
+ *   attempt a = 0 .. 15 takes word a % 4 of Philox4x32-10(counter = (b, t, j,
+ *   a / 4), key = seed) and maps it to first_item + mulhi(word, V -
+ *   first_item); the first attempt that is not seen wins; after 16 rejections
+ *   the ids above the 16th candidate are walked upward, cyclically through
+ *   [first_item, V), to the first unseen one; -1 when every id is seen.
+ * offsets [B + 1] and inv [B] given (rb_pack_plan's layout): every position
+ * t < len_b writes neg[(offsets[inv[b]] + t) * n_neg + j] — packed order, rows
+ * < ntok — and the rows [ntok, m_pad) are filled with -1.  Both NULL (ntok =
+ * m_pad = B): only t = len_b - 1 is drawn, into row b; these are exactly the
+ * dense call's rows at each sequence's last position.  A pure function of its
+ * arguments; no atomics.  Needs 1 <= n_neg <= 16, 0 <= first_item < V < 2^31,
+ * L <= 8191; an index outside its range writes nothing. */
+int rb_sample_negatives(const int64_t* item_seq, int64_t seq_rs, const int64_t* lengths,
+                        const int64_t* pos_items, const int64_t* offsets, const int64_t* inv,
+                        int64_t B, int64_t L, int64_t n_neg, int64_t first_item, int64_t V,
+                        uint64_t seed, int64_t ntok, int64_t m_pad, int64_t* neg, void* stream);
+
+/* Bytes of rb_pair_loss_fwd's workspace for M rows (0 for M <= 0). */
+int64_t rb_pair_loss_workspace(int64_t M);
+
+/* h [M, d] (row stride ldh), table [V, d], pos [M] (rb_next_item_targets: -1
+ * an ignored row), neg [M, n_neg] (-1 an ignored pair).  For every live pair
+ *   x = h_r . table[pos_r] - h_r . table[neg_rj]    -> diff [M, n_neg] (0 when ignored)
+ *   l = -log(gamma + sigmoid(x))
+ * loss[0] = sum l / max(n_live, 1), n_live[0] = live pairs (device scalars,
+ * no host sync); the sum runs over per-workgroup partials in workgroup order.
+ * An id outside [-1, V) gives a NaN loss (it is never dereferenced).  d a
+ * multiple of 4 up to 512; h, table 16-B aligned with ldh % 4 == 0. */
+int rb_pair_loss_fwd(const float* h, int64_t ldh, const float* table, const int64_t* pos,
+                     const int64_t* neg, int64_t M, int64_t d, int64_t V, int64_t n_neg,
+                     float gamma, float* diff, float* loss, int64_t* n_live, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
+/* With c_rj = dloss[0] / max(n_live[0], 1) * (-s (1 - s) / (gamma + s)), s =
+ * sigmoid(diff_rj), and c_rj = 0 for an ignored pair:
+ *   dh [M, d] (contiguous)  dh_r = sum_j c_rj (table[pos_r] - table[neg_rj])
+ *   coef [(1 + n_neg) * M]  [ sum_j c_rj | -c_r0 | -c_r1 | ... ], one block of M
+ *                           per id column: position p = k * M + r of the ids
+ *                           [pos | neg_0 | neg_1 ...] has the gradient row
+ *                           coef[p] * h_r (rb_embedding_bwd_apply_scaled). */
+int rb_pair_loss_bwd(const float* table, const int64_t* pos, const int64_t* neg,
+                     const float* diff, const float* dloss, const int64_t* n_live, int64_t M,
+                     int64_t d, int64_t V, int64_t n_neg, float gamma, float* dh, float* coef,
+                     void* stream);
+
+/* rb_embedding_bwd_apply (recblr_hip.h; same plan, same workspace, same sums)
+ * with position p's gradient row read as coef[p] * src[p mod src_rows] (src
+ * [src_rows, d], row stride src_ld) instead of grad[p]: the M gradient rows are
+ * never stored.  Bitwise rb_embedding_bwd_apply on the materialised rows. */
+int rb_embedding_bwd_apply_scaled(const float* src, int64_t src_ld, int64_t src_rows,
+                                  const float* coef, int64_t M, int64_t d, int64_t V,
+                                  int64_t padding_idx, float* dweight, void* workspace,
+                                  int64_t workspace_bytes, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* RECBLR_PAIRS_H */
