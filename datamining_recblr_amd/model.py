@@ -622,3 +622,24 @@ class RecBLR(SequentialRecommender):
         from .session import recommend
 
         return recommend(self, state, items, slots, k, exclude_seen, first_item)
+
+    def session_park(self, state, slots=None, release: bool = False, out=None):
+        """The slots' sessions as rows of an int32 [B, state.blob_words] blob,
+        one launch (session.park); release=True also frees the slots."""
+        from .session import park
+
+        return park(state, slots, release, out)
+
+    def session_resume(self, state, blob, slots=None):
+        """Put parked sessions (session_park's rows, or their host copy) into
+        the slots; returns the rows' statuses (session.resume)."""
+        from .session import resume
+
+        return resume(state, blob, slots)
+
+    def session_exchange(self, state, blob, slots=None, out=None):
+        """Park the slots' sessions and resume the rows of blob into the same
+        slots in one launch; returns the outgoing blob (session.exchange)."""
+        from .session import exchange
+
+        return exchange(state, blob, slots, out)

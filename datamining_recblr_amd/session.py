@@ -52,11 +52,22 @@ per call, before the encoder launches).  ``state.history()`` reads it oldest
 first, and ``recommend`` is the serving call it is for: a step or an append,
 then ``scoring.top_items`` with the slots' rings as the seen-item lists.
 ``record_reference`` is that kernel's restatement in torch ops.
+
+A live session can leave its slot and come back later: ``park`` writes the
+slots' whole state (h, conv history, count, out, item ring) as rows of an
+int32 ``[B, W]`` blob in one launch (rb_session_transfer,
+session/session_transfer.hip; the format is documented in
+session/recblr_session.h), ``resume`` puts such rows into any slots of a state
+of the same shape, ``exchange`` does both at once.  A row carries
+``SessionState.blob_tag``; a row with another tag, a negative count or a ring
+entry outside ``[-1, V)`` is refused as a whole (``BAD_BLOB``) and its slot left
+alone.  ``transfer_reference`` is the kernel's restatement in torch ops.
 """
 from __future__ import annotations
 
 import ctypes
 import os
+import zlib
 
 import torch
 import torch.nn.functional as F
@@ -67,13 +78,17 @@ from .recurrence import pad_prefix_state, pow2_pad_len
 
 __all__ = ["SessionState", "EncoderParams", "step", "step_reference", "prefill",
            "capture_reference", "append", "append_reference", "record_reference", "recommend",
-           "kernel_supports", "STEPPED", "NO_EVENT", "BAD_ITEM", "BAD_SLOT"]
+           "kernel_supports", "STEPPED", "NO_EVENT", "BAD_ITEM", "BAD_SLOT", "park", "resume",
+           "exchange", "transfer_reference", "MOVED", "BAD_BLOB"]
 
 _header = _lib._read(os.path.join(_lib._HERE, "session", "recblr_session.h"))
 STEPPED = _lib._define(_header, "RB_SESSION_STEPPED")
 NO_EVENT = _lib._define(_header, "RB_SESSION_NO_EVENT")
 BAD_ITEM = _lib._define(_header, "RB_SESSION_BAD_ITEM")
 BAD_SLOT = _lib._define(_header, "RB_SESSION_BAD_SLOT")
+MOVED = _lib._define(_header, "RB_SESSION_MOVED")
+BAD_BLOB = _lib._define(_header, "RB_SESSION_BAD_BLOB")
+BLOB_FORMAT = _lib._define(_header, "RB_SESSION_BLOB_FORMAT")
 MAX_LAYERS = _lib._define(_header, "RB_SESSION_MAX_LAYERS")
 MAX_LDS = _lib._define(_header, "RB_SESSION_MAX_LDS")
 TILE = _lib._define(_header, "RB_SESSION_TILE")   # events per rb_session_append launch
@@ -188,7 +203,54 @@ class SessionState:
         self.items = (torch.empty((N, int(history)), device=p.device, dtype=torch.int64)
                       if history else None)
         self._plan = None
+        self._transfer_plan = None
         self.reset()
+
+    @property
+    def blob_words(self) -> int:
+        """W, the 4-byte words of one parked session of this state
+        (rb_session_blob_words: the one statement of the sum)."""
+        _, d, H, K, layers, use_conv, _ = self.shape
+        S = 0 if self.items is None else self.items.shape[1]
+        W = _lib.load_session().rb_session_blob_words(d, H, K, layers, S, int(use_conv))
+        if W < 0:
+            raise ValueError(f"SessionState.blob_words: no blob format for the shape {self.shape}")
+        return W
+
+    @property
+    def blob_tag(self) -> int:
+        """Word 0 of this state's parked rows, as the int32 it is stored as:
+        the CRC-32 of the format number, ``shape``, the ring length S and
+        ``seq_len``, bit 0 forced on so it is never 0 (0 marks an invalid row).
+        It guards the shape only: a blob of another model with the same shape
+        (other weights) carries the same tag."""
+        S = 0 if self.items is None else self.items.shape[1]
+        text = repr((BLOB_FORMAT, tuple(int(v) for v in self.shape), int(S), self.seq_len))
+        tag = zlib.crc32(text.encode()) | 1
+        return tag - (1 << 32) if tag >= 1 << 31 else tag
+
+    def blob_layout(self) -> dict:
+        """name -> (first word, word count) of a parked row's parts, in row
+        order: ``tag``, ``reserved``, ``count`` (int64, low word first), ``out``,
+        per layer ``h{i}`` and ``conv{i}`` (absent without a conv history),
+        ``items`` (the ring, int64 each; absent with history=0) and ``pad``
+        (zeros up to a multiple of 4 words; absent when there is none)."""
+        _, d, H, K, layers, use_conv, _ = self.shape
+        S = 0 if self.items is None else self.items.shape[1]
+        parts = [("tag", 1), ("reserved", 1), ("count", 2), ("out", d)]
+        for i in range(layers):
+            parts.append((f"h{i}", H))
+            if use_conv and K > 1:
+                parts.append((f"conv{i}", (K - 1) * H))
+        if S:
+            parts.append(("items", 2 * S))
+        layout, w = {}, 0
+        for name, n in parts:
+            layout[name] = (w, n)
+            w += n
+        if w % 4:
+            layout["pad"] = (w, 4 - w % 4)
+        return layout
 
     @torch.no_grad()
     def reset(self, slots=None) -> None:
@@ -949,3 +1011,233 @@ def recommend(model, state: SessionState, items=None, slots=None, k: int = 10,
     ids.masked_fill_(dead[:, None], -1)
     scores.masked_fill_(dead[:, None], float("-inf"))
     return ids, scores
+
+
+# ---- parked sessions ------------------------------------------------------------
+def _blob_check(state: SessionState, blob, B, name: str, who: str, device_ok) -> None:
+    """A blob argument is int32 [B, W], contiguous, on one of device_ok."""
+    if not isinstance(blob, torch.Tensor) or blob.dtype != torch.int32:
+        raise ValueError(f"{who}: {name} must be an int32 tensor")
+    if blob.dim() != 2 or blob.shape[1] != state.blob_words:
+        raise ValueError(f"{who}: {name} must be [B, {state.blob_words}] (state.blob_words), "
+                         f"got {tuple(blob.shape)}")
+    if B is not None and blob.shape[0] != B:
+        raise ValueError(f"{who}: slots and {name} must have the same length "
+                         f"({B} slots, {blob.shape[0]} rows)")
+    if not blob.is_contiguous():
+        raise ValueError(f"{who}: {name} must be contiguous")
+    if blob.device not in device_ok:
+        raise ValueError(f"{who}: {name} is on {blob.device}, the state on {state.device}")
+
+
+def _overlap(a: torch.Tensor, b: torch.Tensor) -> bool:
+    if a.device != b.device or not a.numel() or not b.numel():
+        return False
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * 4 and b0 < a0 + a.numel() * 4
+
+
+def _transfer_rows(state: SessionState, slots, blob_in, out, who: str, check_slots: bool = True):
+    """A transfer call's rows: ``(slots [B] or None, blob_in on the state's
+    device or None, B)``, with the blobs validated (ValueError)."""
+    if slots is not None:
+        slots = (_slot_tensor(slots, state) if check_slots else
+                 torch.as_tensor(slots, dtype=torch.int64).reshape(-1).to(state.device))
+    B = None if slots is None else slots.numel()
+    if blob_in is not None:
+        _blob_check(state, blob_in, B, "blob", who, (state.device, torch.device("cpu")))
+        B = blob_in.shape[0]
+        blob_in = blob_in.to(state.device)      # a host blob: one copy to the device
+    elif B is None:
+        B = state.capacity
+    if B == 0:
+        raise ValueError(f"{who}: no row to move")
+    if slots is None and B > state.capacity:
+        raise ValueError(f"{who}: {B} rows for a state of {state.capacity} slots")
+    if out is not None:
+        _blob_check(state, out, B, "out", who, (state.device,))
+        if blob_in is not None and _overlap(blob_in, out):
+            raise ValueError(f"{who}: the incoming blob and out overlap")
+    return slots, blob_in, B
+
+
+def _blob_words(t: torch.Tensor, B: int) -> torch.Tensor:
+    """Rows of a state tensor as their int32 words [B, n], bit for bit."""
+    return t.reshape(B, -1).contiguous().view(torch.int32)
+
+
+@torch.no_grad()
+def transfer_reference(state: SessionState, slots=None, blob_in=None, want_out: bool = True,
+                       release: bool = False):
+    """rb_session_transfer in plain torch ops, on the state's device (CPU
+    included): ``(blob_out int32 [B, W] or None, status int32 [B])``; the
+    status is also left in ``state.status``.  Blob contents and status are
+    bit-identical to the kernel's.
+
+    slots: int64 [B], unique (None: slot b); a slot outside [0, N) is masked,
+    not refused: its outgoing row is all zeros, its status BAD_SLOT, and
+    nothing of the state is touched.  want_out: build the outgoing blob from
+    the slots' state as it stands before the call (the row format:
+    session/recblr_session.h, ``SessionState.blob_layout``).  blob_in: rows to
+    put into the slots; a row is applied as a whole (MOVED) when its word 0 is
+    ``state.blob_tag``, its count >= 0 and every ring entry in [-1, V), and
+    otherwise leaves the slot untouched (BAD_BLOB).  release (without blob_in):
+    the slots are left as ``state.reset(slots)`` leaves them, with the h0 the
+    state holds."""
+    who = "transfer_reference"
+    if blob_in is None and not want_out and not release:
+        raise ValueError(f"{who}: nothing to do: give blob_in, want_out or release")
+    if blob_in is not None and release:
+        raise ValueError(f"{who}: release cannot be combined with an incoming blob")
+    slots, blob_in, B = _transfer_rows(state, slots, blob_in, None, who, check_slots=False)
+    dev, N, V, W = state.device, state.capacity, state.shape[0], state.blob_words
+    if slots is None:
+        slots = torch.arange(B, device=dev)
+    slot_ok = ~_bad_slot(state, slots)
+    safe = slots.clamp(0, N - 1)
+    lay, tag = state.blob_layout(), state.blob_tag
+    convs = [(i, c) for i, c in enumerate(state.conv) if c is not None]
+    status = torch.full((B,), MOVED, device=dev, dtype=torch.int32)
+    blob_out = None
+    if want_out:
+        head = torch.tensor([tag, 0], device=dev, dtype=torch.int32).expand(B, 2)
+        parts = [head, _blob_words(state.count[safe], B), _blob_words(state.out[safe], B)]
+        for i, h in enumerate(state.h):
+            parts.append(_blob_words(h[safe], B))
+            if state.conv[i] is not None:
+                parts.append(_blob_words(state.conv[i][safe], B))
+        if state.items is not None:
+            parts.append(_blob_words(state.items[safe], B))
+        used = sum(p.shape[1] for p in parts)
+        parts.append(torch.zeros((B, W - used), device=dev, dtype=torch.int32))
+        blob_out = torch.cat(parts, 1)
+        blob_out[~slot_ok] = 0
+    if blob_in is not None:
+        def part(name, dtype):
+            w0, n = lay[name]
+            return blob_in[:, w0:w0 + n].contiguous().view(dtype)
+
+        count_in = part("count", torch.int64)[:, 0]
+        valid = slot_ok & (blob_in[:, 0] == tag) & (count_in >= 0)
+        if state.items is not None:
+            ring_in = part("items", torch.int64)
+            valid &= ((ring_in >= -1) & (ring_in < V)).all(1)
+        idx = slots[valid]
+        state.count[idx] = count_in[valid]
+        state.out[idx] = part("out", torch.float32)[valid]
+        for i, h in enumerate(state.h):
+            h[idx] = part(f"h{i}", torch.float32)[valid]
+        for i, c in convs:
+            c[idx] = part(f"conv{i}", torch.float32)[valid].reshape(-1, *c.shape[1:])
+        if state.items is not None:
+            state.items[idx] = ring_in[valid]
+        status[slot_ok & ~valid] = BAD_BLOB
+    elif release:
+        idx = slots[slot_ok]
+        for h, h0 in zip(state.h, state.h0):
+            h[idx] = h0
+        for _, c in convs:
+            c[idx] = 0.0
+        state.count[idx] = 0
+        state.out[idx] = 0.0
+        if state.items is not None:
+            state.items[idx] = -1
+    status[~slot_ok] = BAD_SLOT
+    state.status = status
+    return blob_out, status
+
+
+def _transfer_layers(state: SessionState):
+    """The rb_session_layer array rb_session_transfer reads: h, conv_state and
+    h0 only (no weights), rebuilt only when a tensor has moved."""
+    tensors = [dict(h0=h0, h=h, conv_state=c) for h0, h, c in zip(state.h0, state.h, state.conv)]
+    key = tuple(t.data_ptr() if t is not None else 0 for row in tensors for t in row.values())
+    if state._transfer_plan is not None and state._transfer_plan[0] == key:
+        return state._transfer_plan[1]
+    arr = (_Layer * len(tensors))()
+    for dst, row in zip(arr, tensors):
+        for f, t in row.items():
+            setattr(dst, f, t.data_ptr() if t is not None else None)
+    state._transfer_plan = (key, arr)
+    return arr
+
+
+def _transfer_kernel(state: SessionState, slots, blob_in, blob_out, status, release: bool) -> None:
+    """The one launch (rb_session_transfer)."""
+    V, d, H, K, n_layers, use_conv, _ = state.shape
+    ptr = lambda t: t.data_ptr() if t is not None else None     # noqa: E731
+    S = 0 if state.items is None else state.items.shape[1]
+    _lib.call_session(
+        "rb_session_transfer", ctypes.addressof(_transfer_layers(state)), n_layers,
+        state.count.data_ptr(), state.out.data_ptr(), ptr(state.items), ptr(slots), ptr(blob_in),
+        ptr(blob_out), status.data_ptr(), state.blob_tag, int(release), status.numel(),
+        state.capacity, V, d, H, K, S, int(use_conv), state.blob_words,
+        kernels._stream(state.out))
+
+
+def _transfer(state: SessionState, slots, blob_in, want_out: bool, release: bool, out, who: str):
+    """park / resume / exchange: (blob_out or None, status)."""
+    slots, blob_in, B = _transfer_rows(state, slots, blob_in, out, who)
+    _, d, H = state.shape[:3]
+    if state.device.type != "cuda" or d % 4 or H % 4:
+        blob_out, status = transfer_reference(state, slots, blob_in, want_out, release)
+        if out is not None and blob_out is not None:
+            blob_out = out.copy_(blob_out)
+        return blob_out, status
+    blob_out = None
+    if want_out:
+        blob_out = out if out is not None else torch.empty(
+            (B, state.blob_words), device=state.device, dtype=torch.int32)
+    status = torch.empty((B,), device=state.device, dtype=torch.int32)
+    with torch.cuda.device(state.device):
+        _transfer_kernel(state, slots, blob_in, blob_out, status, release)
+    state.status = status
+    return blob_out, status
+
+
+@torch.no_grad()
+def park(state: SessionState, slots=None, release: bool = False, out=None) -> torch.Tensor:
+    """Take the slots' sessions out of the state: one launch writes each
+    slot's whole state (count, out, per layer h and the conv history, the item
+    ring) as a row of the returned int32 ``[B, W]`` blob (``W =
+    state.blob_words``) on the state's device; ``blob.cpu()`` is the host copy
+    a service stores.  slots None: every slot.  release=True also leaves the
+    slots as ``state.reset(slots)`` does (free for the next session); otherwise
+    the state is only read.  out: a buffer to write into (int32 [B, W],
+    contiguous, on the state's device).
+
+    The rows carry ``state.blob_tag``, which guards the model *shape* (and the
+    window and ring length), not its weights: resuming a blob under a model
+    of the same shape and other weights is the caller's error and goes
+    undetected.  slots are ``step``'s: a list is checked; a device tensor costs
+    no sync, must be unique, and a slot outside the state yields an all-zero
+    row and BAD_SLOT in ``state.status`` (MOVED for the others).  A state on the
+    CPU, or with d or H no multiple of 4, runs transfer_reference."""
+    return _transfer(state, slots, None, True, release, out, "park")[0]
+
+
+@torch.no_grad()
+def resume(state: SessionState, blob, slots=None) -> torch.Tensor:
+    """Put parked sessions back: row b of blob (int32 [B, W], on the state's
+    device or the CPU, then copied over) replaces the whole state of slot
+    slots[b] (None: slot b), which need not be the slot it was parked from.
+    Returns the rows' statuses (also ``state.status``): MOVED, BAD_SLOT, or
+    BAD_BLOB for a row that is not a parked session of this state's shape
+    (another tag, e.g. the all-zero row of a bad park), has a negative count
+    or a ring entry outside [-1, V); such a row leaves its slot untouched, the
+    other rows of the call are applied.  One launch, no host sync."""
+    if blob is None:
+        raise ValueError("resume: blob must be an int32 tensor")
+    return _transfer(state, slots, blob, False, False, None, "resume")[1]
+
+
+@torch.no_grad()
+def exchange(state: SessionState, blob, slots=None, out=None) -> torch.Tensor:
+    """park and resume in one launch: the slots' present sessions go out (the
+    returned blob, the state as it stood before the call), the rows of blob
+    come in.  A refused incoming row (``state.status``: BAD_BLOB) still parks
+    the slot's session and leaves it in place.  blob and out must not
+    overlap."""
+    if blob is None:
+        raise ValueError("exchange: blob must be an int32 tensor")
+    return _transfer(state, slots, blob, True, False, out, "exchange")[0]

@@ -4,7 +4,8 @@
  * slot in one launch, rb_session_append by up to 16 consecutive events per
  * slot; rb_session_capture reads a layer's session state off its forward
  * over stored histories; rb_session_record keeps the ring of the last item
- * ids a slot consumed (python: datamining_recblr_amd/session.py).  Its own
+ * ids a slot consumed; rb_session_transfer parks a slot's whole state as one
+ * row of words and resumes it (python: datamining_recblr_amd/session.py).  Its own
  * library, beside the product library, as the probe and experimental
  * libraries are ("Stateful sessions").  Same conventions as the
  * boundary (include/recblr_hip.h): raw device pointers, int status (0 = ok,
@@ -29,6 +30,11 @@ extern "C" {
 #define RB_SESSION_STEPPED 1
 #define RB_SESSION_BAD_ITEM (-1)
 #define RB_SESSION_BAD_SLOT (-2)
+/* row status written by rb_session_transfer (with RB_SESSION_BAD_SLOT) */
+#define RB_SESSION_MOVED 2
+#define RB_SESSION_BAD_BLOB (-3)
+/* the number the blob format below carries in its tag */
+#define RB_SESSION_BLOB_FORMAT 1
 
 /* One RecurrentLayer (RecBLR.py:124-145): its parameters (host struct of
  * device pointers, fp32, contiguous, 16-byte aligned) and the per-slot state
@@ -174,6 +180,71 @@ int rb_session_capture(const float* u, int64_t u_rs, const float* xc, int64_t xc
 int rb_session_record(const int64_t* items, int64_t B, int64_t W, const int64_t* slots,
                       const int64_t* count, int64_t* ring, int64_t* seen,
                       int64_t N, int64_t S, int64_t V, void* stream);
+
+/* Parked sessions.  A slot's whole state leaves the session state as one row
+ * of 4-byte words (a blob row; python: a row of an int32 [B, W] tensor) and
+ * comes back later, into any slot of a state of the same shape.  Everything is
+ * copied bit for bit, nothing is converted.  The row, W = row_words words:
+ *   word 0          the tag: the caller's 32-bit fingerprint of the format
+ *                   number (RB_SESSION_BLOB_FORMAT) and the model shape, never
+ *                   0 (python: SessionState.blob_tag); 0 marks an invalid row
+ *   word 1          0 (reserved)
+ *   words 2-3       count[slot], int64, low word first
+ *   next d          out[slot]
+ *   per layer, in   h[slot] (H words), then conv_state[slot] ((K - 1) H words,
+ *   order           oldest row first; absent without has_conv or with K == 1)
+ *   next 2 S        the item ring ring[slot, 0 .. S) in ring order (raw
+ *                   positions), int64 each, low word first; absent with S == 0
+ *   pad             zeros up to a multiple of 4 words
+ * rb_session_blob_words returns W (RB_EINVAL for d or H outside [1, 2^20], K
+ * outside [1, 8], n_layers outside [1, 8] or S outside [0, 2^31)).  The
+ * format holds for every d and H; rb_session_transfer takes multiples of 4. */
+int64_t rb_session_blob_words(int64_t d, int64_t H, int64_t K, int64_t n_layers, int64_t S,
+                              int has_conv);
+
+/* Park, resume or exchange B sessions in one launch.  Call row b names slot
+ * slots[b] (slots NULL: slot b; slots unique, as for the step).  Of each
+ * rb_session_layer only h, conv_state and h0 are read: the weight pointers
+ * may be NULL.  ring [N, S] is the item ring (NULL with S == 0).
+ *   blob_out given (park): the slot's state is written to row b of blob_out
+ *   [B, row_words] in the format above, with `tag` in word 0.  A slot outside
+ *   [0, N) gives an all-zero row and status RB_SESSION_BAD_SLOT.
+ *   blob_in given (resume): row b of blob_in is checked as a whole: word 0
+ *   must equal tag, count must be >= 0 and every ring entry must lie in
+ *   [-1, V).  A row that passes replaces the slot's h, conv_state, count, out
+ *   and ring (status RB_SESSION_MOVED); a row that fails leaves the slot
+ *   untouched (status RB_SESSION_BAD_BLOB).
+ *   both (exchange): the old state goes out and the new one comes in; each
+ *   element's old value is read before the same thread writes its new one,
+ *   so row b of blob_out is the state before the call whatever blob_in holds
+ *   (a rejected row still parks the old state).  blob_in and blob_out must
+ *   not overlap.
+ *   release != 0 (blob_in NULL): after the export the slot is left as a reset
+ *   leaves it: h = h0 (zeros when h0 is NULL), conv_state 0, count 0, out 0,
+ *   ring -1.  release with blob_in, and neither blob without release, are
+ *   argument errors.
+ * status [B] int32 (optional): RB_SESSION_MOVED for a row that was parked,
+ * released or resumed, RB_SESSION_BAD_SLOT, or RB_SESSION_BAD_BLOB (a bad
+ * slot wins: its blob row is not examined).
+ * The kernel's rules: every slot is range-checked before an address is formed
+ * from it; a row's validity is decided (from blob_in's header and all of its
+ * ring) before the first store to its slot; every branch on slot or validity
+ * is wave-uniform;
+ * no atomics and no scratch; no location is written twice in a launch; no
+ * other slot is written.  One workgroup of 256 threads per call row (a row is
+ * 12 to a few thousand words: up to a few 16-byte sweeps of the workgroup).
+ * The float parts move in 16-byte accesses, so d and H are multiples of 4,
+ * out, h, conv_state, h0 and both blobs 16-byte aligned and row_words a
+ * multiple of 4 (it must equal rb_session_blob_words); the ring and count
+ * move in 8-byte accesses, as a ring row is only 8-byte aligned when S is odd.
+ * Status and argument checks come before any HIP call.  B, N, V >= 1, S >= 0,
+ * all < 2^31; K in [1, 8]; n_layers in [1, RB_SESSION_MAX_LAYERS]. */
+int rb_session_transfer(const rb_session_layer* layers, int64_t n_layers, int64_t* count,
+                        float* out, int64_t* ring, const int64_t* slots,
+                        const int32_t* blob_in, int32_t* blob_out, int32_t* status,
+                        int tag, int release, int64_t B, int64_t N, int64_t V, int64_t d,
+                        int64_t H, int64_t K, int64_t S, int has_conv, int64_t row_words,
+                        void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,7 @@
 // session_capi.hip — the extern "C" entry points of the session library
 // (recblr_session.h): argument checks, then the launchers in session_step.hip,
-// session_append.hip, session_capture.hip and session_record.hip.
+// session_append.hip, session_capture.hip, session_record.hip and
+// session_transfer.hip.
 // Built with hidden visibility, so its error helpers (rb::fail,
 // rb::launch_status) are its own and never interpose the product library's.
 #include "../csrc/common.h"
@@ -47,6 +48,13 @@ int launch_session_capture(const float* u, int64_t u_rs, const float* xc, int64_
 int launch_session_record(const int64_t* items, int64_t B, int64_t W, const int64_t* slots,
                           const int64_t* count, int64_t* ring, int64_t* seen, int64_t N, int S,
                           int64_t V, hipStream_t st);
+int64_t session_blob_words(int64_t d, int64_t H, int64_t K, int64_t n_layers, int64_t S,
+                           bool has_conv);
+int launch_session_transfer(const rb_session_layer* layers, int n_layers, int64_t* count,
+                            float* out, int64_t* ring, const int64_t* slots,
+                            const int32_t* blob_in, int32_t* blob_out, int32_t* status, int tag,
+                            int release, int64_t B, int64_t N, int64_t V, int d, int H, int K,
+                            int64_t S, bool has_conv, int64_t row_words, hipStream_t st);
 }  // namespace rb
 
 using namespace rb;
@@ -177,6 +185,65 @@ RB_EXPORT int rb_session_record(const int64_t* items, int64_t B, int64_t W, cons
     return fail("rb_session_record: B, W, N, S and V must be < 2^31");
   return launch_session_record(items, B, W, slots, count, ring, seen, N, (int)S, V,
                                reinterpret_cast<hipStream_t>(stream));
+}
+
+// whether (d, H, K, n_layers, S) is a shape rb_session_blob_words sizes
+static bool blob_shape_ok(int64_t d, int64_t H, int64_t K, int64_t n_layers, int64_t S) {
+  return d > 0 && H > 0 && d <= (1 << 20) && H <= (1 << 20) && K >= 1 && K <= 8 &&
+         n_layers >= 1 && n_layers <= RB_SESSION_MAX_LAYERS && S >= 0 && S < (1LL << 31);
+}
+
+RB_EXPORT int64_t rb_session_blob_words(int64_t d, int64_t H, int64_t K, int64_t n_layers,
+                                        int64_t S, int has_conv) {
+  if (!blob_shape_ok(d, H, K, n_layers, S)) return RB_EINVAL;
+  return session_blob_words(d, H, K, n_layers, S, has_conv != 0);
+}
+
+RB_EXPORT int rb_session_transfer(const rb_session_layer* layers, int64_t n_layers, int64_t* count,
+                        float* out, int64_t* ring, const int64_t* slots,
+                        const int32_t* blob_in, int32_t* blob_out, int32_t* status,
+                        int tag, int release, int64_t B, int64_t N, int64_t V, int64_t d,
+                        int64_t H, int64_t K, int64_t S, int has_conv, int64_t row_words,
+                        void* stream) {
+  if (!layers || !count || !out) return fail("rb_session_transfer: null pointer");
+  if (!blob_in && !blob_out && !release)
+    return fail("rb_session_transfer: nothing to do: give blob_in, blob_out or release");
+  if (blob_in && release)
+    return fail("rb_session_transfer: release cannot be combined with blob_in");
+  if (n_layers < 1 || n_layers > RB_SESSION_MAX_LAYERS)
+    return fail("rb_session_transfer: n_layers must be in [1, 8]");
+  if (K < 1 || K > 8) return fail("rb_session_transfer: conv kernel size K must be in [1, 8]");
+  if (d <= 0 || H <= 0 || d % 4 || H % 4 || d > (1 << 20) || H > (1 << 20))
+    return fail("rb_session_transfer: d and H must be positive multiples of 4");
+  if (B <= 0 || N <= 0 || V <= 0) return fail("rb_session_transfer: B, N and V must be positive");
+  if (S < 0) return fail("rb_session_transfer: S must be >= 0");
+  if (B >= (1LL << 31) || N >= (1LL << 31) || V >= (1LL << 31) || S >= (1LL << 31))
+    return fail("rb_session_transfer: B, N, V and S must be < 2^31");
+  if (S > 0 && !ring) return fail("rb_session_transfer: null ring with S > 0");
+  if (row_words != session_blob_words(d, H, K, n_layers, S, has_conv != 0))
+    return fail("rb_session_transfer: row_words is not rb_session_blob_words of this shape");
+  const bool hist = has_conv && K > 1;
+  for (int64_t i = 0; i < n_layers; ++i) {
+    const rb_session_layer& L = layers[i];
+    if (!L.h || (hist && !L.conv_state))
+      return fail("rb_session_transfer: null state pointer in a layer");
+    if (!aligned16(L.h) || !aligned16(L.conv_state) || !aligned16(L.h0))
+      return fail("rb_session_transfer: h, conv_state and h0 must be 16-byte aligned");
+  }
+  // the float parts and the blob rows move 16 bytes per lane
+  if (!aligned16(out) || !aligned16(blob_in) || !aligned16(blob_out))
+    return fail("rb_session_transfer: out, blob_in and blob_out must be 16-byte aligned");
+  if (blob_in && blob_out) {
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(blob_in);
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(blob_out);
+    const uintptr_t bytes = (uintptr_t)B * (uintptr_t)row_words * 4;
+    if (i0 < o0 + bytes && o0 < i0 + bytes)
+      return fail("rb_session_transfer: blob_in and blob_out overlap");
+  }
+  return launch_session_transfer(layers, (int)n_layers, count, out, ring, slots, blob_in,
+                                 blob_out, status, tag, release, B, N, V, (int)d, (int)H, (int)K,
+                                 S, has_conv != 0, row_words,
+                                 reinterpret_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

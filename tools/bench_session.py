@@ -31,6 +31,14 @@ launch; (b) the same result without the ring: session_step, a caller-kept
 index_select of the rows' lists and top_items(exclude=...); (c) session_step
 and top_items without exclusion, so (a) - (c) is what the bookkeeping costs.
 
+--park runs only a fifth leg (park_rows): taking B of 4,096 live sessions
+(S = 200 remembered items, 2,580 words each) out of the state and putting B
+others in: session.park, session.resume and session.exchange, one
+rb_session_transfer launch each, against the torch composition of the same
+result (out: one index_select per state tensor and the cat into the blob; in:
+the split and one index_copy_ per tensor); for B = 2,048 also the bytes moved
+per second, every word counted once read and once written.
+
 Prints one JSON line; --out also writes it to a file."""
 from __future__ import annotations
 
@@ -189,12 +197,120 @@ def recommend_leg(model, B: int, seq, lens, g, windows: int, k: int = 10) -> dic
                 first_call_equal=equal)
 
 
+def torch_park(state, slots, head, out):
+    """park as torch ops: one index_select per state tensor and the cat into
+    the blob (the row format of session/recblr_session.h)."""
+    B, i32 = slots.numel(), torch.int32
+    parts = [head, state.count.index_select(0, slots)[:, None].view(i32),
+             state.out.index_select(0, slots).view(i32)]
+    for h, conv in zip(state.h, state.conv):
+        parts.append(h.index_select(0, slots).view(i32))
+        parts.append(conv.index_select(0, slots).reshape(B, -1).view(i32))
+    parts.append(state.items.index_select(0, slots).view(i32))
+    return torch.cat(parts, 1, out=out)
+
+
+def torch_resume(state, blob, slots):
+    """resume as torch ops: the split and one index_copy_ per state tensor (no
+    check of the rows: the composition of the same result for valid rows)."""
+    lay, f32, i64 = state.blob_layout(), torch.float32, torch.int64
+
+    def part(name, dtype):
+        w0, n = lay[name]
+        return blob[:, w0:w0 + n].view(dtype)
+
+    state.count.index_copy_(0, slots, part("count", i64)[:, 0])
+    state.out.index_copy_(0, slots, part("out", f32))
+    for i, (h, conv) in enumerate(zip(state.h, state.conv)):
+        h.index_copy_(0, slots, part(f"h{i}", f32))
+        conv.index_copy_(0, slots, part(f"conv{i}", f32).reshape(-1, *conv.shape[1:]))
+    state.items.index_copy_(0, slots, part("items", i64))
+
+
+def park_leg(model, B: int, seq, windows: int, N: int = 4096) -> dict:
+    """Parking, resuming and exchanging B of N live sessions (S = L remembered
+    items): session.park / resume / exchange, one rb_session_transfer launch
+    each, against the torch composition of the same result, alternating window
+    by window in this process."""
+    from datamining_recblr_amd import session
+
+    dev = seq.device
+    g = torch.Generator().manual_seed(B)
+    states = [model.session_open(N, history=L) for _ in range(2)]     # kernel's, torch's
+    fill = torch.randint(1, N_ITEMS, (N, 32), generator=g).to(dev)
+    for st in states:
+        model.session_append(st, fill)                                # live slots, full of values
+    ker, tor = states
+    slots = torch.randperm(N, generator=g)[:B].to(dev)
+    W = ker.blob_words
+    lay = ker.blob_layout()
+    assert "pad" not in lay, "the composition below cats no pad"
+    head = torch.tensor([ker.blob_tag, 0], device=dev, dtype=torch.int32).expand(B, 2)
+    # the sessions that come in: B other live sessions
+    donor = model.session_open(B, history=L)
+    model.session_append(donor, seq[:, :48])
+    incoming = session.park(donor)
+    buf_k, buf_t = (torch.empty((B, W), device=dev, dtype=torch.int32) for _ in range(2))
+    # the same results first
+    equal = torch.equal(session.park(ker, slots, out=buf_k), torch_park(tor, slots, head, buf_t))
+    session.resume(ker, incoming, slots)
+    torch_resume(tor, incoming, slots)
+    same = lambda: all(torch.equal(a, b) for a, b in zip(                      # noqa: E731
+        [*ker.h, *ker.conv, ker.count, ker.out, ker.items],
+        [*tor.h, *tor.conv, tor.count, tor.out, tor.items]))
+    equal = equal and same() and bool((ker.status == session.MOVED).all())
+    swap_k, swap_t = [incoming.clone(), buf_k], [incoming.clone(), buf_t]
+
+    def exchange_kernel():
+        session.exchange(ker, swap_k[0], slots, out=swap_k[1])
+        swap_k.reverse()
+
+    def exchange_torch():
+        torch_park(tor, slots, head, swap_t[1])
+        torch_resume(tor, swap_t[0], slots)
+        swap_t.reverse()
+
+    legs = dict(
+        park=(lambda: session.park(ker, slots, out=buf_k),
+              lambda: torch_park(tor, slots, head, buf_t)),
+        resume=(lambda: session.resume(ker, incoming, slots),
+                lambda: torch_resume(tor, incoming, slots)),
+        exchange=(exchange_kernel, exchange_torch))
+    calls = 2000          # a call is 20-130 us: windows of 40-250 ms
+    row = dict(B=B, N=N, S=L, blob_words=W, blob_bytes=4 * W, calls_per_window=calls)
+    for name, (kernel, composed) in legs.items():
+        for _ in range(2):
+            window_ms(kernel, calls)
+            window_ms(composed, calls)
+        tk, tt = [], []
+        for _ in range(windows):
+            tk.append(window_ms(kernel, calls))
+            tt.append(window_ms(composed, calls))
+        k, t = statistics.median(tk), statistics.median(tt)
+        row.update({f"{name}_ms": round(k, 4), f"{name}_ms_min": round(min(tk), 4),
+                    f"{name}_ms_max": round(max(tk), 4), f"{name}_torch_ms": round(t, 4),
+                    f"{name}_torch_ms_min": round(min(tt), 4),
+                    f"{name}_torch_ms_max": round(max(tt), 4),
+                    f"torch_over_{name}": round(t / k, 2)})
+        if B >= 2048:       # bytes moved: each word read once and written once
+            moved = (4 if name == "exchange" else 2) * B * W * 4
+            row[f"{name}_bytes"] = moved
+            row[f"{name}_gb_per_s"] = round(moved / (k * 1e-3) / 1e9, 1)
+    equal = equal and same()              # after an even number of exchanges on both sides
+    row.update(round_trip_ms=round(row["park_ms"] + row["resume_ms"], 4),
+               kernel_equals_torch=bool(equal))
+    return row
+
+
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 64, 2048])
     ap.add_argument("--windows", type=int, default=9)
     ap.add_argument("--recommend", action="store_true",
                     help="also time session_recommend against a caller-kept seen-item matrix")
+    ap.add_argument("--park", action="store_true",
+                    help="time only session park / resume / exchange against their torch "
+                         "composition (B of 4,096 slots)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -205,6 +321,21 @@ def main() -> None:
                MAX_ITEM_LIST_LENGTH=L)
     torch.manual_seed(2020)
     model = RecBLR(cfg, SyntheticDataset(N_ITEMS)).to(dev).eval()
+    if args.park:
+        park_rows = []
+        with torch.no_grad():
+            for B in args.batches:
+                g = torch.Generator().manual_seed(B)
+                seq = torch.randint(1, N_ITEMS, (B, L), generator=g).to(dev)
+                park_rows.append(park_leg(model, B, seq, args.windows))
+        line = json.dumps(dict(bench="session_park", d=128, layers=2, K=4, L=L, S=L,
+                               n_items=N_ITEMS, windows=args.windows, park_rows=park_rows))
+        print(line)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                fh.write(line + "\n")
+        return
     rows, prefill_rows, append_rows, recommend_rows = [], [], [], []
     with torch.no_grad():
         for B in args.batches:
