@@ -726,6 +726,69 @@ int rb_embedding_bwd_apply_scaled(const float* src, int64_t src_ld, int64_t src_
                                        workspace, workspace_bytes, as_stream(stream));
 }
 
+// ---- candidate-list scoring (include/recblr_candidates.h) ---------------------------
+namespace {
+// what the three share: h, table, cand and their sizes (B >= 1 here)
+int check_candidates(const char* fn, const float* h, int64_t ldh, const float* table,
+                     const int64_t* cand, int64_t C, int64_t d, int64_t V) {
+  if (!h || !table || !cand) return fail(fn, "null pointer");
+  if (C < 1) return fail(fn, "C must be positive");
+  if (V < 1 || V >= (int64_t(1) << 31)) return fail(fn, "need 1 <= V < 2^31");
+  if (d < 4 || d > 512 || d % 4) return fail(fn, "d must be a multiple of 4 in [4, 512]");
+  if (ldh < d || ldh % 4 || !aligned16(h) || !aligned16(table))
+    return fail(fn, "h and table must be 16-B aligned with ldh >= d, ldh % 4 == 0");
+  return 0;
+}
+}  // namespace
+
+int rb_candidate_scores(const float* h, int64_t ldh, const float* table, const int64_t* cand,
+                        int64_t B, int64_t C, int64_t d, int64_t V, float* scores,
+                        void* stream) {
+  const char* fn = "rb_candidate_scores";
+  if (B < 0) return fail(fn, "B must be >= 0");
+  if (B == 0) return 0;
+  if (int rc = check_candidates(fn, h, ldh, table, cand, C, d, V)) return rc;
+  if (!scores) return fail(fn, "null pointer");
+  if (B >= (int64_t(1) << 31) || C >= (int64_t(1) << 31) || B * C >= (int64_t(1) << 37))
+    return fail(fn, "B * C must stay below 2^37");
+  return launch_candidate_scores(h, ldh, table, cand, B, C, d, V, scores, as_stream(stream));
+}
+
+int rb_candidate_topk(const float* h, int64_t ldh, const float* table, const int64_t* cand,
+                      int64_t B, int64_t C, int64_t d, int64_t V, int64_t first_item, int64_t k,
+                      const int64_t* exclude, int64_t E, int64_t* ids, float* scores,
+                      void* stream) {
+  const char* fn = "rb_candidate_topk";
+  if (B < 0) return fail(fn, "B must be >= 0");
+  if (B == 0) return 0;
+  if (int rc = check_candidates(fn, h, ldh, table, cand, C, d, V)) return rc;
+  if (!ids || !scores) return fail(fn, "null pointer");
+  if (C > 4096) return fail(fn, "C must be in [1, 4096]");
+  if (E < 0 || E > 4096) return fail(fn, "E must be in [0, 4096]");
+  if (E > 0 && !exclude) return fail(fn, "null pointer");
+  if (k < 1 || k >= (int64_t(1) << 31)) return fail(fn, "k must be in [1, 2^31)");
+  if (first_item < 0 || first_item > V) return fail(fn, "first_item must be in [0, V]");
+  if (B >= (int64_t(1) << 31)) return fail(fn, "grid too large");
+  return launch_candidate_topk(h, ldh, table, cand, B, C, d, V, first_item, k, exclude, E, ids,
+                               scores, as_stream(stream));
+}
+
+int rb_candidate_ranks(const float* h, int64_t ldh, const float* table, const int64_t* target,
+                       const int64_t* cand, int64_t B, int64_t C, int64_t d, int64_t V,
+                       int64_t first_item, int64_t* n_greater, int64_t* n_equal, void* stream) {
+  const char* fn = "rb_candidate_ranks";
+  if (B < 0) return fail(fn, "B must be >= 0");
+  if (B == 0) return 0;
+  if (int rc = check_candidates(fn, h, ldh, table, cand, C, d, V)) return rc;
+  if (!target || !n_greater || !n_equal) return fail(fn, "null pointer");
+  if (first_item < 0 || first_item > V) return fail(fn, "first_item must be in [0, V]");
+  if (B >= (int64_t(1) << 31) || C >= (int64_t(1) << 40) ||
+      B * candidate_rank_chunks(C) >= (int64_t(1) << 31))
+    return fail(fn, "grid too large");
+  return launch_candidate_ranks(h, ldh, table, target, cand, B, C, d, V, first_item, n_greater,
+                                n_equal, as_stream(stream));
+}
+
 int rb_group_absmax(const float* x, int64_t n, int64_t c, int64_t ld, float* out, void* stream) {
   if (!x || !out) return fail("rb_group_absmax: null pointer");
   if (n <= 0 || c <= 0 || ld < c) return fail("rb_group_absmax: bad shape");

@@ -11,6 +11,7 @@
 #include "../../include/recblr_hip.h"
 #include "../../include/recblr_dense.h"
 #include "../../include/recblr_pairs.h"
+#include "../../include/recblr_candidates.h"
 
 namespace rb {
 
@@ -520,6 +521,17 @@ int launch_pair_loss_bwd(const float* tab, const int64_t* pos, const int64_t* ne
                          const float* diff, const float* dloss, const int64_t* n_live, int64_t M,
                          int64_t d, int64_t V, int64_t n_neg, float gamma, float* dh, float* coef,
                          hipStream_t st);
+int launch_candidate_scores(const float* h, int64_t ldh, const float* tab, const int64_t* cand,
+                            int64_t B, int64_t C, int64_t d, int64_t V, float* scores,
+                            hipStream_t st);
+int launch_candidate_topk(const float* h, int64_t ldh, const float* tab, const int64_t* cand,
+                          int64_t B, int64_t C, int64_t d, int64_t V, int64_t first, int64_t k,
+                          const int64_t* exclude, int64_t E, int64_t* ids, float* scores,
+                          hipStream_t st);
+int64_t candidate_rank_chunks(int64_t C);
+int launch_candidate_ranks(const float* h, int64_t ldh, const float* tab, const int64_t* target,
+                           const int64_t* cand, int64_t B, int64_t C, int64_t d, int64_t V,
+                           int64_t first, int64_t* n_gt, int64_t* n_eq, hipStream_t st);
 int64_t item_ce_workspace_bytes(int64_t B, int64_t V, int64_t D);
 int64_t item_rank_workspace_bytes(int64_t B, int64_t V);
 int launch_item_ce_fwd(const float* E, const float* W, const int64_t* tgt, int64_t B, int64_t V,

@@ -25,6 +25,8 @@ __all__ = [
     "next_item_targets", "next_item_targets_reference",
     "sample_negatives", "sample_negatives_reference", "philox4x32_10", "pair_loss_fwd",
     "pair_loss_bwd", "embedding_bwd_scaled", "pair_loss_supported",
+    "candidate_scores", "candidate_topk", "candidate_ranks", "candidates_supported",
+    "CANDIDATE_MAX", "CANDIDATE_EXCLUDE_MAX",
 ]
 
 
@@ -1357,6 +1359,103 @@ def embedding_bwd_scaled(coef: torch.Tensor, src: torch.Tensor, num_rows: int, p
             rows, coef.contiguous().data_ptr(), M, d, num_rows, pad, dw.data_ptr(),
             plan.data_ptr(), plan.numel(), _stream(src), _fn="rb_embedding_bwd_apply_scaled")
     return dw
+
+
+# ---- candidate lists (csrc/candidates.hip, include/recblr_candidates.h) -------------
+CANDIDATE_MAX = 4096           # rb_candidate_topk's largest C
+CANDIDATE_EXCLUDE_MAX = 4096   # ... and its largest E
+CANDIDATE_MAX_D = 512
+
+
+def candidates_supported(h: torch.Tensor, table: torch.Tensor) -> bool:
+    """The candidate kernels take fp32 GPU rows of d a multiple of 4 up to 512."""
+    return (h.is_cuda and table.is_cuda and h.dtype == torch.float32
+            and table.dtype == torch.float32 and h.dim() == 2 and table.dim() == 2
+            and h.shape[1] == table.shape[1] and h.shape[1] % 4 == 0
+            and 4 <= h.shape[1] <= CANDIDATE_MAX_D)
+
+
+def _candidate_operands(h, table, cand):
+    """(h with unit-stride, 16-B aligned rows, contiguous table, contiguous
+    cand [B, C]) of a candidate kernel; copies only what the kernel cannot read."""
+    _check(h, "h")
+    _check(table, "table")
+    _check(cand, "candidates", torch.int64)
+    if h.dim() != 2 or table.dim() != 2 or table.shape[1] != h.shape[1]:
+        raise ValueError("candidates: h [B, d] and table [V, d] required")
+    if cand.dim() != 2 or cand.shape[0] != h.shape[0]:
+        raise ValueError(f"candidates must be [B, C], got {tuple(cand.shape)}")
+    if h.stride(1) != 1 or h.stride(0) % 4 or h.data_ptr() % 16:
+        h = h.contiguous()
+    return h, table.contiguous(), cand.contiguous()
+
+
+def candidate_scores(h: torch.Tensor, table: torch.Tensor, cand: torch.Tensor) -> torch.Tensor:
+    """rb_candidate_scores: scores [B, C] fp32, h_b . table[cand[b, c]]; -inf
+    for an id outside [0, V).  h [B, d] (unit-stride rows of any 16-B aligned
+    stride), table [V, d], cand [B, C] int64."""
+    h, table, cand = _candidate_operands(h, table, cand)
+    (B, d), C, V = h.shape, cand.shape[1], table.shape[0]
+    out = torch.empty((B, C), device=h.device, dtype=torch.float32)
+    if B and C:
+        _launch("rb_candidate_scores", 4 * (C + 1) * d * B, h.data_ptr(), h.stride(0),
+                table.data_ptr(), cand.data_ptr(), B, C, d, V, out.data_ptr(), _stream(h))
+    return out
+
+
+def candidate_topk(h: torch.Tensor, table: torch.Tensor, cand: torch.Tensor, k: int,
+                   first_item: int = 0, exclude: torch.Tensor | None = None):
+    """rb_candidate_topk: (ids int64 [B, k], scores fp32 [B, k]), each row's k
+    best distinct candidates in [first_item, V) not listed in exclude [B, E]
+    (int64; entries outside [0, V) ignored), by (score descending, id
+    ascending), scores bit-identical to candidate_scores'; id -1 / score -inf
+    where fewer than k survive.  C <= CANDIDATE_MAX, E <= CANDIDATE_EXCLUDE_MAX;
+    one launch."""
+    h, table, cand = _candidate_operands(h, table, cand)
+    (B, d), C, V = h.shape, cand.shape[1], table.shape[0]
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k = {k} must be positive")
+    if not 1 <= C <= CANDIDATE_MAX:
+        raise ValueError(f"C = {C} candidates per row: expected 1 .. {CANDIDATE_MAX}")
+    E = 0
+    if exclude is not None:
+        _check(exclude, "exclude", torch.int64)
+        if exclude.dim() != 2 or exclude.shape[0] != B:
+            raise ValueError(f"exclude must be [B, E], got {tuple(exclude.shape)}")
+        exclude = exclude.contiguous()
+        E = exclude.shape[1]
+        if E > CANDIDATE_EXCLUDE_MAX:
+            raise ValueError(f"E = {E} excluded ids per row: at most {CANDIDATE_EXCLUDE_MAX}")
+    ids = torch.empty((B, k), device=h.device, dtype=torch.int64)
+    scores = torch.empty((B, k), device=h.device, dtype=torch.float32)
+    if B:
+        _launch("rb_candidate_topk", 4 * (C + 1) * d * B, h.data_ptr(), h.stride(0),
+                table.data_ptr(), cand.data_ptr(), B, C, d, V, int(first_item), k,
+                exclude.data_ptr() if E > 0 else None, E, ids.data_ptr(), scores.data_ptr(),
+                _stream(h))
+    return ids, scores
+
+
+def candidate_ranks(h: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
+                    cand: torch.Tensor, first_item: int = 1):
+    """rb_candidate_ranks: (n_greater, n_equal) int64 [B] over the entries of
+    cand[b] in [first_item, V) other than target[b] with a non-NaN score,
+    counted as listed; -1, -1 for a target outside [first_item, V)."""
+    h, table, cand = _candidate_operands(h, table, cand)
+    _check(target, "target", torch.int64)
+    (B, d), C, V = h.shape, cand.shape[1], table.shape[0]
+    if target.shape != (B,):
+        raise ValueError(f"target must be [B], got {tuple(target.shape)}")
+    if C < 1:
+        raise ValueError("candidates must hold at least one id per row")
+    gt = torch.empty((B,), device=h.device, dtype=torch.int64)
+    eq = torch.empty((B,), device=h.device, dtype=torch.int64)
+    if B:
+        _launch("rb_candidate_ranks", 4 * (C + 2) * d * B, h.data_ptr(), h.stride(0),
+                table.data_ptr(), target.contiguous().data_ptr(), cand.data_ptr(), B, C, d, V,
+                int(first_item), gt.data_ptr(), eq.data_ptr(), _stream(h))
+    return gt, eq
 
 
 class _SplitJob(ctypes.Structure):

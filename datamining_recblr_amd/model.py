@@ -38,8 +38,8 @@ from .recbole_compat import BPRLoss, SequentialRecommender, install_interaction_
 from .recurrence import bd_lru, fused_ok, pow2_pad_len, row_pad_lens
 
 
-from .scoring import (full_sort_scores, item_cross_entropy, item_cross_entropy_rows, pair_loss,
-                      target_ranks, top_items)
+from .scoring import (candidate_ranks, candidate_scores, full_sort_scores, item_cross_entropy,
+                      item_cross_entropy_rows, pair_loss, target_ranks, top_candidates, top_items)
 
 # RECBLR_CONV_ROWS=0: packed conv forward per sequence instead of per row tile
 _CONV_ROWS = os.environ.get("RECBLR_CONV_ROWS", "1") != "0"
@@ -577,6 +577,37 @@ class RecBLR(SequentialRecommender):
         return top_items(seq_output, self.item_embedding.weight, k, first_item=first_item,
                          exclude=item_seq if exclude_seen else None)
 
+    # ---- candidate lists (scoring.candidate_scores / top_candidates) ----------
+    def predict_candidates(self, interaction, candidates):
+        """scores [B, C] of each row's own candidates [B, C] (int64; an id
+        outside [0, n_items) scores -inf): predict for several items per row.
+        Under no_grad one launch after the forward, no [B, C, d] gather; with
+        gradients enabled the torch expression, which backpropagates to the
+        item table and the encoder."""
+        seq_output = self.forward(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN])
+        return candidate_scores(seq_output, self.item_embedding.weight, candidates)
+
+    @torch.no_grad()
+    def rerank(self, interaction, candidates, k: int = 10, exclude_seen: bool = False,
+               first_item: int = 1):
+        """(ids, scores) [B, k]: each row's k best of its own candidates
+        [B, C] (-1 pads a ragged list) by (score descending, id ascending) over
+        the distinct ids in [first_item, n_items); exclude_seen drops the row's
+        own ITEM_SEQ entries, as full_sort_topk does.  k = C orders the list."""
+        item_seq = interaction[self.ITEM_SEQ]
+        seq_output = self.forward(item_seq, interaction[self.ITEM_SEQ_LEN])
+        return top_candidates(seq_output, self.item_embedding.weight, candidates, k,
+                              first_item=first_item, exclude=item_seq if exclude_seen else None)
+
+    @torch.no_grad()
+    def sampled_rank(self, interaction, negatives, first_item: int = 1):
+        """Rank of each row's target (POS_ITEM_ID) among its sampled negatives
+        [B, n] (RecBole's uni100-style protocol): (n_greater, n_equal) for
+        rank_metrics, negatives counted as listed, the target's own id skipped."""
+        seq_output = self.forward(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN])
+        return candidate_ranks(seq_output, self.item_embedding.weight,
+                               interaction[self.POS_ITEM_ID], negatives, first_item)
+
     # ---- stateful session inference (session.py) ----------------------------
     def session_open(self, capacity: int, seq_len: int | None = None, history: int = 0):
         """A session.SessionState of `capacity` slots for the window seq_len
@@ -622,6 +653,15 @@ class RecBLR(SequentialRecommender):
         from .session import recommend
 
         return recommend(self, state, items, slots, k, exclude_seen, first_item)
+
+    def session_rerank(self, state, candidates, items=None, slots=None, k: int = 10,
+                       exclude_seen: bool = False, first_item: int = 1):
+        """(ids, scores) [B, k]: the rows' own candidates [B, C] ordered for
+        their sessions after one step (items [B]) or append (items [B, W]), or
+        from the slots' stored outputs (items None) (session.rerank)."""
+        from .session import rerank
+
+        return rerank(self, state, candidates, items, slots, k, exclude_seen, first_item)
 
     def session_park(self, state, slots=None, release: bool = False, out=None):
         """The slots' sessions as rows of an int32 [B, state.blob_words] blob,

@@ -23,6 +23,15 @@ RECBLR_CE_PIPE), ranking and scores on the fp32 pipe:
   * full_sort_scores: the score matrix itself when a caller needs it;
   * top_items: each row's k best items (a recommendation list), with
     seen-item exclusion, selected inside the scoring kernel.
+
+And against chosen items only (csrc/candidates.hip: a 16-lane group per (row,
+id), no [B, C, d] gather, no sweep over the table):
+
+  * candidate_scores: [B, C] scores of each row's own candidate ids;
+  * top_candidates: a row's candidate list ordered by the model (reranking),
+    scored, filtered, sorted and written by one launch; order_candidates is
+    its selection rule alone, in torch ops;
+  * candidate_ranks: the target's rank among a row's sampled negatives.
 """
 from __future__ import annotations
 
@@ -34,7 +43,8 @@ import torch.nn.functional as F
 from . import kernels
 
 __all__ = ["item_cross_entropy", "item_cross_entropy_rows", "full_sort_scores", "target_ranks", "rank_metrics",
-           "top_items", "supported", "pair_loss", "pair_loss_reference"]
+           "top_items", "supported", "pair_loss", "pair_loss_reference", "candidate_scores",
+           "order_candidates", "top_candidates", "candidate_ranks"]
 
 
 def supported(seq: torch.Tensor, table: torch.Tensor) -> bool:
@@ -516,6 +526,182 @@ def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 
         return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
                                  exclude=exclude)
     return _top_items_torch(seq.detach(), table.detach(), k, first_item, exclude)
+
+
+# ---- candidate lists: scoring chosen items (csrc/candidates.hip) --------------------
+def _check_candidates(seq, table, candidates):
+    if seq.dim() != 2 or table.dim() != 2 or seq.shape[1] != table.shape[1]:
+        raise ValueError(f"seq [B, d] and table [V, d] required, got {tuple(seq.shape)} and "
+                         f"{tuple(table.shape)}")
+    if (not isinstance(candidates, torch.Tensor) or candidates.dim() != 2
+            or candidates.shape[0] != seq.shape[0]):
+        raise ValueError("candidates must be [B, C], got "
+                         f"{tuple(getattr(candidates, 'shape', ()))}")
+    return candidates.to(device=seq.device, dtype=torch.int64)
+
+
+def _candidate_scores_torch(seq, table, candidates):
+    """candidate_scores in torch ops (differentiable; materialises [B, C, d])."""
+    V = table.shape[0]
+    ok = (candidates >= 0) & (candidates < V)
+    s = (seq[:, None, :] * table[candidates.clamp(0, V - 1)]).sum(-1)
+    return torch.where(ok, s, torch.full_like(s, float("-inf")))
+
+
+def candidate_scores(seq: torch.Tensor, table: torch.Tensor,
+                     candidates: torch.Tensor) -> torch.Tensor:
+    """scores [B, C]: seq_b . table[candidates[b, c]]; -inf for an id outside
+    [0, V), so -1 pads a ragged list.  On fp32 GPU tensors with d a multiple
+    of 4 up to 512 and no gradient needed this is one launch
+    (rb_candidate_scores: no [B, C, d] gather, no [B, V] matrix), and a (row,
+    id) pair's score has the same bits wherever the id stands and whatever B
+    and C are.  Anything else takes the torch expression with the same
+    masking, which is differentiable: RecBLR.predict for several items."""
+    candidates = _check_candidates(seq, table, candidates)
+    needs_grad = torch.is_grad_enabled() and (seq.requires_grad or table.requires_grad)
+    if kernels.candidates_supported(seq, table) and not needs_grad:
+        return kernels.candidate_scores(seq.detach(), table.detach(), candidates)
+    return _candidate_scores_torch(seq, table, candidates)
+
+
+@torch.no_grad()
+def order_candidates(scores: torch.Tensor, candidates: torch.Tensor, k: int, first_item: int = 0,
+                     exclude: torch.Tensor | None = None, num_items: int | None = None):
+    """The selection rule of top_candidates alone, in torch ops on any device:
+    ``(ids int64 [B, k], scores fp32 [B, k])`` from scores [B, C] and their ids
+    candidates [B, C].
+
+    Per row it selects over the distinct ids that lie in [first_item,
+    num_items) (num_items None: no upper limit), are not listed in exclude
+    [B, E] (entries outside [0, num_items) are ignored, duplicates allowed —
+    top_items' rule) and whose score is not NaN, ordered by (score descending,
+    id ascending).  An id listed several times appears once, where its first
+    entry in that order stands.  When fewer than k survive the tail holds id
+    -1, score -inf; a selectable candidate that itself scores -inf comes before
+    that padding."""
+    k, first = int(k), int(first_item)
+    if k < 1:
+        raise ValueError(f"k = {k} must be positive")
+    if first < 0:
+        raise ValueError(f"first_item = {first_item} must be >= 0")
+    if scores.dim() != 2 or candidates.shape != scores.shape:
+        raise ValueError(f"scores and candidates must both be [B, C], got {tuple(scores.shape)} "
+                         f"and {tuple(candidates.shape)}")
+    B, C = scores.shape
+    dev = scores.device
+    scores = scores.float()
+    ids = candidates.to(device=dev, dtype=torch.int64)
+    drop = torch.isnan(scores) | (ids < first)
+    if num_items is not None:
+        drop |= ids >= int(num_items)
+    if exclude is not None and exclude.numel() > 0:
+        if exclude.dim() != 2 or exclude.shape[0] != B:
+            raise ValueError(f"exclude must be [B, E], got {tuple(exclude.shape)}")
+        ex = exclude.to(device=dev, dtype=torch.int64)
+        bad = ex < 0
+        if num_items is not None:
+            bad |= ex >= int(num_items)
+        # membership by a sorted search: an ignored entry becomes -1, which only
+        # a dropped candidate (id < 0 <= first_item) can equal
+        ex = torch.sort(torch.where(bad, torch.full_like(ex, -1), ex), dim=1).values
+        at = torch.searchsorted(ex, ids.contiguous()).clamp(max=ex.shape[1] - 1)
+        drop |= ex.gather(1, at) == ids
+    masked = torch.where(drop, torch.full_like(scores, float("-inf")), scores)
+    # three stable sorts: by id, then by score descending (equal scores keep
+    # the smaller id first), then the dropped entries behind the rest
+    order = torch.sort(ids, dim=1, stable=True).indices
+    order = order.gather(1, torch.sort(masked.gather(1, order), dim=1, descending=True,
+                                       stable=True).indices)
+    order = order.gather(1, torch.sort(drop.gather(1, order).to(torch.int8), dim=1,
+                                       stable=True).indices)
+    # duplicates by id: in a stable sort of the ordered ids each id's run
+    # starts with its earliest entry; every later one is dropped as well
+    sid, sdrop = ids.gather(1, order), drop.gather(1, order)
+    by_id = torch.sort(sid, dim=1, stable=True)
+    run_start = torch.ones_like(sid, dtype=torch.bool)
+    run_start[:, 1:] = by_id.values[:, 1:] != by_id.values[:, :-1]
+    dup = torch.ones_like(sdrop).scatter_(1, by_id.indices, ~run_start)
+    gone = sdrop | dup
+    order = order.gather(1, torch.sort(gone.to(torch.int8), dim=1, stable=True).indices)
+    n_ok = (~gone).sum(1, keepdim=True)
+    kk = min(k, C)
+    out_ids = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+    out = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
+    live = torch.arange(kk, device=dev)[None, :] < n_ok
+    out_ids[:, :kk] = torch.where(live, ids.gather(1, order[:, :kk]), out_ids[:, :kk])
+    out[:, :kk] = torch.where(live, scores.gather(1, order[:, :kk]), out[:, :kk])
+    return out_ids, out
+
+
+@torch.no_grad()
+def top_candidates(seq: torch.Tensor, table: torch.Tensor, candidates: torch.Tensor, k: int,
+                   first_item: int = 0, exclude: torch.Tensor | None = None):
+    """Each row's candidate list ordered by the model: ``(ids int64 [B, k],
+    scores fp32 [B, k])``, the k best distinct ids of candidates [B, C] (-1
+    pads a ragged list) by (score descending, id ascending) — top_items'
+    order and top_items' rules for first_item, exclude [B, E] and NaN scores;
+    a repeated id appears once; where fewer than k survive the tail holds id
+    -1, score -inf.  k = C orders the whole list.
+
+    On fp32 GPU tensors with d a multiple of 4 up to 512, C <=
+    kernels.CANDIDATE_MAX and E <= kernels.CANDIDATE_EXCLUDE_MAX it is one
+    launch that scores, filters, sorts and writes (rb_candidate_topk), its
+    scores bit-identical to candidate_scores'; anything else is
+    order_candidates(candidate_scores(...), ...)."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k = {k} must be positive")
+    if int(first_item) < 0:
+        raise ValueError(f"first_item = {first_item} must be >= 0")
+    candidates = _check_candidates(seq, table, candidates)
+    if exclude is not None:
+        if exclude.dim() != 2 or exclude.shape[0] != seq.shape[0]:
+            raise ValueError(f"exclude must be [B, E], got {tuple(exclude.shape)}")
+        exclude = exclude.to(device=seq.device, dtype=torch.int64)
+    V, C = table.shape[0], candidates.shape[1]
+    E = 0 if exclude is None else exclude.shape[1]
+    seq, table = seq.detach(), table.detach()
+    if (kernels.candidates_supported(seq, table) and 1 <= C <= kernels.CANDIDATE_MAX
+            and E <= kernels.CANDIDATE_EXCLUDE_MAX and int(first_item) <= V):
+        return kernels.candidate_topk(seq, table, candidates, k, first_item=first_item,
+                                      exclude=exclude if E else None)
+    return order_candidates(candidate_scores(seq, table, candidates), candidates, k, first_item,
+                            exclude, num_items=V)
+
+
+def _candidate_ranks_torch(seq, table, target, candidates, first_item):
+    V = table.shape[0]
+    s = _candidate_scores_torch(seq, table, torch.cat([target[:, None], candidates], 1))
+    st, s = s[:, :1], s[:, 1:]
+    ok = ((candidates >= first_item) & (candidates < V) & (candidates != target[:, None])
+          & ~torch.isnan(s))
+    gt, eq = (ok & (s > st)).sum(1), (ok & (s == st)).sum(1)
+    bad = (target < first_item) | (target >= V)
+    return gt.masked_fill(bad, -1), eq.masked_fill(bad, -1)
+
+
+@torch.no_grad()
+def candidate_ranks(seq: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
+                    candidates: torch.Tensor, first_item: int = 1):
+    """(n_greater, n_equal) int64 [B] of each row's target among its own
+    candidates [B, C] (sampled negatives): over the entries that lie in
+    [first_item, V), differ from the target and have a non-NaN score, how many
+    score strictly above the target and how many exactly equal to it.  Entries
+    count as listed (a repeated negative counts twice, as a batch expanded
+    through predict counts it); a target outside [first_item, V) gives -1, -1,
+    which rank_metrics drops.  One launch on the GPU (rb_candidate_ranks, any
+    C); the CPU and an unsupported d take torch ops."""
+    if int(first_item) < 0:
+        raise ValueError(f"first_item = {first_item} must be >= 0")
+    candidates = _check_candidates(seq, table, candidates)
+    if target.shape != (seq.shape[0],):
+        raise ValueError(f"target must be [B], got {tuple(target.shape)}")
+    target = target.to(device=seq.device, dtype=torch.int64)
+    seq, table = seq.detach(), table.detach()
+    if (kernels.candidates_supported(seq, table) and candidates.shape[1] >= 1
+            and int(first_item) <= table.shape[0]):
+        return kernels.candidate_ranks(seq, table, target, candidates, first_item=first_item)
+    return _candidate_ranks_torch(seq, table, target, candidates, int(first_item))
 
 
 def rank_metrics(n_greater: torch.Tensor, n_equal: torch.Tensor | None = None,

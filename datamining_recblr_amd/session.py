@@ -78,6 +78,7 @@ from .recurrence import pad_prefix_state, pow2_pad_len
 
 __all__ = ["SessionState", "EncoderParams", "step", "step_reference", "prefill",
            "capture_reference", "append", "append_reference", "record_reference", "recommend",
+           "rerank",
            "kernel_supports", "STEPPED", "NO_EVENT", "BAD_ITEM", "BAD_SLOT", "park", "resume",
            "exchange", "transfer_reference", "MOVED", "BAD_BLOB"]
 
@@ -973,8 +974,22 @@ def recommend(model, state: SessionState, items=None, slots=None, k: int = 10,
     left it."""
     from .scoring import top_items
 
+    p, y, seen, dead = _serve_rows(model, state, items, slots, exclude_seen, "recommend")
+    ids, scores = top_items(y, p.t["item_embedding.weight"], k, first_item,
+                            exclude=seen if exclude_seen else None)
+    ids.masked_fill_(dead[:, None], -1)
+    scores.masked_fill_(dead[:, None], float("-inf"))
+    return ids, scores
+
+
+def _serve_rows(model, state: SessionState, items, slots, exclude_seen: bool, who: str):
+    """The front half recommend and rerank share: the call's events, then
+    ``(params, y [B, d], seen [B, S] or None, dead [B])`` — the rows'
+    seq_output afterwards, their item rings as the seen lists (with
+    exclude_seen) and the rows that must come back as -1 / -inf (a slot outside
+    the state, or one that has consumed no event yet)."""
     if exclude_seen and state.items is None:
-        raise ValueError("recommend(exclude_seen=True) needs the slots' item ring: open the "
+        raise ValueError(f"{who}(exclude_seen=True) needs the slots' item ring: open the "
                          "state with history=S (session_open(capacity, history=S)), or pass "
                          "exclude_seen=False")
     p = _params(model)
@@ -1006,8 +1021,35 @@ def recommend(model, state: SessionState, items=None, slots=None, k: int = 10,
         dead = state.count[:B] == 0
     else:
         dead = _bad_slot(state, slots) | (state.count[slots.clamp(0, state.capacity - 1)] == 0)
-    ids, scores = top_items(y, p.t["item_embedding.weight"], k, first_item,
-                            exclude=seen if exclude_seen else None)
+    return p, y, seen, dead
+
+
+@torch.no_grad()
+def rerank(model, state: SessionState, candidates, items=None, slots=None, k: int = 10,
+           exclude_seen: bool = False, first_item: int = 1):
+    """Order these items for this session: ``(ids int64 [B, k], scores fp32
+    [B, k])``, each row's k best of its own candidates [B, C] (int64, -1 pads a
+    ragged list) by ``scoring.top_candidates`` for its slot's seq_output after
+    the call's events; k = C orders the whole list.
+
+    items, slots, the masked rows (-1 / -inf for a slot outside the state or
+    one without an event yet), the refusals and the fallbacks are exactly
+    ``recommend``'s; exclude_seen drops the ids in the slot's item ring and
+    needs a state opened with ``history=S``.  A state on the CPU runs the whole
+    call in torch ops."""
+    from .scoring import top_candidates
+
+    candidates = torch.as_tensor(candidates, dtype=torch.int64)
+    if candidates.dim() != 2:
+        raise ValueError(f"candidates must be [B, C], got {tuple(candidates.shape)}")
+    # the call's rows, known before any event is consumed
+    B = (torch.as_tensor(items).shape[0] if items is not None
+         else state.capacity if slots is None else torch.as_tensor(slots).numel())
+    if candidates.shape[0] != B:
+        raise ValueError(f"candidates has {candidates.shape[0]} rows, the call {B}")
+    p, y, seen, dead = _serve_rows(model, state, items, slots, exclude_seen, "rerank")
+    ids, scores = top_candidates(y, p.t["item_embedding.weight"], candidates.to(state.device), k,
+                                 first_item, exclude=seen if exclude_seen else None)
     ids.masked_fill_(dead[:, None], -1)
     scores.masked_fill_(dead[:, None], float("-inf"))
     return ids, scores
