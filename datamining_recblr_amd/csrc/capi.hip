@@ -504,7 +504,7 @@ int rb_item_ce_probs(const float* seq, const float* items, const int64_t* target
   if (int rc = check_items("rb_item_ce_probs", seq, items, B, V, d)) return rc;
   if (!target || !lse || !dloss || !probs) return fail("rb_item_ce_probs: null pointer");
   if (ld < V) return fail("rb_item_ce_probs: ld < V");
-  return launch_item_ce_probs(seq, items, target, lse, dloss, B, V, d, item_offset, V, probs, ld,
+  return launch_item_ce_probs(seq, items, target, lse, dloss, B, V, d, item_offset, probs, ld,
                               reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -527,43 +527,73 @@ int check_items_h(const void* seq_img, const int* seq_exp, const void* item_img,
   return check_items("item scores (f16)", reinterpret_cast<const float*>(seq_img),
                      reinterpret_cast<const float*>(item_img), B, V, d);
 }
+
+// the rows variants' normaliser: 1 / (live rows of the whole call)
+int check_inv_n(const char* fn, float inv_n) {
+  if (!(inv_n > 0.0f) || !(inv_n <= 1.0f)) return fail(fn, "inv_n must be in (0, 1]");
+  return 0;
+}
+
+// rows: rb_item_ce_fwd_h_rows, which also checks its inv_n and accumulate
+int item_ce_fwd_h(const char* fn, bool rows, const void* seq_img, const int* seq_exp,
+                  const void* item_img, const int* item_exp, const int64_t* target, int64_t B,
+                  int64_t V, int64_t d, float inv_n, int accumulate, float* lse, float* loss,
+                  void* workspace, int64_t workspace_bytes, void* stream) {
+  if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
+  if (!target || !lse || !loss || !workspace) return fail(fn, "null pointer");
+  if (rows) {
+    if (int rc = check_inv_n(fn, inv_n)) return rc;
+    if (accumulate != 0 && accumulate != 1) return fail(fn, "accumulate must be 0 or 1");
+  }
+  return launch_item_ce_fwd_h(seq_img, seq_exp, item_img, item_exp, target, B, V, d, lse, loss,
+                              workspace, workspace_bytes, rows, inv_n, accumulate,
+                              as_stream(stream));
+}
+
+// The five rb_item_ce_probs_h* entry points.  want_p / want_pt: the layouts
+// entry point fn writes; each needs its buffer, P^T its item group maxima and
+// both together the row group maxima too.
+int item_ce_probs_h(const char* fn, bool want_p, bool want_pt, const void* seq_img,
+                    const int* seq_exp, const void* item_img, const int* item_exp,
+                    const int64_t* target, const float* lse, const float* dloss, int64_t B,
+                    int64_t V, int64_t d, int64_t item_offset, const CeProbsOut& o, void* stream) {
+  if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
+  if (!target || !lse || !dloss || (want_p && !o.p) || (want_pt && (!o.pt || !o.item_max)) ||
+      (want_p && want_pt && !o.row_max))
+    return fail(fn, "null pointer");
+  if (o.rows)
+    if (int rc = check_inv_n(fn, o.inv_n)) return rc;
+  if (want_p && o.ld < V) return fail(fn, "ld < V");
+  if (want_pt && (o.ldt < B || o.ldt % 4 || reinterpret_cast<uintptr_t>(o.pt) % 16))
+    return fail(fn, "probs_t must be 16-B aligned with ldt >= B, ldt % 4 == 0");
+  return launch_item_ce_probs_h(seq_img, seq_exp, item_img, item_exp, target, lse, dloss, B, V, d,
+                                item_offset, o, as_stream(stream));
+}
 }  // namespace
 
 int rb_item_ce_fwd_h(const void* seq_img, const int* seq_exp, const void* item_img,
                      const int* item_exp, const int64_t* target, int64_t B, int64_t V, int64_t d,
                      float* lse, float* loss, void* workspace, int64_t workspace_bytes,
                      void* stream) {
-  if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
-  if (!target || !lse || !loss || !workspace) return fail("rb_item_ce_fwd_h: null pointer");
-  return launch_item_ce_fwd_h(seq_img, seq_exp, item_img, item_exp, target, B, V, d, lse, loss,
-                              workspace, workspace_bytes, false, 0.0f, 0,
-                              reinterpret_cast<hipStream_t>(stream));
+  return item_ce_fwd_h("rb_item_ce_fwd_h", false, seq_img, seq_exp, item_img, item_exp, target, B,
+                       V, d, 0.0f, 0, lse, loss, workspace, workspace_bytes, stream);
 }
 
 int rb_item_ce_probs_h(const void* seq_img, const int* seq_exp, const void* item_img,
                        const int* item_exp, const int64_t* target, const float* lse,
                        const float* dloss, int64_t B, int64_t V, int64_t d, int64_t item_offset,
                        float* probs, int64_t ld, void* stream) {
-  if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
-  if (!target || !lse || !dloss || !probs) return fail("rb_item_ce_probs_h: null pointer");
-  if (ld < V) return fail("rb_item_ce_probs_h: ld < V");
-  return launch_item_ce_probs_h(seq_img, seq_exp, item_img, item_exp, target, lse, dloss, B, V, d,
-                                item_offset, probs, ld, nullptr, nullptr, 0, nullptr, 0.0f,
-                                reinterpret_cast<hipStream_t>(stream));
+  return item_ce_probs_h("rb_item_ce_probs_h", true, false, seq_img, seq_exp, item_img, item_exp,
+                         target, lse, dloss, B, V, d, item_offset, {.p = probs, .ld = ld}, stream);
 }
 
 int rb_item_ce_probs_h_t(const void* seq_img, const int* seq_exp, const void* item_img,
                          const int* item_exp, const int64_t* target, const float* lse,
                          const float* dloss, int64_t B, int64_t V, int64_t d, int64_t item_offset,
                          float* probs_t, int64_t ldt, float* group_max, void* stream) {
-  if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
-  if (!target || !lse || !dloss || !probs_t || !group_max)
-    return fail("rb_item_ce_probs_h_t: null pointer");
-  if (ldt < B || ldt % 4 || reinterpret_cast<uintptr_t>(probs_t) % 16)
-    return fail("rb_item_ce_probs_h_t: probs_t must be 16-B aligned with ldt >= B, ldt % 4 == 0");
-  return launch_item_ce_probs_h(seq_img, seq_exp, item_img, item_exp, target, lse, dloss, B, V, d,
-                                item_offset, probs_t, ldt, group_max, nullptr, 0, nullptr, 0.0f,
-                                reinterpret_cast<hipStream_t>(stream));
+  return item_ce_probs_h("rb_item_ce_probs_h_t", false, true, seq_img, seq_exp, item_img,
+                         item_exp, target, lse, dloss, B, V, d, item_offset,
+                         {.pt = probs_t, .ldt = ldt, .item_max = group_max}, stream);
 }
 
 int rb_item_ce_probs_h_both(const void* seq_img, const int* seq_exp, const void* item_img,
@@ -572,51 +602,30 @@ int rb_item_ce_probs_h_both(const void* seq_img, const int* seq_exp, const void*
                             int64_t item_offset, float* probs, int64_t ld, float* probs_t,
                             int64_t ldt, float* row_group_max, float* item_group_max,
                             void* stream) {
-  if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
-  if (!target || !lse || !dloss || !probs || !probs_t || !row_group_max || !item_group_max)
-    return fail("rb_item_ce_probs_h_both: null pointer");
-  if (ld < V) return fail("rb_item_ce_probs_h_both: ld < V");
-  if (ldt < B || ldt % 4 || reinterpret_cast<uintptr_t>(probs_t) % 16)
-    return fail("rb_item_ce_probs_h_both: probs_t must be 16-B aligned with ldt >= B, ldt % 4 == 0");
-  return launch_item_ce_probs_h(seq_img, seq_exp, item_img, item_exp, target, lse, dloss, B, V, d,
-                                item_offset, probs_t, ldt, item_group_max, probs, ld,
-                                row_group_max, 0.0f, reinterpret_cast<hipStream_t>(stream));
+  return item_ce_probs_h("rb_item_ce_probs_h_both", true, true, seq_img, seq_exp, item_img,
+                         item_exp, target, lse, dloss, B, V, d, item_offset,
+                         {.p = probs, .ld = ld, .pt = probs_t, .ldt = ldt,
+                          .row_max = row_group_max, .item_max = item_group_max},
+                         stream);
 }
 
 // ---- include/recblr_dense.h: the all-position training loss -------------------------
-namespace {
-// the rows variants' normaliser: 1 / (live rows of the whole call)
-int check_inv_n(const char* fn, float inv_n) {
-  if (!(inv_n > 0.0f) || !(inv_n <= 1.0f)) return fail(fn, "inv_n must be in (0, 1]");
-  return 0;
-}
-}  // namespace
-
 int rb_item_ce_fwd_h_rows(const void* seq_img, const int* seq_exp, const void* item_img,
                           const int* item_exp, const int64_t* target, int64_t B, int64_t V,
                           int64_t d, float inv_n, int accumulate, float* lse, float* loss,
                           void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
-  if (!target || !lse || !loss || !workspace) return fail("rb_item_ce_fwd_h_rows: null pointer");
-  if (int rc = check_inv_n("rb_item_ce_fwd_h_rows", inv_n)) return rc;
-  if (accumulate != 0 && accumulate != 1)
-    return fail("rb_item_ce_fwd_h_rows: accumulate must be 0 or 1");
-  return launch_item_ce_fwd_h(seq_img, seq_exp, item_img, item_exp, target, B, V, d, lse, loss,
-                              workspace, workspace_bytes, true, inv_n, accumulate,
-                              reinterpret_cast<hipStream_t>(stream));
+  return item_ce_fwd_h("rb_item_ce_fwd_h_rows", true, seq_img, seq_exp, item_img, item_exp,
+                       target, B, V, d, inv_n, accumulate, lse, loss, workspace, workspace_bytes,
+                       stream);
 }
 
 int rb_item_ce_probs_h_rows(const void* seq_img, const int* seq_exp, const void* item_img,
                             const int* item_exp, const int64_t* target, const float* lse,
                             const float* dloss, float inv_n, int64_t B, int64_t V, int64_t d,
                             int64_t item_offset, float* probs, int64_t ld, void* stream) {
-  if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
-  if (!target || !lse || !dloss || !probs) return fail("rb_item_ce_probs_h_rows: null pointer");
-  if (int rc = check_inv_n("rb_item_ce_probs_h_rows", inv_n)) return rc;
-  if (ld < V) return fail("rb_item_ce_probs_h_rows: ld < V");
-  return launch_item_ce_probs_h(seq_img, seq_exp, item_img, item_exp, target, lse, dloss, B, V, d,
-                                item_offset, probs, ld, nullptr, nullptr, 0, nullptr, inv_n,
-                                reinterpret_cast<hipStream_t>(stream));
+  return item_ce_probs_h("rb_item_ce_probs_h_rows", true, false, seq_img, seq_exp, item_img,
+                         item_exp, target, lse, dloss, B, V, d, item_offset,
+                         {.p = probs, .ld = ld, .rows = true, .inv_n = inv_n}, stream);
 }
 
 int rb_item_ce_probs_h_both_rows(const void* seq_img, const int* seq_exp, const void* item_img,
@@ -625,17 +634,12 @@ int rb_item_ce_probs_h_both_rows(const void* seq_img, const int* seq_exp, const 
                                  int64_t item_offset, float* probs, int64_t ld, float* probs_t,
                                  int64_t ldt, float* row_group_max, float* item_group_max,
                                  void* stream) {
-  if (int rc = check_items_h(seq_img, seq_exp, item_img, item_exp, B, V, d)) return rc;
-  if (!target || !lse || !dloss || !probs || !probs_t || !row_group_max || !item_group_max)
-    return fail("rb_item_ce_probs_h_both_rows: null pointer");
-  if (int rc = check_inv_n("rb_item_ce_probs_h_both_rows", inv_n)) return rc;
-  if (ld < V) return fail("rb_item_ce_probs_h_both_rows: ld < V");
-  if (ldt < B || ldt % 4 || reinterpret_cast<uintptr_t>(probs_t) % 16)
-    return fail("rb_item_ce_probs_h_both_rows: probs_t must be 16-B aligned with ldt >= B, "
-                "ldt % 4 == 0");
-  return launch_item_ce_probs_h(seq_img, seq_exp, item_img, item_exp, target, lse, dloss, B, V, d,
-                                item_offset, probs_t, ldt, item_group_max, probs, ld,
-                                row_group_max, inv_n, reinterpret_cast<hipStream_t>(stream));
+  return item_ce_probs_h("rb_item_ce_probs_h_both_rows", true, true, seq_img, seq_exp, item_img,
+                         item_exp, target, lse, dloss, B, V, d, item_offset,
+                         {.p = probs, .ld = ld, .pt = probs_t, .ldt = ldt,
+                          .row_max = row_group_max, .item_max = item_group_max, .rows = true,
+                          .inv_n = inv_n},
+                         stream);
 }
 
 int rb_next_item_targets(const int64_t* ids, const int64_t* seq_offsets, const int64_t* order,

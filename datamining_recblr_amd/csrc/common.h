@@ -549,7 +549,7 @@ int launch_item_topk(const float* E, const float* W, int64_t B, int64_t V, int64
                      void* ws, int64_t ws_bytes, hipStream_t st);
 int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, const float* lse,
                          const float* dloss, int64_t B, int64_t V, int64_t D, int64_t v_off,
-                         int64_t n_total, float* out, int64_t ld, hipStream_t st);
+                         float* out, int64_t ld, hipStream_t st);
 int launch_item_scores(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
                        float* out, hipStream_t st);
 int launch_item_split_h(const float* X, int64_t N, int64_t D, void* img, int* ex, float* gmax,
@@ -558,10 +558,23 @@ int launch_item_ce_fwd_h(const void* Ei, const int* Ee, const void* Wi, const in
                          const int64_t* tgt, int64_t B, int64_t V, int64_t D, float* lse,
                          float* loss, void* ws, int64_t ws_bytes, bool rows_mode, float inv_n,
                          int accumulate, hipStream_t st);
+// What rb_item_ce_probs_h* writes.  p: P [B, ld]; pt: P^T [V, ldt]; either may
+// be null, and with both set row_max / item_max take every 32-row / 32-item
+// group's max |P| (item_max alone goes with pt alone).  rows: a target of -1 is
+// an ignored row and P is scaled by inv_n, not by 1 / B.
+struct CeProbsOut {
+  float* p;
+  int64_t ld;
+  float* pt;
+  int64_t ldt;
+  float* row_max;
+  float* item_max;
+  bool rows;
+  float inv_n;
+};
 int launch_item_ce_probs_h(const void* Ei, const int* Ee, const void* Wi, const int* We,
                            const int64_t* tgt, const float* lse, const float* dloss, int64_t B,
-                           int64_t V, int64_t D, int64_t v_off, float* out, int64_t ld,
-                           float* gmax, float* out2, int64_t ld2, float* bmax, float rows_inv_n,
+                           int64_t V, int64_t D, int64_t v_off, const CeProbsOut& o,
                            hipStream_t st);
 int launch_group_absmax(const float* x, int64_t n, int64_t c, int64_t ld, float* out,
                         hipStream_t st);

@@ -1351,34 +1351,51 @@ void ce_fwd_h_t(const void* Ei, const int* Ee, const void* Wi, const int* We, co
                      ticket);
 }
 
-template <int D>
-void probs_h_t(const void* Ei, const int* Ee, const void* Wi, const int* We, int64_t B, int64_t V,
-               const Grid2& g, float* out, int64_t ld, const float* lse, const int64_t* tgt,
-               const float* dloss, float inv_n, int64_t v_off, float* gmax, float* out2,
-               int64_t ld2, float* bmax, bool rows_mode, hipStream_t st) {
-  if (rows_mode && out2)
-    hipLaunchKernelGGL((k_ce_probs_h<D, 2, true>), dim3(g.wgs()), dim3(256), 0, st,
-                       (const _Float16*)Ei, Ee, (const _Float16*)Wi, We, B, V, g.per, g.blocks,
-                       g.splits, out, ld, lse, tgt, dloss, inv_n, v_off, gmax, out2, ld2, bmax);
-  else if (rows_mode)   // row-major P only (the launcher rejects P^T alone)
-    hipLaunchKernelGGL((k_ce_probs_h<D, 0, true>), dim3(g.wgs()), dim3(256), 0, st,
-                       (const _Float16*)Ei, Ee, (const _Float16*)Wi, We, B, V, g.per, g.blocks,
-                       g.splits, out, ld, lse, tgt, dloss, inv_n, v_off, nullptr, nullptr,
-                       (int64_t)0, nullptr);
-  else if (out2)
-    hipLaunchKernelGGL((k_ce_probs_h<D, 2>), dim3(g.wgs()), dim3(256), 0, st,
-                       (const _Float16*)Ei, Ee, (const _Float16*)Wi, We, B, V, g.per, g.blocks,
-                       g.splits, out, ld, lse, tgt, dloss, inv_n, v_off, gmax, out2, ld2, bmax);
-  else if (gmax)
-    hipLaunchKernelGGL((k_ce_probs_h<D, 1>), dim3(g.wgs()), dim3(256), 0, st,
-                       (const _Float16*)Ei, Ee, (const _Float16*)Wi, We, B, V, g.per, g.blocks,
-                       g.splits, out, ld, lse, tgt, dloss, inv_n, v_off, gmax, nullptr,
-                       (int64_t)0, nullptr);
-  else
-    hipLaunchKernelGGL((k_ce_probs_h<D, 0>), dim3(g.wgs()), dim3(256), 0, st,
-                       (const _Float16*)Ei, Ee, (const _Float16*)Wi, We, B, V, g.per, g.blocks,
-                       g.splits, out, ld, lse, tgt, dloss, inv_n, v_off, gmax, nullptr,
-                       (int64_t)0, nullptr);
+// The one launch of k_ce_probs_h.  The kernel's first output is P^T whenever it
+// writes one (MODE 1, 2), with P second in MODE 2; MODE 0 writes P alone.
+template <int D, int MODE, bool ROWS>
+void probs_h_launch(const void* Ei, const int* Ee, const void* Wi, const int* We, int64_t B,
+                    int64_t V, const Grid2& g, const CeProbsOut& o, const float* lse,
+                    const int64_t* tgt, const float* dloss, float inv_n, int64_t v_off,
+                    hipStream_t st) {
+  constexpr bool TR = MODE != 0, BOTH = MODE == 2;
+  hipLaunchKernelGGL((k_ce_probs_h<D, MODE, ROWS>), dim3(g.wgs()), dim3(256), 0, st,
+                     (const _Float16*)Ei, Ee, (const _Float16*)Wi, We, B, V, g.per, g.blocks,
+                     g.splits, TR ? o.pt : o.p, TR ? o.ldt : o.ld, lse, tgt, dloss, inv_n, v_off,
+                     TR ? o.item_max : nullptr, BOTH ? o.p : nullptr, BOTH ? o.ld : (int64_t)0,
+                     BOTH ? o.row_max : nullptr);
+}
+
+// mode: 0 P, 1 P^T, 2 both (launch_item_ce_probs_h rejects rows with mode 1)
+template <int D, class... Args>
+void probs_h_t(int mode, bool rows, Args... a) {
+  if (rows && mode == 2) probs_h_launch<D, 2, true>(a...);
+  else if (rows) probs_h_launch<D, 0, true>(a...);
+  else if (mode == 2) probs_h_launch<D, 2, false>(a...);
+  else if (mode == 1) probs_h_launch<D, 1, false>(a...);
+  else probs_h_launch<D, 0, false>(a...);
+}
+
+// The forward's two passes over one workspace: `partials` (k_ce_fwd or
+// k_ce_fwd_h, by d) leaves each item split's running max and sum, and
+// k_ce_rows<ROWS> folds them into lse and the loss.
+template <bool ROWS, class Partials>
+int ce_fwd_passes(const char* fn, const int64_t* tgt, int64_t B, int64_t V, int64_t D, float* lse,
+                  float* loss, void* ws, int64_t ws_bytes, float inv_n, int accumulate,
+                  hipStream_t st, Partials partials) {
+  const CeWs L = ce_layout(B, V, D);
+  if (ws_bytes < (int64_t)L.total) return fail((std::string(fn) + ": workspace too small").c_str());
+  char* w = static_cast<char*>(ws);
+  float* ts = reinterpret_cast<float*>(w + L.ts);
+  float* m = reinterpret_cast<float*>(w + L.m);
+  float* s = reinterpret_cast<float*>(w + L.s);
+  float* rows = reinterpret_cast<float*>(w + L.rows);
+  unsigned* ticket = reinterpret_cast<unsigned*>(w + L.ticket);
+  const Grid2 g = plan(B, ntiles(V));
+  if (int rc = partials(g, m, s, ts, ticket)) return rc;
+  hipLaunchKernelGGL(k_ce_rows<ROWS>, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, m, s,
+                     g.splits, ts, tgt, B, V, lse, rows, ticket, loss, inv_n, accumulate);
+  return launch_status(fn);
 }
 
 void sum_parts(const float* parts, int64_t P, int64_t n, float* out, hipStream_t st) {
@@ -1400,19 +1417,12 @@ int64_t item_rank_workspace_bytes(int64_t B, int64_t V) {
 int launch_item_ce_fwd(const float* E, const float* W, const int64_t* tgt, int64_t B, int64_t V,
                        int64_t D, float* lse, float* loss, void* ws, int64_t ws_bytes,
                        hipStream_t st) {
-  const CeWs L = ce_layout(B, V, D);
-  if (ws_bytes < (int64_t)L.total) return fail("rb_item_ce_fwd: workspace too small");
-  char* w = static_cast<char*>(ws);
-  float* ts = reinterpret_cast<float*>(w + L.ts);
-  float* m = reinterpret_cast<float*>(w + L.m);
-  float* s = reinterpret_cast<float*>(w + L.s);
-  float* rows = reinterpret_cast<float*>(w + L.rows);
-  const Grid2 g = plan(B, ntiles(V));
-  unsigned* ticket = reinterpret_cast<unsigned*>(w + L.ticket);
-  RB_ITEM_DISPATCH(D, ce_fwd_t, E, W, tgt, B, V, g, m, s, ts, ticket, st);
-  hipLaunchKernelGGL(k_ce_rows<false>, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, m,
-                     s, g.splits, ts, tgt, B, V, lse, rows, ticket, loss, 0.0f, 0);
-  return launch_status("rb_item_ce_fwd");
+  return ce_fwd_passes<false>(
+      "rb_item_ce_fwd", tgt, B, V, D, lse, loss, ws, ws_bytes, 0.0f, 0, st,
+      [&](const Grid2& g, float* m, float* s, float* ts, unsigned* ticket) {
+        RB_ITEM_DISPATCH(D, ce_fwd_t, E, W, tgt, B, V, g, m, s, ts, ticket, st);
+        return 0;
+      });
 }
 
 int launch_item_ce_bwd(const float* E, const float* W, const int64_t* tgt, const float* lse,
@@ -1475,10 +1485,9 @@ int launch_item_topk(const float* E, const float* W, int64_t B, int64_t V, int64
 
 int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, const float* lse,
                          const float* dloss, int64_t B, int64_t V, int64_t D, int64_t v_off,
-                         int64_t n_total, float* out, int64_t ld, hipStream_t st) {
+                         float* out, int64_t ld, hipStream_t st) {
   const Grid2 g = plan(B, ntiles(V));
   const float inv_n = 1.0f / (float)B;
-  (void)n_total;
   RB_ITEM_DISPATCH(D, probs_t, E, W, B, V, g, out, ld, lse, tgt, dloss, inv_n, v_off, st);
   return launch_status("rb_item_ce_probs");
 }
@@ -1501,44 +1510,32 @@ int launch_item_ce_fwd_h(const void* Ei, const int* Ee, const void* Wi, const in
                          const int64_t* tgt, int64_t B, int64_t V, int64_t D, float* lse,
                          float* loss, void* ws, int64_t ws_bytes, bool rows_mode, float inv_n,
                          int accumulate, hipStream_t st) {
-  const CeWs L = ce_layout(B, V, D);
-  if (ws_bytes < (int64_t)L.total)
-    return fail(rows_mode ? "rb_item_ce_fwd_h_rows: workspace too small"
-                          : "rb_item_ce_fwd_h: workspace too small");
-  char* w = static_cast<char*>(ws);
-  float* ts = reinterpret_cast<float*>(w + L.ts);
-  float* m = reinterpret_cast<float*>(w + L.m);
-  float* s = reinterpret_cast<float*>(w + L.s);
-  float* rows = reinterpret_cast<float*>(w + L.rows);
-  const Grid2 g = plan(B, ntiles(V));
-  unsigned* ticket = reinterpret_cast<unsigned*>(w + L.ticket);
-  RB_ITEM_DISPATCH(D, ce_fwd_h_t, Ei, Ee, Wi, We, tgt, B, V, g, m, s, ts, ticket, st);
-  if (rows_mode) {
-    hipLaunchKernelGGL(k_ce_rows<true>, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, m, s,
-                       g.splits, ts, tgt, B, V, lse, rows, ticket, loss, inv_n, accumulate);
-    return launch_status("rb_item_ce_fwd_h_rows");
-  }
-  hipLaunchKernelGGL(k_ce_rows<false>, dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, m,
-                     s, g.splits, ts, tgt, B, V, lse, rows, ticket, loss, 0.0f, 0);
-  return launch_status("rb_item_ce_fwd_h");
+  const auto partials = [&](const Grid2& g, float* m, float* s, float* ts, unsigned* ticket) {
+    RB_ITEM_DISPATCH(D, ce_fwd_h_t, Ei, Ee, Wi, We, tgt, B, V, g, m, s, ts, ticket, st);
+    return 0;
+  };
+  if (rows_mode)
+    return ce_fwd_passes<true>("rb_item_ce_fwd_h_rows", tgt, B, V, D, lse, loss, ws, ws_bytes,
+                               inv_n, accumulate, st, partials);
+  return ce_fwd_passes<false>("rb_item_ce_fwd_h", tgt, B, V, D, lse, loss, ws, ws_bytes, 0.0f, 0,
+                              st, partials);
 }
 
 int launch_item_ce_probs_h(const void* Ei, const int* Ee, const void* Wi, const int* We,
                            const int64_t* tgt, const float* lse, const float* dloss, int64_t B,
-                           int64_t V, int64_t D, int64_t v_off, float* out, int64_t ld,
-                           float* gmax, float* out2, int64_t ld2, float* bmax, float rows_inv_n,
+                           int64_t V, int64_t D, int64_t v_off, const CeProbsOut& o,
                            hipStream_t st) {
-  // rows_inv_n > 0: the rows variants (ignorable rows, the caller's
-  // normaliser); 0: the batch mean of the entry points without them
-  const bool rows_mode = rows_inv_n > 0.0f;
-  if (rows_mode && gmax && !out2) return fail("rb_item_ce_probs_h_rows: no transposed-only form");
+  const int mode = o.pt ? (o.p ? 2 : 1) : 0;
+  if (o.rows && mode == 1) return fail("rb_item_ce_probs_h_rows: no transposed-only form");
+  static const char* const kNames[2][3] = {
+      {"rb_item_ce_probs_h", "rb_item_ce_probs_h_t", "rb_item_ce_probs_h_both"},
+      {"rb_item_ce_probs_h_rows", nullptr, "rb_item_ce_probs_h_both_rows"}};
   const Grid2 g = plan(B, ntiles(V));
-  const float inv_n = rows_mode ? rows_inv_n : 1.0f / (float)B;
-  RB_ITEM_DISPATCH(D, probs_h_t, Ei, Ee, Wi, We, B, V, g, out, ld, lse, tgt, dloss, inv_n, v_off,
-                   gmax, out2, ld2, bmax, rows_mode, st);
-  if (rows_mode) return launch_status(out2 ? "rb_item_ce_probs_h_both_rows" : "rb_item_ce_probs_h_rows");
-  return launch_status(out2 ? "rb_item_ce_probs_h_both"
-                            : gmax ? "rb_item_ce_probs_h_t" : "rb_item_ce_probs_h");
+  // the rows forms take the caller's normaliser, the others the batch mean
+  const float inv_n = o.rows ? o.inv_n : 1.0f / (float)B;
+  RB_ITEM_DISPATCH(D, probs_h_t, mode, o.rows, Ei, Ee, Wi, We, B, V, g, o, lse, tgt, dloss, inv_n,
+                   v_off, st);
+  return launch_status(kNames[o.rows][mode]);
 }
 
 int launch_item_scores(const float* E, const float* W, int64_t B, int64_t V, int64_t D,

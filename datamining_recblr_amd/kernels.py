@@ -743,11 +743,9 @@ def item_ce_fwd(seq, items, target):
 def item_ce_bwd(seq, items, target, lse, dloss, want_seq=True, want_items=True):
     """(dseq, ditems) of item_ce_fwd for the scalar upstream gradient dloss."""
     seq, items, target = _item_operands(seq, items, target)
-    _check(lse, "lse")
-    _check(dloss, "dloss")
+    lse, dloss = _grad_scalars(lse, dloss)
     B, d = seq.shape
     V = items.shape[0]
-    dloss = dloss.reshape(1).contiguous()
     lib = _lib.load()
     ws_bytes = int(lib.rb_item_ce_workspace(B, V, d))
     ws = torch.empty((ws_bytes,), device=seq.device, dtype=torch.uint8)
@@ -755,29 +753,41 @@ def item_ce_bwd(seq, items, target, lse, dloss, want_seq=True, want_items=True):
     ditems = torch.empty_like(items) if want_items else None
     flops = 2 * B * V * d * (int(want_seq) + int(want_items))
     _launch("rb_item_ce_bwd", flops, seq.data_ptr(), items.data_ptr(), target.data_ptr(),
-            lse.contiguous().data_ptr(), dloss.data_ptr(), B, V, d,
+            lse.data_ptr(), dloss.data_ptr(), B, V, d,
             dseq.data_ptr() if dseq is not None else None,
             ditems.data_ptr() if ditems is not None else None, ws.data_ptr(), ws_bytes,
             _stream(seq), _flops=True)
     return dseq, ditems
 
 
+def _grad_scalars(lse, dloss):
+    """lse [B] and the scalar dloss as the contiguous arrays the kernels read."""
+    _check(lse, "lse")
+    _check(dloss, "dloss")
+    return lse.contiguous(), dloss.reshape(1).contiguous()
+
+
+def _probs_out(out, B, V, dev):
+    """The caller's [B, V] buffer for P (any row stride), or a fresh one."""
+    if out is None:
+        out = torch.empty((B, V), device=dev, dtype=torch.float32)
+    _check(out, "probs")
+    if out.shape != (B, V) or out.stride(1) != 1:
+        raise ValueError("probs must be [B, V] with unit column stride")
+    return out
+
+
 def item_ce_probs(seq, items, target, lse, dloss, item_offset=0, out=None):
     """P = (softmax - onehot) * dloss / B for the item rows `items` =
     table[item_offset : item_offset + V] ([B, V], row stride of `out`)."""
     seq, items, target = _item_operands(seq, items, target)
-    _check(lse, "lse")
-    _check(dloss, "dloss")
+    lse, dloss = _grad_scalars(lse, dloss)
     B, d = seq.shape
     V = items.shape[0]
-    if out is None:
-        out = torch.empty((B, V), device=seq.device, dtype=torch.float32)
-    _check(out, "probs")
-    if out.shape != (B, V) or out.stride(1) != 1:
-        raise ValueError("probs must be [B, V] with unit column stride")
+    out = _probs_out(out, B, V, seq.device)
     _launch("rb_item_ce_probs", 2 * B * V * d, seq.data_ptr(), items.data_ptr(),
-            target.data_ptr(), lse.contiguous().data_ptr(), dloss.reshape(1).contiguous().data_ptr(),
-            B, V, d, int(item_offset), out.data_ptr(), out.stride(0), _stream(seq), _flops=True)
+            target.data_ptr(), lse.data_ptr(), dloss.data_ptr(), B, V, d, int(item_offset),
+            out.data_ptr(), out.stride(0), _stream(seq), _flops=True)
     return out
 
 
@@ -830,6 +840,41 @@ def _split_operands(seq, items, target):
     return B, items.shape[0], d, target.contiguous()
 
 
+def _ce_probs_h_args(seq, items, target, lse, dloss, *, inv_n=None, item_offset=0, out=None,
+                     layout="p", pad_to=1):
+    """(_launch's arguments after the name, the outputs) of rb_item_ce_probs_h*.
+    layout "p": P [B, V] (into `out` if given); "t": (P^T [V, B], gmax);
+    "both": (P [B, Vp], P^T, bmax, gmax) with P's columns padded to a multiple
+    of pad_to.  bmax [ceil(B/32)] and gmax [ceil(V/32)] are atomic maxima and
+    start at zero.  inv_n: the rows entry points' normaliser (None for the
+    others)."""
+    B, V, d, target = _split_operands(seq, items, target)
+    lse, dloss = _grad_scalars(lse, dloss)
+    dev = seq.img.device
+    nb, ng = (B + 31) // 32, (V + 31) // 32
+    ldt = (B + 3) // 4 * 4
+    if layout == "p":
+        outs = p = _probs_out(out, B, V, dev)
+        tail = (p.data_ptr(), p.stride(0))
+    elif layout == "t":
+        pt = torch.empty((V, ldt), device=dev, dtype=torch.float32)[:, :B]
+        gmax = torch.zeros(ng, device=dev, dtype=torch.float32)
+        outs = (pt, gmax)
+        tail = (pt.data_ptr(), ldt, gmax.data_ptr())
+    else:
+        Vp = (V + pad_to - 1) // pad_to * pad_to
+        p = torch.empty((B, Vp), device=dev, dtype=torch.float32)   # pad columns zeroed in-kernel
+        pt = torch.empty((V, ldt), device=dev, dtype=torch.float32)[:, :B]
+        maxes = torch.zeros(nb + ng, device=dev, dtype=torch.float32)
+        bmax, gmax = maxes[:nb], maxes[nb:]
+        outs = (p, pt, bmax, gmax)
+        tail = (p.data_ptr(), Vp, pt.data_ptr(), ldt, bmax.data_ptr(), gmax.data_ptr())
+    rows = () if inv_n is None else (_check_inv_n(inv_n),)
+    return (2 * B * V * d, seq.img.data_ptr(), seq.exps.data_ptr(), items.img.data_ptr(),
+            items.exps.data_ptr(), target.data_ptr(), lse.data_ptr(), dloss.data_ptr(), *rows,
+            B, V, d, int(item_offset), *tail, _stream(seq.img)), outs
+
+
 def item_ce_fwd_h(seq: SplitRows, items: SplitRows, target):
     """item_ce_fwd on split images (the f16 MFMA pipe): (loss, lse)."""
     B, V, d, target = _split_operands(seq, items, target)
@@ -849,38 +894,19 @@ def item_ce_probs_h(seq: SplitRows, items: SplitRows, target, lse, dloss, item_o
                     out=None):
     """item_ce_probs on split images; items = the table image's rows
     [item_offset, item_offset + V) (SplitRows.rows)."""
-    B, V, d, target = _split_operands(seq, items, target)
-    _check(lse, "lse")
-    _check(dloss, "dloss")
-    dev = seq.img.device
-    if out is None:
-        out = torch.empty((B, V), device=dev, dtype=torch.float32)
-    _check(out, "probs")
-    if out.shape != (B, V) or out.stride(1) != 1:
-        raise ValueError("probs must be [B, V] with unit column stride")
-    _launch("rb_item_ce_probs_h", 2 * B * V * d, seq.img.data_ptr(), seq.exps.data_ptr(),
-            items.img.data_ptr(), items.exps.data_ptr(), target.data_ptr(),
-            lse.contiguous().data_ptr(), dloss.reshape(1).contiguous().data_ptr(), B, V, d,
-            int(item_offset), out.data_ptr(), out.stride(0), _stream(seq.img), _flops=True)
-    return out
+    args, p = _ce_probs_h_args(seq, items, target, lse, dloss, item_offset=item_offset, out=out)
+    _launch("rb_item_ce_probs_h", *args, _flops=True)
+    return p
 
 
 def item_ce_probs_h_t(seq: SplitRows, items: SplitRows, target, lse, dloss, item_offset=0):
     """item_ce_probs_h transposed (rb_item_ce_probs_h_t): (P^T [V, B], gmax
     [ceil(V/32)]) with gmax the max |P| of every 32-item group — the operands
     of dseq = P W (rb_gemm_tn_h) and ditems = P^T seq (rb_gemm_nt_h)."""
-    B, V, d, target = _split_operands(seq, items, target)
-    _check(lse, "lse")
-    _check(dloss, "dloss")
-    dev = seq.img.device
-    ldt = (B + 3) // 4 * 4
-    pt = torch.empty((V, ldt), device=dev, dtype=torch.float32)[:, :B]
-    gmax = torch.zeros((V + 31) // 32, device=dev, dtype=torch.float32)
-    _launch("rb_item_ce_probs_h_t", 2 * B * V * d, seq.img.data_ptr(), seq.exps.data_ptr(),
-            items.img.data_ptr(), items.exps.data_ptr(), target.data_ptr(),
-            lse.contiguous().data_ptr(), dloss.reshape(1).contiguous().data_ptr(), B, V, d,
-            int(item_offset), pt.data_ptr(), ldt, gmax.data_ptr(), _stream(seq.img), _flops=True)
-    return pt, gmax
+    args, outs = _ce_probs_h_args(seq, items, target, lse, dloss, item_offset=item_offset,
+                                  layout="t")
+    _launch("rb_item_ce_probs_h_t", *args, _flops=True)
+    return outs
 
 
 def item_ce_probs_h_both(seq: SplitRows, items: SplitRows, target, lse, dloss, item_offset=0,
@@ -889,22 +915,10 @@ def item_ce_probs_h_both(seq: SplitRows, items: SplitRows, target, lse, dloss, i
     (rb_item_ce_probs_h_both): (P [B, Vp], P^T [V, B], bmax [ceil(B/32)],
     gmax [ceil(V/32)]) — P's columns padded with zeros to Vp = V rounded up to
     pad_to; bmax / gmax the max |P| of every 32-row / 32-item group."""
-    B, V, d, target = _split_operands(seq, items, target)
-    _check(lse, "lse")
-    _check(dloss, "dloss")
-    dev = seq.img.device
-    Vp = (V + pad_to - 1) // pad_to * pad_to
-    p = torch.empty((B, Vp), device=dev, dtype=torch.float32)   # pad columns zeroed in-kernel
-    ldt = (B + 3) // 4 * 4
-    pt = torch.empty((V, ldt), device=dev, dtype=torch.float32)[:, :B]
-    maxes = torch.zeros((B + 31) // 32 + (V + 31) // 32, device=dev, dtype=torch.float32)
-    bmax, gmax = maxes[:(B + 31) // 32], maxes[(B + 31) // 32:]
-    _launch("rb_item_ce_probs_h_both", 2 * B * V * d, seq.img.data_ptr(), seq.exps.data_ptr(),
-            items.img.data_ptr(), items.exps.data_ptr(), target.data_ptr(),
-            lse.contiguous().data_ptr(), dloss.reshape(1).contiguous().data_ptr(), B, V, d,
-            int(item_offset), p.data_ptr(), Vp, pt.data_ptr(), ldt, bmax.data_ptr(),
-            gmax.data_ptr(), _stream(seq.img), _flops=True)
-    return p, pt, bmax, gmax
+    args, outs = _ce_probs_h_args(seq, items, target, lse, dloss, item_offset=item_offset,
+                                  layout="both", pad_to=pad_to)
+    _launch("rb_item_ce_probs_h_both", *args, _flops=True)
+    return outs
 
 
 # ---- the same three with ignorable rows (include/recblr_dense.h) -------------------
@@ -951,20 +965,10 @@ def item_ce_probs_h_rows(seq: SplitRows, items: SplitRows, target, lse, dloss, i
                          item_offset=0, out=None):
     """item_ce_probs_h with ignorable rows and the caller's normaliser
     (rb_item_ce_probs_h_rows): an ignored row's P is exactly 0."""
-    B, V, d, target = _split_operands(seq, items, target)
-    _check(lse, "lse")
-    _check(dloss, "dloss")
-    if out is None:
-        out = torch.empty((B, V), device=seq.img.device, dtype=torch.float32)
-    _check(out, "probs")
-    if out.shape != (B, V) or out.stride(1) != 1:
-        raise ValueError("probs must be [B, V] with unit column stride")
-    _launch("rb_item_ce_probs_h_rows", 2 * B * V * d, seq.img.data_ptr(), seq.exps.data_ptr(),
-            items.img.data_ptr(), items.exps.data_ptr(), target.data_ptr(),
-            lse.contiguous().data_ptr(), dloss.reshape(1).contiguous().data_ptr(),
-            _check_inv_n(inv_n), B, V, d, int(item_offset), out.data_ptr(), out.stride(0),
-            _stream(seq.img), _flops=True)
-    return out
+    args, p = _ce_probs_h_args(seq, items, target, lse, dloss, inv_n=inv_n,
+                               item_offset=item_offset, out=out)
+    _launch("rb_item_ce_probs_h_rows", *args, _flops=True)
+    return p
 
 
 def item_ce_probs_h_both_rows(seq: SplitRows, items: SplitRows, target, lse, dloss, inv_n: float,
@@ -972,22 +976,10 @@ def item_ce_probs_h_both_rows(seq: SplitRows, items: SplitRows, target, lse, dlo
     """item_ce_probs_h_both with ignorable rows and the caller's normaliser
     (rb_item_ce_probs_h_both_rows): (P [B, Vp], P^T [V, B], bmax, gmax), an
     ignored row exactly 0 in both layouts and in both group maxima."""
-    B, V, d, target = _split_operands(seq, items, target)
-    _check(lse, "lse")
-    _check(dloss, "dloss")
-    dev = seq.img.device
-    Vp = (V + pad_to - 1) // pad_to * pad_to
-    p = torch.empty((B, Vp), device=dev, dtype=torch.float32)   # pad columns zeroed in-kernel
-    ldt = (B + 3) // 4 * 4
-    pt = torch.empty((V, ldt), device=dev, dtype=torch.float32)[:, :B]
-    maxes = torch.zeros((B + 31) // 32 + (V + 31) // 32, device=dev, dtype=torch.float32)
-    bmax, gmax = maxes[:(B + 31) // 32], maxes[(B + 31) // 32:]
-    _launch("rb_item_ce_probs_h_both_rows", 2 * B * V * d, seq.img.data_ptr(),
-            seq.exps.data_ptr(), items.img.data_ptr(), items.exps.data_ptr(), target.data_ptr(),
-            lse.contiguous().data_ptr(), dloss.reshape(1).contiguous().data_ptr(),
-            _check_inv_n(inv_n), B, V, d, int(item_offset), p.data_ptr(), Vp, pt.data_ptr(), ldt,
-            bmax.data_ptr(), gmax.data_ptr(), _stream(seq.img), _flops=True)
-    return p, pt, bmax, gmax
+    args, outs = _ce_probs_h_args(seq, items, target, lse, dloss, inv_n=inv_n,
+                                  item_offset=item_offset, layout="both", pad_to=pad_to)
+    _launch("rb_item_ce_probs_h_both_rows", *args, _flops=True)
+    return outs
 
 
 def group_absmax(x: torch.Tensor) -> torch.Tensor:

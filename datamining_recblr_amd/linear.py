@@ -395,11 +395,16 @@ _tn_few = os.environ.get("RECBLR_TN_FEW", "1") != "0"
 _ncus = {}
 
 
-def _tn_splits(dev, nt: int) -> int:
+def _num_cus(dev) -> int:
+    """The device's compute-unit count (asked of the runtime once per device)."""
     n = _ncus.get(dev)
     if n is None:
         n = _ncus[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
-    return max(8, (2 * n // nt) // 8 * 8)   # ~2 workgroups per CU, a multiple of 8
+    return n
+
+
+def _tn_splits(dev, nt: int) -> int:
+    return max(8, (2 * _num_cus(dev) // nt) // 8 * 8)   # ~2 workgroups per CU, a multiple of 8
 
 
 def wgrad(dy2: torch.Tensor, x2: torch.Tensor, splits: int = SPLIT_K,

@@ -40,7 +40,8 @@ import os
 import torch
 import torch.nn.functional as F
 
-from . import kernels
+from . import kernels, linear
+from .linear import _timed
 
 __all__ = ["item_cross_entropy", "item_cross_entropy_rows", "full_sort_scores", "target_ranks", "rank_metrics",
            "top_items", "supported", "pair_loss", "pair_loss_reference", "candidate_scores",
@@ -98,17 +99,18 @@ GEMM_TN_MAX_N = 65536
 def _tn_splits8(dev, nt: int, div: int = 1) -> int:
     """linear._tn_splits(dev, nt) // div rounded down to a multiple of 8
     (rb_gemm_tn_h takes row splits in multiples of 8), at least 8."""
-    from .linear import _tn_splits
-    return max(8, _tn_splits(dev, nt) // div // 8 * 8)
+    return max(8, linear._tn_splits(dev, nt) // div // 8 * 8)
 
 
-def _f16_grads_ok(seq, table) -> bool:
-    """The logits' input gradients as f16x3 GEMMs (_bwd_f16): B a multiple of
-    256 (the weight-gradient kernel's N; its row splits), d of 128, both
+def _f16_grads_ok(seq, table, rows: int | None = None) -> bool:
+    """The logits' input gradients as f16x3 GEMMs (_f16_products): B a multiple
+    of 256 (the weight-gradient kernel's N; its row splits), d of 128, both
     layouts of P within twice PROBS_SLICE_BYTES, the padded item count within
-    the weight-gradient kernel's N limit."""
-    from . import linear
+    the weight-gradient kernel's N limit.  rows: P's row count B when it is not
+    seq's (_ItemCERows: one chunk)."""
     B, d = seq.shape
+    if rows is not None:
+        B = rows
     V = table.shape[0]
     return (CE_GRADS == "f16" and linear.gemm_format() == "f16x3" and B % 256 == 0
             and d % 128 == 0 and table.stride(1) == 1 and table.data_ptr() % 16 == 0
@@ -127,10 +129,7 @@ def _round_splits(dev, nt: int, rows: int) -> int:
     steps of fixed cost); the smallest such count (fewer partials to sum).
     The item table's product at B = 2,048: 42 tiles x 6 splits in one round
     instead of 8 splits in 1.3."""
-    from .linear import _ncus
-    n = _ncus.get(dev)
-    if n is None:
-        n = _ncus[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
+    n = linear._num_cus(dev)
     best, best_cost = 1, None
     for s in range(1, max(1, rows // 32) + 1):
         cost = -(-nt * s // n) * (-(-(-(-rows // s)) // 32) + 3)
@@ -146,41 +145,52 @@ def _group_max(x: torch.Tensor) -> torch.Tensor:
     return F.pad(m, (0, (-m.numel()) % 32)).view(-1, 32).amax(1)
 
 
-def _bwd_f16(seq, table, target, lse, dloss, want_seq, want_items, split):
-    """The logits' gradient in both layouts from one pass
-    (rb_item_ce_probs_h_both: P [B, Vp] with its 32-row group maxima, P^T
-    [V, B] with its 32-item group maxima) and both products as the f16x3
-    weight-gradient GEMM (rb_gemm_tn_h, fixed-order row-chunk partials, a
-    column sum): ditems = P^T seq reduced over P's batch rows, dseq = P W over
-    P^T's item rows — no library GEMM."""
-    from .linear import _timed
+def _batch_splits(dev, nt: int, rows: int) -> int:
+    """_round_splits, or round 5's count under RECBLR_CE_ROUND_SPLITS=0."""
+    if _ROUND_SPLITS:
+        return _round_splits(dev, nt, rows)
+    return max(8, min(_tn_splits8(dev, nt), rows // 256 // 8 * 8))
 
-    B, d = seq.shape
+
+def _f16_products(probs, rows, rmax, table, tmax, want_seq, want_items, splits):
+    """(drows [n, d], dtable [V, d]) from probs = (P [n, Vp], P^T [V, n], bmax,
+    gmax) of one rb_item_ce_probs_h_both* pass, both as the f16x3
+    weight-gradient GEMM (rb_gemm_tn_h, fixed-order row-chunk partials, a
+    column sum): dtable = P^T rows reduced over P's rows, drows = P table over
+    P^T's item rows — no library GEMM.  rmax / tmax: the 32-row group maxima of
+    rows / table (None: computed here); splits(dev, nt, n): the split count of
+    the table's product."""
+    p, pt, bmax, gmax = probs
+    n, d = rows.shape
     V = table.shape[0]
-    s_seq, s_tab = split
-    p, pt, bmax, gmax = kernels.item_ce_probs_h_both(s_seq, s_tab, target, lse, dloss,
-                                                     pad_to=256)
-    fl = 2 * B * V * d
-    dseq = dtable = None
+    fl = 2 * n * V * d
+    drows = dtable = None
     if want_items:
         Vp = p.shape[1]
-        nt = (Vp // 256) * (d // 128)
-        S1 = (_round_splits(seq.device, nt, B) if _ROUND_SPLITS
-              else max(8, min(_tn_splits8(seq.device, nt), B // 256 // 8 * 8)))
-        smax = s_seq.gmax if s_seq.gmax is not None else kernels.group_absmax(seq)
-        parts = _timed("gemm", fl, kernels.gemm_tn_h, p, seq, bmax, smax, S1)
+        S1 = splits(rows.device, (Vp // 256) * (d // 128), n)
+        if rmax is None:
+            rmax = kernels.group_absmax(rows)
+        parts = _timed("gemm", fl, kernels.gemm_tn_h, p, rows, bmax, rmax, S1)
         dtable = kernels.colsum(parts.view(S1, -1)).view(Vp, d)[:V]
     if want_seq:
-        S2 = _tn_splits8(seq.device, (B // 256) * (d // 128), div=2)
-        tmax = s_tab.gmax if s_tab.gmax is not None else kernels.group_absmax(table)
+        S2 = _tn_splits8(rows.device, (n // 256) * (d // 128), div=2)
+        if tmax is None:
+            tmax = kernels.group_absmax(table)
         parts = _timed("gemm", fl, kernels.gemm_tn_h, pt, table, gmax, tmax, S2)
-        dseq = kernels.colsum(parts.view(S2, -1)).view(B, d)
-    return dseq, dtable
+        drows = kernels.colsum(parts.view(S2, -1)).view(n, d)
+    return drows, dtable
+
+
+def _bwd_f16(seq, table, target, lse, dloss, want_seq, want_items, split):
+    """The logits' gradient in both layouts from one pass
+    (rb_item_ce_probs_h_both) and both input gradients from it (_f16_products)."""
+    s_seq, s_tab = split
+    probs = kernels.item_ce_probs_h_both(s_seq, s_tab, target, lse, dloss, pad_to=256)
+    return _f16_products(probs, seq, s_seq.gmax, table, s_tab.gmax, want_seq, want_items,
+                         _batch_splits)
 
 
 def _bwd_slices(seq, table, target, lse, dloss, want_seq, want_items, split=None):
-    from .linear import _timed
-
     B, d = seq.shape
     V = table.shape[0]
     vc = max(32, min(V, PROBS_SLICE_BYTES // (4 * B)))
@@ -250,16 +260,6 @@ def item_cross_entropy(seq: torch.Tensor, table: torch.Tensor,
 CE_ROWS_ALIGN = 256   # rb_gemm_tn_h's N: a chunk's rows are a multiple of it
 
 
-def _rows_f16_ok(seq, table, chunk_rows: int) -> bool:
-    """Both of a chunk's products on rb_gemm_tn_h (_bwd_f16's conditions with B
-    = chunk_rows); other supported d: one library GEMM pair per chunk."""
-    from . import linear
-    d, V = seq.shape[1], table.shape[0]
-    return (CE_GRADS == "f16" and linear.gemm_format() == "f16x3" and d % 128 == 0
-            and table.data_ptr() % 16 == 0 and 8 * chunk_rows * V <= 2 * PROBS_SLICE_BYTES
-            and (V + 255) // 256 * 256 <= GEMM_TN_MAX_N)
-
-
 class _ItemCERows(torch.autograd.Function):
     """seq [Mp, d] (Mp a multiple of 256, padding rows zero with target -1),
     table [V, d], target [Mp] in [0, V) or -1; inv_n = 1 / live rows."""
@@ -284,8 +284,6 @@ class _ItemCERows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dloss):
-        from .linear import _timed
-
         seq, table, target, lse = ctx.saved_tensors
         want_seq, want_items = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         s_seq, s_tab = ctx.split
@@ -294,7 +292,10 @@ class _ItemCERows(torch.autograd.Function):
         Mp, d = seq.shape
         V = table.shape[0]
         dloss = dloss.float()
-        f16 = _rows_f16_ok(seq, table, chunk)
+        # both of a chunk's products on rb_gemm_tn_h, as in _ItemCE; other
+        # supported d: one library GEMM pair per chunk.  (chunk is a multiple
+        # of 256 and table contiguous: item_cross_entropy_rows, forward)
+        f16 = _f16_grads_ok(seq, table, rows=chunk)
         dseq = torch.empty_like(seq) if want_seq else None
         dtable = None
         # chunk by chunk in row order: P of one chunk at a time, dtable summed
@@ -306,19 +307,14 @@ class _ItemCERows(torch.autograd.Function):
             sr = kernels.SplitRows(s_seq.img[r0:r1], s_seq.exps[r0:r1])
             fl = 2 * n * V * d
             if f16:
-                p, pt, bmax, gmax = kernels.item_ce_probs_h_both_rows(sr, s_tab, tgt, l, dloss,
-                                                                      inv_n, pad_to=256)
+                probs = kernels.item_ce_probs_h_both_rows(sr, s_tab, tgt, l, dloss, inv_n,
+                                                          pad_to=256)
+                dr, dt = _f16_products(probs, rows, s_seq.gmax[r0 // 32:r1 // 32], table,
+                                       s_tab.gmax, want_seq, want_items, _round_splits)
                 if want_items:
-                    Vp = p.shape[1]
-                    S1 = _round_splits(seq.device, (Vp // 256) * (d // 128), n)
-                    parts = _timed("gemm", fl, kernels.gemm_tn_h, p, rows, bmax,
-                                   s_seq.gmax[r0 // 32:r1 // 32], S1)
-                    dt = kernels.colsum(parts.view(S1, -1)).view(Vp, d)[:V]
                     dtable = dt.contiguous() if dtable is None else dtable.add_(dt)
                 if want_seq:
-                    S2 = _tn_splits8(seq.device, (n // 256) * (d // 128), div=2)
-                    parts = _timed("gemm", fl, kernels.gemm_tn_h, pt, table, gmax, s_tab.gmax, S2)
-                    dseq[r0:r1] = kernels.colsum(parts.view(S2, -1)).view(n, d)
+                    dseq[r0:r1] = dr
             else:
                 p = kernels.item_ce_probs_h_rows(sr, s_tab, tgt, l, dloss, inv_n)
                 if want_seq:

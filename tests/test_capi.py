@@ -226,6 +226,74 @@ def test_f16_item_ce_argument_errors():
     assert rc == _lib.RB_EINVAL and b"ld < V" in lib.rb_last_error_string()
 
 
+# The seven f16-pipe CE entry points (B = 4, V = 8, d = 128): argument lists
+# that pass every check (the non-null pointers are fake and never
+# dereferenced), then bad values; with two of them, the check that fires first.
+_CE_OPS = dict(seq_img=_P, seq_exp=_P, item_img=_P, item_exp=_P, target=_P)
+_CE_GRAD = dict(lse=_P, dloss=_P)
+_CE_DIMS = dict(B=4, V=8, d=128)
+_CE_FWD_OUT = dict(lse=_P, loss=_P, workspace=_P, workspace_bytes=1 << 20, stream=None)
+_CE_P = dict(item_offset=0, probs=_P, ld=8)
+_CE_PT = dict(probs_t=_P, ldt=4)
+_CE_MAXES = dict(row_group_max=_P, item_group_max=_P, stream=None)
+CE_H = {
+    "rb_item_ce_fwd_h": {**_CE_OPS, **_CE_DIMS, **_CE_FWD_OUT},
+    "rb_item_ce_fwd_h_rows": {**_CE_OPS, **_CE_DIMS, "inv_n": 0.5, "accumulate": 0, **_CE_FWD_OUT},
+    "rb_item_ce_probs_h": {**_CE_OPS, **_CE_GRAD, **_CE_DIMS, **_CE_P, "stream": None},
+    "rb_item_ce_probs_h_t": {**_CE_OPS, **_CE_GRAD, **_CE_DIMS, "item_offset": 0, **_CE_PT,
+                             "group_max": _P, "stream": None},
+    "rb_item_ce_probs_h_both": {**_CE_OPS, **_CE_GRAD, **_CE_DIMS, **_CE_P, **_CE_PT, **_CE_MAXES},
+    "rb_item_ce_probs_h_rows": {**_CE_OPS, **_CE_GRAD, "inv_n": 0.5, **_CE_DIMS, **_CE_P,
+                                "stream": None},
+    "rb_item_ce_probs_h_both_rows": {**_CE_OPS, **_CE_GRAD, "inv_n": 0.5, **_CE_DIMS, **_CE_P,
+                                     **_CE_PT, **_CE_MAXES},
+}
+_CE_SHARED = {"item scores (f16): null exponent pointer", "item scores: null pointer",
+              "item scores: d must be 16, 32, 64, 128 or 256"}   # carry no entry point's name
+_CE_LDT = "probs_t must be 16-B aligned with ldt >= B, ldt % 4 == 0"
+_CE_INV_N = "inv_n must be in (0, 1]"
+_CE_POINTERS = ("target", "lse", "loss", "dloss", "workspace", "probs", "probs_t", "group_max",
+                "row_group_max", "item_group_max")
+CE_H_CASES = (
+    [(fn, {"seq_exp": None}, "item scores (f16): null exponent pointer") for fn in CE_H]
+    + [(fn, {"item_img": None}, "item scores: null pointer") for fn in CE_H]
+    + [(fn, {k: None}, "null pointer") for fn, ok in CE_H.items() for k in ok if k in _CE_POINTERS]
+    + [(fn, {"ld": 7}, "ld < V") for fn, ok in CE_H.items() if "ld" in ok]
+    + [(fn, bad, _CE_LDT) for fn, ok in CE_H.items() if "ldt" in ok
+       for bad in ({"ldt": 3}, {"ldt": 6}, {"probs_t": 8})]      # < B; % 4; not 16-B aligned
+    + [(fn, {"inv_n": v}, _CE_INV_N) for fn, ok in CE_H.items() if "inv_n" in ok
+       for v in (0.0, 1.5, -0.5, float("nan"))]
+    + [("rb_item_ce_fwd_h_rows", {"accumulate": 2}, "accumulate must be 0 or 1"),
+       ("rb_item_ce_fwd_h_rows", {"accumulate": -1}, "accumulate must be 0 or 1")]
+    # two bad values: operands, then null pointers, inv_n, accumulate / ld, ldt
+    + [(fn, {"d": 100, "target": None}, "item scores: d must be 16, 32, 64, 128 or 256")
+       for fn in CE_H]
+    + [(fn, {"lse": None, "inv_n": 0.0}, "null pointer") for fn, ok in CE_H.items() if "inv_n" in ok]
+    + [("rb_item_ce_fwd_h_rows", {"inv_n": 1.5, "accumulate": 2}, _CE_INV_N),
+       ("rb_item_ce_probs_h_rows", {"inv_n": 1.5, "ld": 7}, _CE_INV_N),
+       ("rb_item_ce_probs_h_both_rows", {"inv_n": 1.5, "ld": 7, "ldt": 3}, _CE_INV_N),
+       ("rb_item_ce_probs_h_both_rows", {"ld": 7, "ldt": 3}, "ld < V"),
+       ("rb_item_ce_probs_h_both", {"ld": 7, "ldt": 3}, "ld < V"),
+       ("rb_item_ce_probs_h_both", {"dloss": None, "ld": 7}, "null pointer"),
+       ("rb_item_ce_probs_h_t", {"group_max": None, "ldt": 3}, "null pointer")]
+)
+
+
+@pytest.mark.parametrize("fn,bad,what", CE_H_CASES,
+                         ids=[f"{fn}-{'-'.join(f'{k}={v}' for k, v in bad.items())}"
+                              for fn, bad, _ in CE_H_CASES])
+def test_f16_item_ce_entry_points_refuse_with_their_own_message(fn, bad, what):
+    """Each of the seven refuses before any launch (RB_EINVAL) with exactly the
+    message behind its own name, and with the earliest failing check's."""
+    lib = _lib.load()
+    assert set(bad) <= set(CE_H[fn])
+    args = list({**CE_H[fn], **bad}.values())
+    assert len(args) == len({**_lib.SIGNATURES, **_lib.DENSE_SIGNATURES}[fn][1])
+    assert getattr(lib, fn)(*args) == _lib.RB_EINVAL
+    want = what if what in _CE_SHARED else f"{fn}: {what}"
+    assert lib.rb_last_error_string().decode() == want
+
+
 def test_probe_library_is_separate_and_exports_its_header():
     """bench.py's measurement aids live in their own library
     (probes/recblr_probe.h, lib/libdmrecblr_probe.so): the product library
