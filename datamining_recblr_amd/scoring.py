@@ -56,7 +56,8 @@ def supported(seq: torch.Tensor, table: torch.Tensor) -> bool:
 # Backward strategy: "slices" writes the logits' gradient P one item slice at
 # a time (rb_item_ce_probs, at most PROBS_SLICE_BYTES) and runs dseq += P W,
 # ditems = P^T seq as library GEMMs; "fused" (rb_item_ce_bwd) recomputes the
-# logits inside the MFMA kernels and needs no [B, V] buffer at all.
+# logits inside the MFMA kernels (fp32 pipe) and needs no [B, V] buffer at all;
+# its forward runs on the fp32 pipe as well, whatever CE_PIPE says.
 def _env_choice(name: str, default: str, allowed: tuple) -> str:
     """An environment switch checked at import: a value outside `allowed`
     raises instead of silently selecting another path."""
@@ -218,7 +219,13 @@ class _ItemCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, seq, table, target):
         seq, table = seq.contiguous(), table.contiguous()
-        if CE_PIPE == "f16":
+        # The fused backward (rb_item_ce_bwd) recomputes the logits on the fp32
+        # pipe only, so its forward runs there too: P = exp(x - lse) - onehot
+        # needs x and lse from the same logits.  With the f16 pipe's lse a
+        # confident row (1 - p ~ 1e-2) lost 9x the accuracy of every other path
+        # (tests/test_gpu_item_ce_ref.py, peaked 600 x 4100 x 128).
+        ctx.fused = CE_BACKWARD == "fused"
+        if CE_PIPE == "f16" and not ctx.fused:
             # the split also gives the 32-row group maxima the f16 backward's
             # weight-gradient GEMMs scale these operands by
             s_seq = kernels.item_split_h(seq, group_max=True)
@@ -235,7 +242,7 @@ class _ItemCE(torch.autograd.Function):
     def backward(ctx, dloss):
         seq, table, target, lse = ctx.saved_tensors
         want_seq, want_items = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if CE_BACKWARD == "fused":
+        if ctx.fused:   # as the forward chose: the same logits on both sides
             dseq, dtable = kernels.item_ce_bwd(seq, table, target, lse, dloss.float(),
                                                want_seq=want_seq, want_items=want_items)
         elif ctx.split is not None and _f16_grads_ok(seq, table):
