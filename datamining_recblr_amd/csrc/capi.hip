@@ -663,7 +663,7 @@ int rb_sample_negatives(const int64_t* item_seq, int64_t seq_rs, const int64_t* 
   if ((offsets == nullptr) != (inv == nullptr))
     return fail(fn, "offsets and inv must be given together");
   if (B < 1 || L < 1 || L > 8191 || seq_rs < L) return fail(fn, "need B >= 1, 1 <= L <= 8191, seq_rs >= L");
-  if (n_neg < 1 || n_neg > 16) return fail(fn, "n_neg must be in [1, 16]");
+  if (n_neg < 1 || n_neg > 256) return fail(fn, "n_neg must be in [1, 256]");
   if (first_item < 0 || V <= first_item || V >= (int64_t(1) << 31))
     return fail(fn, "need 0 <= first_item < V < 2^31");
   if (offsets ? (ntok < 1 || m_pad < ntok || ntok > B * L) : (ntok != B || m_pad != B))
@@ -728,6 +728,62 @@ int rb_embedding_bwd_apply_scaled(const float* src, int64_t src_ld, int64_t src_
     return fail(fn, "need 1 <= src_rows < 2^31 and src_ld >= d");
   return launch_embedding_apply_scaled(src, src_ld, src_rows, coef, M, d, V, padding_idx, dweight,
                                        workspace, workspace_bytes, as_stream(stream));
+}
+
+// ---- sampled softmax, negatives shared per sequence (include/recblr_pairs.h) --------
+namespace {
+int check_shared(const char* fn, int64_t M, int64_t B, int64_t d, int64_t V, int64_t n_neg,
+                 int64_t max_len, float shift) {
+  if (M < 1 || B < 1 || V < 1 || max_len < 1) return fail(fn, "M, B, V and max_len must be positive");
+  if (d < 16 || d > 224 || d % 16) return fail(fn, "d must be a multiple of 16 in [16, 224]");
+  if (n_neg < 1 || n_neg > 256) return fail(fn, "n_neg must be in [1, 256]");
+  if (!(shift - shift == 0.0f)) return fail(fn, "shift must be finite");
+  if (M >= (int64_t(1) << 31) || V >= (int64_t(1) << 31) || B >= (int64_t(1) << 22))
+    return fail(fn, "M, V or B too large");
+  return 0;
+}
+}  // namespace
+
+int64_t rb_shared_softmax_workspace(int64_t B, int64_t max_len) {
+  return B <= 0 || B >= (int64_t(1) << 22) ? 0 : shared_softmax_workspace_bytes(B, max_len);
+}
+
+int rb_shared_softmax_fwd(const float* h, int64_t ldh, const float* table,
+                          const int64_t* target, const int64_t* neg, const int64_t* offsets,
+                          const int64_t* order, int64_t M, int64_t B, int64_t d, int64_t V,
+                          int64_t n_neg, int64_t max_len, float shift, float* lse, float* z0,
+                          float* loss, int64_t* n_live, void* workspace,
+                          int64_t workspace_bytes, void* stream) {
+  const char* fn = "rb_shared_softmax_fwd";
+  if (!h || !table || !target || !neg || !offsets || !order || !lse || !z0 || !loss || !n_live ||
+      !workspace)
+    return fail(fn, "null pointer");
+  if (int rc = check_shared(fn, M, B, d, V, n_neg, max_len, shift)) return rc;
+  if (ldh < d || ldh % 4 || !aligned16(h) || !aligned16(table))
+    return fail(fn, "h and table must be 16-B aligned with ldh >= d, ldh % 4 == 0");
+  if (workspace_bytes < shared_softmax_workspace_bytes(B, max_len) || !aligned16(workspace))
+    return fail(fn, "workspace too small or misaligned");
+  return launch_shared_softmax_fwd(h, ldh, table, target, neg, offsets, order, M, B, d, V, n_neg,
+                                   max_len, shift, lse, z0, loss, n_live, workspace,
+                                   as_stream(stream));
+}
+
+int rb_shared_softmax_bwd(const float* h, int64_t ldh, const float* table,
+                          const int64_t* target, const int64_t* neg, const int64_t* offsets,
+                          const int64_t* order, const float* lse, const float* dloss,
+                          const int64_t* n_live, int64_t M, int64_t B, int64_t d, int64_t V,
+                          int64_t n_neg, int64_t max_len, float shift, float* dh, float* coef,
+                          float* dneg, void* stream) {
+  const char* fn = "rb_shared_softmax_bwd";
+  if (!h || !table || !target || !neg || !offsets || !order || !lse || !dloss || !n_live || !dh ||
+      !coef || !dneg)
+    return fail(fn, "null pointer");
+  if (int rc = check_shared(fn, M, B, d, V, n_neg, max_len, shift)) return rc;
+  if (ldh < d || ldh % 4 || !aligned16(h) || !aligned16(table))
+    return fail(fn, "h and table must be 16-B aligned with ldh >= d, ldh % 4 == 0");
+  return launch_shared_softmax_bwd(h, ldh, table, target, neg, offsets, order, lse, dloss, n_live,
+                                   M, B, d, V, n_neg, max_len, shift, dh, coef, dneg,
+                                   as_stream(stream));
 }
 
 // ---- candidate-list scoring (include/recblr_candidates.h) ---------------------------

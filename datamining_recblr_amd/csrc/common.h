@@ -521,6 +521,19 @@ int launch_pair_loss_bwd(const float* tab, const int64_t* pos, const int64_t* ne
                          const float* diff, const float* dloss, const int64_t* n_live, int64_t M,
                          int64_t d, int64_t V, int64_t n_neg, float gamma, float* dh, float* coef,
                          hipStream_t st);
+int64_t shared_softmax_blocks(int64_t B, int64_t max_len);
+int64_t shared_softmax_workspace_bytes(int64_t B, int64_t max_len);
+int launch_shared_softmax_fwd(const float* h, int64_t ldh, const float* tab, const int64_t* target,
+                              const int64_t* neg, const int64_t* offsets, const int64_t* order,
+                              int64_t M, int64_t B, int64_t d, int64_t V, int64_t n,
+                              int64_t max_len, float shift, float* lse, float* z0, float* loss,
+                              int64_t* n_live, void* workspace, hipStream_t st);
+int launch_shared_softmax_bwd(const float* h, int64_t ldh, const float* tab, const int64_t* target,
+                              const int64_t* neg, const int64_t* offsets, const int64_t* order,
+                              const float* lse, const float* dloss, const int64_t* n_live,
+                              int64_t M, int64_t B, int64_t d, int64_t V, int64_t n,
+                              int64_t max_len, float shift, float* dh, float* coef, float* dneg,
+                              hipStream_t st);
 int launch_candidate_scores(const float* h, int64_t ldh, const float* tab, const int64_t* cand,
                             int64_t B, int64_t C, int64_t d, int64_t V, float* scores,
                             hipStream_t st);

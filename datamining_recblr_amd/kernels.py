@@ -24,7 +24,8 @@ __all__ = [
     "item_ce_fwd_h_rows", "item_ce_probs_h_rows", "item_ce_probs_h_both_rows",
     "next_item_targets", "next_item_targets_reference",
     "sample_negatives", "sample_negatives_reference", "philox4x32_10", "pair_loss_fwd",
-    "pair_loss_bwd", "embedding_bwd_scaled", "pair_loss_supported",
+    "pair_loss_bwd", "embedding_bwd_scaled", "pair_loss_supported", "shared_softmax_fwd",
+    "shared_softmax_bwd", "shared_softmax_supported", "MAX_SHARED_NEGATIVES",
     "candidate_scores", "candidate_topk", "candidate_ranks", "candidates_supported",
     "CANDIDATE_MAX", "CANDIDATE_EXCLUDE_MAX",
 ]
@@ -1351,6 +1352,87 @@ def embedding_bwd_scaled(coef: torch.Tensor, src: torch.Tensor, num_rows: int, p
             rows, coef.contiguous().data_ptr(), M, d, num_rows, pad, dw.data_ptr(),
             plan.data_ptr(), plan.numel(), _stream(src), _fn="rb_embedding_bwd_apply_scaled")
     return dw
+
+
+# ---- sampled softmax, negatives shared per sequence (csrc/shared_softmax.hip) -------
+MAX_SHARED_NEGATIVES = 256
+SHARED_MAX_D = 224
+
+
+def shared_softmax_supported(h: torch.Tensor, table: torch.Tensor, n: int) -> bool:
+    """The shared-negatives softmax kernels take fp32 GPU rows of d a multiple
+    of 16 up to 224 and 1 .. 256 negatives per sequence."""
+    return (h.is_cuda and table.is_cuda and h.dtype == torch.float32
+            and table.dtype == torch.float32 and h.dim() == 2 and table.dim() == 2
+            and h.shape[1] == table.shape[1] and h.shape[1] % 16 == 0
+            and 16 <= h.shape[1] <= SHARED_MAX_D and 1 <= int(n) <= MAX_SHARED_NEGATIVES)
+
+
+def _shared_operands(h, table, target, neg, offsets, order):
+    _check(h, "h")
+    _check(table, "table")
+    for t, name in ((target, "target"), (neg, "neg"), (offsets, "offsets"), (order, "order")):
+        _check(t, name, torch.int64)
+    if h.dim() != 2 or table.dim() != 2 or neg.dim() != 2:
+        raise ValueError("shared softmax: h [M, d], table [V, d], neg [B, n]")
+    M, d = h.shape
+    B, n = neg.shape
+    if (target.shape != (M,) or table.shape[1] != d or offsets.shape != (B + 1,)
+            or order.shape != (B,)):
+        raise ValueError("shared softmax: h [M, d], table [V, d], target [M], neg [B, n], "
+                         "offsets [B + 1], order [B]")
+    for t, name in ((table, "table"), (target, "target"), (neg, "neg"), (offsets, "offsets"),
+                    (order, "order")):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if h.stride(1) != 1 or h.stride(0) % 4 or h.data_ptr() % 16:
+        raise ValueError("h needs unit-stride, 16-B aligned rows")
+    return M, d, B, n, table.shape[0]
+
+
+def shared_softmax_fwd(h: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
+                       neg: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor,
+                       shift: float, max_len: int):
+    """rb_shared_softmax_fwd: (loss [], n_live [] int64, lse [M], z0 [M]) of the
+    packed rows h [M, d] (unit-stride rows, any 16-B aligned row stride)
+    against table [V, d]: target [M] int64 (-1 = ignored row), neg [B, n] int64
+    (one list per batch row, -1 = dead column), offsets [B + 1] / order [B] the
+    pack plan.  max_len: an upper estimate of the longest sequence (sizes the
+    grid only)."""
+    M, d, B, n, V = _shared_operands(h, table, target, neg, offsets, order)
+    dev = h.device
+    lse = torch.zeros((M,), device=dev, dtype=torch.float32)
+    z0 = torch.zeros((M,), device=dev, dtype=torch.float32)
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    n_live = torch.empty((), device=dev, dtype=torch.int64)
+    max_len = max(int(max_len), 1)
+    ws_bytes = int(_lib.load().rb_shared_softmax_workspace(B, max_len))
+    ws = torch.empty((ws_bytes,), device=dev, dtype=torch.uint8)
+    _launch("rb_shared_softmax_fwd", 4 * (2 * M + B * n) * d, h.data_ptr(), h.stride(0),
+            table.data_ptr(), target.data_ptr(), neg.data_ptr(), offsets.data_ptr(),
+            order.data_ptr(), M, B, d, V, n, max_len, float(shift), lse.data_ptr(), z0.data_ptr(),
+            loss.data_ptr(), n_live.data_ptr(), ws.data_ptr(), ws_bytes, _stream(h))
+    return loss, n_live, lse, z0
+
+
+def shared_softmax_bwd(h: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
+                       neg: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor,
+                       lse: torch.Tensor, dloss: torch.Tensor, n_live: torch.Tensor,
+                       shift: float, max_len: int):
+    """rb_shared_softmax_bwd: (dh [M, d], coef [M], dneg [B, n, d]); the table's
+    gradient is coef[r] * h_r scattered by target plus dneg's rows scattered by
+    neg.  Rows and lists the plan does not cover are zero."""
+    M, d, B, n, V = _shared_operands(h, table, target, neg, offsets, order)
+    dev = h.device
+    dh = torch.zeros((M, d), device=dev, dtype=torch.float32)
+    coef = torch.zeros((M,), device=dev, dtype=torch.float32)
+    dneg = torch.zeros((B, n, d), device=dev, dtype=torch.float32)
+    _launch("rb_shared_softmax_bwd", 4 * (3 * M + 2 * B * n) * d, h.data_ptr(), h.stride(0),
+            table.data_ptr(), target.data_ptr(), neg.data_ptr(), offsets.data_ptr(),
+            order.data_ptr(), lse.data_ptr(), dloss.data_ptr(), n_live.data_ptr(), M, B, d, V, n,
+            max(int(max_len), 1), float(shift), dh.data_ptr(), coef.data_ptr(), dneg.data_ptr(),
+            _stream(h))
+    return dh, coef, dneg
 
 
 # ---- candidate lists (csrc/candidates.hip, include/recblr_candidates.h) -------------

@@ -31,7 +31,8 @@ from torch import nn
 from ._lib import RecBLRNativeError
 from .blocks import (ResidualGrad, add_dropout_layer_norm, draw_seed, embed_dropout_layer_norm,
                      feed_forward, linear_add_dropout_layer_norm)
-from .kernels import (MAX_NEGATIVES, Packed, grl_max_tiles, grl_pieces, next_item_targets,
+from .kernels import (MAX_NEGATIVES, MAX_SHARED_NEGATIVES, Packed, grl_max_tiles, grl_pieces,
+                      next_item_targets, next_item_targets_reference, sample_negatives_reference,
                       pack_plan, sample_negatives)
 from .linear import HipLinearForward, fire_hooks, has_hooks, linear
 from .recbole_compat import BPRLoss, SequentialRecommender, install_interaction_hook
@@ -39,7 +40,7 @@ from .recurrence import bd_lru, fused_ok, pow2_pad_len, row_pad_lens
 
 
 from .scoring import (candidate_ranks, candidate_scores, full_sort_scores, item_cross_entropy,
-                      item_cross_entropy_rows, pair_loss, target_ranks, top_candidates, top_items)
+                      item_cross_entropy_rows, pair_loss, shared_softmax_loss, target_ranks, top_candidates, top_items)
 
 # RECBLR_CONV_ROWS=0: packed conv forward per sequence instead of per row tile
 _CONV_ROWS = os.environ.get("RECBLR_CONV_ROWS", "1") != "0"
@@ -300,8 +301,31 @@ class RecBLR(SequentialRecommender):
             self.dense_negatives = int(config["dense_negatives"] or 0)
         except (KeyError, TypeError):
             self.dense_negatives = 0
-        if not 0 <= self.dense_negatives <= MAX_NEGATIVES:
-            raise ValueError(f"dense_negatives must be in [0, {MAX_NEGATIVES}]")
+        # what the sampled negatives feed: 'pairs' (calculate_loss_pairs, n per
+        # position) or 'sampled_softmax' (calculate_loss_sampled, n per row,
+        # shared by its positions); not a reference key
+        try:
+            self.dense_loss = config["dense_loss"] or "pairs"
+        except (KeyError, TypeError):
+            self.dense_loss = "pairs"
+        if self.dense_loss not in ("pairs", "sampled_softmax"):
+            raise ValueError(f"dense_loss must be 'pairs' or 'sampled_softmax', got "
+                             f"{self.dense_loss!r}")
+        sampled = self.dense_loss == "sampled_softmax"
+        most = MAX_SHARED_NEGATIVES if sampled else MAX_NEGATIVES
+        if not 0 <= self.dense_negatives <= most:
+            raise ValueError(f"dense_negatives must be in [0, {most}] for dense_loss "
+                             f"{self.dense_loss!r}")
+        if sampled and not self.dense_negatives:
+            raise ValueError("dense_loss 'sampled_softmax' needs dense_negatives >= 1")
+        if sampled and self.loss_type != "CE":
+            raise ValueError("dense_loss 'sampled_softmax' needs loss_type 'CE'")
+        # the log-Q correction of the uniform proposal (calculate_loss_sampled)
+        try:
+            correct = config["sampled_softmax_correct"]
+        except (KeyError, TypeError):
+            correct = None
+        self.sampled_softmax_correct = True if correct is None else bool(correct)
         if self.dense_negatives and not self.train_all_positions:
             raise ValueError("dense_negatives needs train_all_positions: True (the negatives "
                              "are sampled at every position of a row)")
@@ -533,8 +557,42 @@ class RecBLR(SequentialRecommender):
                              f"got {tuple(negatives.shape)}")
         return pair_loss(h, self.item_embedding.weight, target, negatives[:seq.ntok])
 
+    def calculate_loss_sampled(self, interaction, negatives=None):
+        """The sampled softmax at every valid position of every row, the
+        negatives shared by the positions of a row: the mean over all
+        positions t of logsumexp(z0, z_1 .. z_n) - z0 with z0 = h_t . E[next
+        item] and z_j = h_t . E[neg_j] + shift (scoring.shared_softmax_loss).
+        negatives: int64 [B, n] in batch-row order (-1 = no column), or None:
+        dense_negatives ids per row drawn on the device (kernels.
+        sample_negatives' last-position mode, seeded from torch's generator
+        like the dropout), uniform over the items outside the row's window
+        and target — every position's target is one of those, so a row's
+        list is a valid list for each of its positions.  shift =
+        log((n_items - 1) / n), the log-Q correction that makes sum_j
+        exp(z_j) an estimate of the full softmax's sum over the other items
+        (sampled_softmax_correct: False gives shift = 0)."""
+        item_seq, lengths = interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN]
+        h, seq = self.forward_all(item_seq, lengths)
+        pos_items = interaction[self.POS_ITEM_ID].to(torch.int64)
+        # rows on the host (an encoder run elsewhere): the host restatements
+        targets, draw = ((next_item_targets, sample_negatives) if h.is_cuda else
+                         (next_item_targets_reference, sample_negatives_reference))
+        target = targets(seq.ids, seq.offsets, seq.order, pos_items)
+        if negatives is None:
+            negatives = draw(item_seq.to(torch.int64), lengths.to(torch.int64), pos_items,
+                             max(self.dense_negatives, 1), 1, self.n_items, draw_seed())
+        elif negatives.dim() != 2 or negatives.shape[0] != item_seq.shape[0]:
+            raise ValueError(f"negatives must be [{item_seq.shape[0]}, n] in batch-row order, "
+                             f"got {tuple(negatives.shape)}")
+        n = negatives.shape[1]
+        shift = math.log((self.n_items - 1) / n) if self.sampled_softmax_correct else 0.0
+        return shared_softmax_loss(h, self.item_embedding.weight, target, negatives, seq.offsets,
+                                   seq.order, shift, max_len=seq.L)
+
     def calculate_loss(self, interaction):
         if self.train_all_positions:
+            if self.dense_negatives and self.dense_loss == "sampled_softmax":
+                return self.calculate_loss_sampled(interaction)
             if self.dense_negatives:
                 return self.calculate_loss_pairs(interaction)
             return self.calculate_loss_dense(interaction)

@@ -18,6 +18,10 @@ RECBLR_CE_PIPE), ranking and scores on the fp32 pipe:
   * pair_loss: the sampled pairwise (BPR) loss of many rows against each
     row's target and its sampled negatives only (csrc/pair_loss.hip;
     RecBLR.calculate_loss_pairs) — no sweep over the table at all;
+  * shared_softmax_loss: the sampled softmax of the packed rows against each
+    row's target and n negatives shared by the rows of a sequence
+    (csrc/shared_softmax.hip; RecBLR.calculate_loss_sampled) — one small
+    fp32 MFMA product per sequence;
   * target_ranks: per row, the number of items scoring above / equal to the
     target, from which Hit@k, MRR@k and NDCG@k follow exactly;
   * full_sort_scores: the score matrix itself when a caller needs it;
@@ -44,7 +48,8 @@ from . import kernels, linear
 from .linear import _timed
 
 __all__ = ["item_cross_entropy", "item_cross_entropy_rows", "full_sort_scores", "target_ranks", "rank_metrics",
-           "top_items", "supported", "pair_loss", "pair_loss_reference", "candidate_scores",
+           "top_items", "supported", "pair_loss", "pair_loss_reference", "shared_softmax_loss",
+           "shared_softmax_reference", "candidate_scores",
            "order_candidates", "top_candidates", "candidate_ranks"]
 
 
@@ -448,6 +453,123 @@ def pair_loss(h: torch.Tensor, table: torch.Tensor, pos: torch.Tensor, neg: torc
         loss = pair_loss_reference(h, table, pos, neg, gamma)
         return (loss, ((pos >= 0)[:, None] & (neg >= 0)).sum()) if return_live else loss
     loss, n_live = _PairLoss.apply(h, table, pos, neg, float(gamma))
+    return (loss, n_live) if return_live else loss
+
+
+def shared_softmax_reference(h: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
+                             neg: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor,
+                             shift: float = 0.0) -> torch.Tensor:
+    """shared_softmax_loss in torch ops, any device and dtype: the CPU path,
+    the fallback for shapes the kernels refuse, and the tests' reference.  The
+    sequences are padded to the longest one and scored against their own
+    lists with one batched product."""
+    V, (B, n) = table.shape[0], neg.shape
+    lens = offsets[1:] - offsets[:-1]
+    rows = torch.arange(int(offsets[0]), int(offsets[-1]), device=h.device)
+    if rows.numel() == 0:
+        return (h.sum() + table.sum()) * 0.0
+    seq_of = torch.repeat_interleave(torch.arange(B, device=h.device), lens)
+    t_in = rows - offsets[seq_of]
+    hr, tr = h[rows], target[rows]
+    padded = hr.new_zeros((B, int(lens.max()), h.shape[1])).index_put((seq_of, t_in), hr)
+    lists = neg[order]                                       # [B, n], packed-sequence order
+    col_ok = (lists >= 0) & (lists < V)
+    z = torch.bmm(padded, table[lists.clamp(0, V - 1)].transpose(1, 2))[seq_of, t_in] + shift
+    z = torch.where(col_ok[seq_of], z, torch.full_like(z, float("-inf")))
+    row_ok = (tr >= 0) & (tr < V)
+    z0 = (hr * table[tr.clamp(0, V - 1)]).sum(-1)
+    l = torch.logsumexp(torch.cat([z0[:, None], z], 1), 1) - z0
+    loss = torch.where(row_ok, l, torch.zeros_like(l)).sum() / row_ok.sum().clamp(min=1)
+    bad = ((tr < -1) | (tr >= V)).any() | ((neg < -1) | (neg >= V)).any()
+    return torch.where(bad, torch.full_like(loss, float("nan")), loss)
+
+
+class _SharedSoftmax(torch.autograd.Function):
+    """h [M, d], table [V, d], target [M], neg [B, n] and the pack plan: the
+    forward saves lse and plans the table's two scatters (index work only);
+    the backward is the two gradient kernels, the scaled apply over the
+    targets and the plain apply of dneg over the lists."""
+
+    @staticmethod
+    def forward(ctx, h, table, target, neg, offsets, order, shift, max_len):
+        table = table.contiguous()
+        if h.stride(1) != 1 or h.stride(0) % 4 or h.data_ptr() % 16:
+            h = h.contiguous()
+        target, neg = target.contiguous(), neg.contiguous()
+        offsets, order = offsets.contiguous(), order.contiguous()
+        loss, n_live, lse, _ = kernels.shared_softmax_fwd(h, table, target, neg, offsets, order,
+                                                          shift, max_len)
+        ctx.plans = None
+        if ctx.needs_input_grad[1]:
+            V, d = table.shape
+            ctx.plans = (kernels.embedding_plan(target, V, d),
+                         kernels.embedding_plan(neg.reshape(-1), V, d))
+        ctx.shift, ctx.max_len = shift, max_len
+        ctx.save_for_backward(h, table, target, neg, offsets, order, lse, n_live)
+        ctx.mark_non_differentiable(n_live)
+        return loss, n_live
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        h, table, target, neg, offsets, order, lse, n_live = ctx.saved_tensors
+        plans, ctx.plans = ctx.plans, None
+        dh, coef, dneg = kernels.shared_softmax_bwd(h, table, target, neg, offsets, order, lse,
+                                                    dloss.float().contiguous(), n_live,
+                                                    ctx.shift, ctx.max_len)
+        dtable = None
+        if plans is not None:
+            V, d = table.shape
+            dtable = kernels.embedding_bwd_scaled(coef, h, V, plans[0])
+            dtable += kernels.embedding_bwd(neg.reshape(-1), dneg.reshape(-1, d), V,
+                                            padding_idx=None, plan=plans[1])
+        return ((dh if ctx.needs_input_grad[0] else None), dtable, None, None, None, None, None,
+                None)
+
+
+def shared_softmax_loss(h: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
+                        neg: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor,
+                        shift: float = 0.0, return_live: bool = False, *,
+                        max_len: int | None = None):
+    """Sampled softmax of the packed rows h [M, d] against table [V, d] with
+    the negatives shared by the rows of a sequence: neg [B, n] holds one list
+    per batch row, and packed sequence s (rows offsets[s] .. offsets[s + 1])
+    is batch row order[s].  For row r of batch row b
+
+        z0 = h_r . table[target_r],  z_j = h_r . table[neg[b, j]] + shift
+        loss_r = logsumexp(z0, z_j ...) - z0
+
+    and the loss is the mean of loss_r over the live rows.  target_r = -1
+    ignores row r (no loss, exactly zero gradient) and neg[b, j] = -1 is a
+    dead column; any other id outside [0, V) gives NaN.  No live row: loss 0
+    and zero gradients; a live row without a live column has loss 0 and counts.
+    A repeated id counts once per occurrence, and a column may equal a row's
+    target.  shift is the log-Q correction of the proposal (log((V' - 1) / n)
+    for n uniform draws over V' items makes sum_j exp(z_j) an estimate of the
+    full softmax's sum over the non-targets).  The scores of a sequence are
+    one product on the exact-fp32 MFMA and no [M, n] matrix is stored; the
+    table's gradient goes through the embedding backward's deterministic plan,
+    so the result is bitwise reproducible.  return_live: also the live-row
+    count (a device scalar, no sync).  max_len: an upper estimate of the
+    longest sequence (it sizes the launch; without it the lengths are read
+    back once).  CPU tensors, other dtypes, d no multiple of 16 up to 224 and
+    n > 256 take shared_softmax_reference."""
+    if (h.dim() != 2 or target.shape != (h.shape[0],) or neg.dim() != 2 or neg.shape[1] < 1
+            or offsets.shape != (neg.shape[0] + 1,) or order.shape != (neg.shape[0],)):
+        raise ValueError(f"h [M, d], target [M], neg [B, n >= 1], offsets [B + 1] and order [B] "
+                         f"required, got {tuple(h.shape)}, {tuple(target.shape)}, "
+                         f"{tuple(neg.shape)}, {tuple(offsets.shape)} and {tuple(order.shape)}")
+    target, neg = target.to(torch.int64), neg.to(torch.int64)
+    offsets, order = offsets.to(torch.int64), order.to(torch.int64)
+    if not kernels.shared_softmax_supported(h, table, neg.shape[1]):
+        loss = shared_softmax_reference(h, table, target, neg, offsets, order, shift)
+        if not return_live:
+            return loss
+        covered = target[int(offsets[0]):int(offsets[-1])]
+        return loss, ((covered >= 0) & (covered < table.shape[0])).sum()
+    if max_len is None:
+        max_len = int((offsets[1:] - offsets[:-1]).max())
+    loss, n_live = _SharedSoftmax.apply(h, table, target, neg, offsets, order, float(shift),
+                                        int(max_len))
     return (loss, n_live) if return_live else loss
 
 

@@ -67,7 +67,9 @@ def fit(model, data, env: DistEnv, epochs: int = 100, batch_size: int = 2048,
     dense: all-position training — the loader yields one row per user window
     (SequentialLoader(dense=True)) and the model, built with
     train_all_positions, takes the loss at every position of it (the CE, or
-    with dense_negatives the sampled pairwise loss).  A loss_type 'BPR' model
+    with dense_negatives the sampled pairwise loss, or with dense_loss
+    'sampled_softmax' the sampled softmax over negatives shared per row; the
+    loop is the same for all three).  A loss_type 'BPR' model
     gets one sampled negative per row from the loader (NEG_ITEM_ID)."""
     if dense and not getattr(model, "train_all_positions", False):
         raise ValueError("fit(dense=True) needs a model built with train_all_positions=True")

@@ -7,8 +7,8 @@
  * HIP call, 0 / RB_EINVAL / hipError_t returns, rb_last_error_string() for
  * the message.  Plain C declarations, one per ';' — the Python binding
  * (datamining_recblr_amd/_lib.py) parses this header as it parses
- * recblr_hip.h.  Defined in csrc/capi.hip; kernels in csrc/pair_loss.hip and
- * csrc/embedding.hip.
+ * recblr_hip.h.  Defined in csrc/capi.hip; kernels in csrc/pair_loss.hip,
+ * csrc/shared_softmax.hip and csrc/embedding.hip.
  *
  * Every packed row (RecBLR.forward_all, recblr_dense.h) is scored against its
  * target and n sampled negatives only: (2 + n) rows of d floats per position
@@ -39,7 +39,7 @@ extern "C" {
  * < ntok — and the rows [ntok, m_pad) are filled with -1.  Both NULL (ntok =
  * m_pad = B): only t = len_b - 1 is drawn, into row b; these are exactly the
  * dense call's rows at each sequence's last position.  A pure function of its
- * arguments; no atomics.  Needs 1 <= n_neg <= 16, 0 <= first_item < V < 2^31,
+ * arguments; no atomics.  Needs 1 <= n_neg <= 256, 0 <= first_item < V < 2^31,
  * L <= 8191; an index outside its range writes nothing. */
 int rb_sample_negatives(const int64_t* item_seq, int64_t seq_rs, const int64_t* lengths,
                         const int64_t* pos_items, const int64_t* offsets, const int64_t* inv,
@@ -82,6 +82,47 @@ int rb_embedding_bwd_apply_scaled(const float* src, int64_t src_ld, int64_t src_
                                   const float* coef, int64_t M, int64_t d, int64_t V,
                                   int64_t padding_idx, float* dweight, void* workspace,
                                   int64_t workspace_bytes, void* stream);
+
+/* ---- sampled softmax with negatives shared per sequence (csrc/shared_softmax.hip) ----
+ * h [M, d] (row stride ldh) packed rows, table [V, d], target [M]
+ * (rb_next_item_targets: -1 an ignored row), neg [B, n_neg] one list per batch
+ * row (-1 a dead column), offsets [B + 1] / order [B] (rb_pack_plan's layout:
+ * packed sequence s is batch row b = order[s] at rows offsets[s] ..
+ * offsets[s + 1]).  For row r of sequence s
+ *   z0 = h_r . table[target_r],  z_j = h_r . table[neg[b, j]] + shift  (live columns)
+ *   lse[r] = logsumexp(z0, z_j ...),  z0 -> z0[r]     (written for ignored rows too)
+ * loss[0] = sum over the live rows of (lse[r] - z0[r]) / max(n_live, 1),
+ * n_live[0] = live rows (device scalars, no host sync); the sum runs over
+ * per-workgroup partials in workgroup order.  An id outside [-1, V) gives a NaN
+ * loss (it is never dereferenced).  A plan entry with rows outside [0, M), no
+ * rows, or a batch row outside [0, B) is skipped.  max_len >= 1: an upper
+ * estimate of the longest sequence; it sizes the grid and the workspace only
+ * (longer sequences are still covered).  d a multiple of 16 in [16, 224],
+ * 1 <= n_neg <= 256; h, table 16-B aligned with ldh % 4 == 0. */
+int64_t rb_shared_softmax_workspace(int64_t B, int64_t max_len);
+
+int rb_shared_softmax_fwd(const float* h, int64_t ldh, const float* table,
+                          const int64_t* target, const int64_t* neg, const int64_t* offsets,
+                          const int64_t* order, int64_t M, int64_t B, int64_t d, int64_t V,
+                          int64_t n_neg, int64_t max_len, float shift, float* lse, float* z0,
+                          float* loss, int64_t* n_live, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
+/* With scale = dloss[0] / max(n_live[0], 1) and p_rj = exp(z_j - lse[r]) (0 for
+ * a dead column or an ignored row), for the rows the plan covers:
+ *   dh [M, d] (contiguous)   dh_r = scale (sum_j p_rj table[neg[b, j]] - q_r table[target_r]),
+ *                            q_r = sum_j p_rj = 1 - p_r0
+ *   coef [M]                 -scale q_r: the target's gradient row is coef[r] * h_r
+ *                            (rb_embedding_bwd_apply_scaled over the ids target)
+ *   dneg [B, n_neg, d]       scale sum_{r in s} p_rj h_r, summed over the sequence's
+ *                            rows in order (rb_embedding_bwd_apply over the ids neg)
+ * Rows and lists no plan entry covers are not written. */
+int rb_shared_softmax_bwd(const float* h, int64_t ldh, const float* table,
+                          const int64_t* target, const int64_t* neg, const int64_t* offsets,
+                          const int64_t* order, const float* lse, const float* dloss,
+                          const int64_t* n_live, int64_t M, int64_t B, int64_t d, int64_t V,
+                          int64_t n_neg, int64_t max_len, float shift, float* dh, float* coef,
+                          float* dneg, void* stream);
 
 #ifdef __cplusplus
 }
