@@ -654,11 +654,13 @@ int rb_next_item_targets(const int64_t* ids, const int64_t* seq_offsets, const i
 }
 
 // ---- the sampled pairwise loss (include/recblr_pairs.h) ---------------------------
-int rb_sample_negatives(const int64_t* item_seq, int64_t seq_rs, const int64_t* lengths,
-                        const int64_t* pos_items, const int64_t* offsets, const int64_t* inv,
-                        int64_t B, int64_t L, int64_t n_neg, int64_t first_item, int64_t V,
-                        uint64_t seed, int64_t ntok, int64_t m_pad, int64_t* neg, void* stream) {
-  const char* fn = "rb_sample_negatives";
+namespace {
+// both samplers; alias: the proposal's table, NULL for the uniform draw
+int sample_negatives(const char* fn, const int64_t* item_seq, int64_t seq_rs,
+                     const int64_t* lengths, const int64_t* pos_items, const int64_t* offsets,
+                     const int64_t* inv, int64_t B, int64_t L, int64_t n_neg, int64_t first_item,
+                     int64_t V, uint64_t seed, int64_t ntok, int64_t m_pad, const int64_t* alias,
+                     int64_t* neg, void* stream) {
   if (!item_seq || !lengths || !pos_items || !neg) return fail(fn, "null pointer");
   if ((offsets == nullptr) != (inv == nullptr))
     return fail(fn, "offsets and inv must be given together");
@@ -671,7 +673,28 @@ int rb_sample_negatives(const int64_t* item_seq, int64_t seq_rs, const int64_t* 
   if (B >= (int64_t(1) << 31) || B + ((m_pad - ntok) * n_neg + 255) / 256 > 0x7fffffffLL)
     return fail(fn, "grid too large");
   return launch_sample_negatives(item_seq, seq_rs, lengths, pos_items, offsets, inv, B, L, n_neg,
-                                 first_item, V, seed, ntok, m_pad, neg, as_stream(stream));
+                                 first_item, V, seed, ntok, m_pad, alias, neg, as_stream(stream));
+}
+}  // namespace
+
+int rb_sample_negatives(const int64_t* item_seq, int64_t seq_rs, const int64_t* lengths,
+                        const int64_t* pos_items, const int64_t* offsets, const int64_t* inv,
+                        int64_t B, int64_t L, int64_t n_neg, int64_t first_item, int64_t V,
+                        uint64_t seed, int64_t ntok, int64_t m_pad, int64_t* neg, void* stream) {
+  return sample_negatives("rb_sample_negatives", item_seq, seq_rs, lengths, pos_items, offsets,
+                          inv, B, L, n_neg, first_item, V, seed, ntok, m_pad, nullptr, neg, stream);
+}
+
+int rb_sample_negatives_alias(const int64_t* item_seq, int64_t seq_rs, const int64_t* lengths,
+                              const int64_t* pos_items, const int64_t* offsets,
+                              const int64_t* inv, int64_t B, int64_t L, int64_t n_neg,
+                              int64_t first_item, int64_t V, uint64_t seed, int64_t ntok,
+                              int64_t m_pad, const int64_t* alias, int64_t* neg, void* stream) {
+  const char* fn = "rb_sample_negatives_alias";
+  if (!alias) return fail(fn, "null pointer");
+  if (reinterpret_cast<uintptr_t>(alias) % 8) return fail(fn, "alias must be 8-B aligned");
+  return sample_negatives(fn, item_seq, seq_rs, lengths, pos_items, offsets, inv, B, L, n_neg,
+                          first_item, V, seed, ntok, m_pad, alias, neg, stream);
 }
 
 int64_t rb_pair_loss_workspace(int64_t M) { return M <= 0 ? 0 : pair_loss_workspace_bytes(M); }
@@ -742,6 +765,45 @@ int check_shared(const char* fn, int64_t M, int64_t B, int64_t d, int64_t V, int
     return fail(fn, "M, V or B too large");
   return 0;
 }
+
+// the forward and the backward, with (items) and without the per-item
+// correction: item_shift is then required, else it is NULL
+int shared_softmax_fwd(const char* fn, bool items, const float* h, int64_t ldh,
+                       const float* table, const int64_t* target, const int64_t* neg,
+                       const int64_t* offsets, const int64_t* order, int64_t M, int64_t B,
+                       int64_t d, int64_t V, int64_t n_neg, int64_t max_len, float shift,
+                       const float* item_shift, float* lse, float* z0, float* loss,
+                       int64_t* n_live, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!h || !table || !target || !neg || !offsets || !order || !lse || !z0 || !loss || !n_live ||
+      !workspace || (items && !item_shift))
+    return fail(fn, "null pointer");
+  if (int rc = check_shared(fn, M, B, d, V, n_neg, max_len, shift)) return rc;
+  if (ldh < d || ldh % 4 || !aligned16(h) || !aligned16(table))
+    return fail(fn, "h and table must be 16-B aligned with ldh >= d, ldh % 4 == 0");
+  if (workspace_bytes < shared_softmax_workspace_bytes(B, max_len) || !aligned16(workspace))
+    return fail(fn, "workspace too small or misaligned");
+  return launch_shared_softmax_fwd(h, ldh, table, target, neg, offsets, order, M, B, d, V, n_neg,
+                                   max_len, shift, item_shift, lse, z0, loss, n_live, workspace,
+                                   as_stream(stream));
+}
+
+int shared_softmax_bwd(const char* fn, bool items, const float* h, int64_t ldh,
+                       const float* table, const int64_t* target, const int64_t* neg,
+                       const int64_t* offsets, const int64_t* order, const float* lse,
+                       const float* dloss, const int64_t* n_live, int64_t M, int64_t B, int64_t d,
+                       int64_t V, int64_t n_neg, int64_t max_len, float shift,
+                       const float* item_shift, float* dh, float* coef, float* dneg,
+                       void* stream) {
+  if (!h || !table || !target || !neg || !offsets || !order || !lse || !dloss || !n_live || !dh ||
+      !coef || !dneg || (items && !item_shift))
+    return fail(fn, "null pointer");
+  if (int rc = check_shared(fn, M, B, d, V, n_neg, max_len, shift)) return rc;
+  if (ldh < d || ldh % 4 || !aligned16(h) || !aligned16(table))
+    return fail(fn, "h and table must be 16-B aligned with ldh >= d, ldh % 4 == 0");
+  return launch_shared_softmax_bwd(h, ldh, table, target, neg, offsets, order, lse, dloss, n_live,
+                                   M, B, d, V, n_neg, max_len, shift, item_shift, dh, coef, dneg,
+                                   as_stream(stream));
+}
 }  // namespace
 
 int64_t rb_shared_softmax_workspace(int64_t B, int64_t max_len) {
@@ -754,18 +816,21 @@ int rb_shared_softmax_fwd(const float* h, int64_t ldh, const float* table,
                           int64_t n_neg, int64_t max_len, float shift, float* lse, float* z0,
                           float* loss, int64_t* n_live, void* workspace,
                           int64_t workspace_bytes, void* stream) {
-  const char* fn = "rb_shared_softmax_fwd";
-  if (!h || !table || !target || !neg || !offsets || !order || !lse || !z0 || !loss || !n_live ||
-      !workspace)
-    return fail(fn, "null pointer");
-  if (int rc = check_shared(fn, M, B, d, V, n_neg, max_len, shift)) return rc;
-  if (ldh < d || ldh % 4 || !aligned16(h) || !aligned16(table))
-    return fail(fn, "h and table must be 16-B aligned with ldh >= d, ldh % 4 == 0");
-  if (workspace_bytes < shared_softmax_workspace_bytes(B, max_len) || !aligned16(workspace))
-    return fail(fn, "workspace too small or misaligned");
-  return launch_shared_softmax_fwd(h, ldh, table, target, neg, offsets, order, M, B, d, V, n_neg,
-                                   max_len, shift, lse, z0, loss, n_live, workspace,
-                                   as_stream(stream));
+  return shared_softmax_fwd("rb_shared_softmax_fwd", false, h, ldh, table, target, neg, offsets,
+                            order, M, B, d, V, n_neg, max_len, shift, nullptr, lse, z0, loss,
+                            n_live, workspace, workspace_bytes, stream);
+}
+
+int rb_shared_softmax_fwd_items(const float* h, int64_t ldh, const float* table,
+                                const int64_t* target, const int64_t* neg,
+                                const int64_t* offsets, const int64_t* order, int64_t M,
+                                int64_t B, int64_t d, int64_t V, int64_t n_neg, int64_t max_len,
+                                float shift, const float* item_shift, float* lse, float* z0,
+                                float* loss, int64_t* n_live, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+  return shared_softmax_fwd("rb_shared_softmax_fwd_items", true, h, ldh, table, target, neg,
+                            offsets, order, M, B, d, V, n_neg, max_len, shift, item_shift, lse, z0,
+                            loss, n_live, workspace, workspace_bytes, stream);
 }
 
 int rb_shared_softmax_bwd(const float* h, int64_t ldh, const float* table,
@@ -774,16 +839,21 @@ int rb_shared_softmax_bwd(const float* h, int64_t ldh, const float* table,
                           const int64_t* n_live, int64_t M, int64_t B, int64_t d, int64_t V,
                           int64_t n_neg, int64_t max_len, float shift, float* dh, float* coef,
                           float* dneg, void* stream) {
-  const char* fn = "rb_shared_softmax_bwd";
-  if (!h || !table || !target || !neg || !offsets || !order || !lse || !dloss || !n_live || !dh ||
-      !coef || !dneg)
-    return fail(fn, "null pointer");
-  if (int rc = check_shared(fn, M, B, d, V, n_neg, max_len, shift)) return rc;
-  if (ldh < d || ldh % 4 || !aligned16(h) || !aligned16(table))
-    return fail(fn, "h and table must be 16-B aligned with ldh >= d, ldh % 4 == 0");
-  return launch_shared_softmax_bwd(h, ldh, table, target, neg, offsets, order, lse, dloss, n_live,
-                                   M, B, d, V, n_neg, max_len, shift, dh, coef, dneg,
-                                   as_stream(stream));
+  return shared_softmax_bwd("rb_shared_softmax_bwd", false, h, ldh, table, target, neg, offsets,
+                            order, lse, dloss, n_live, M, B, d, V, n_neg, max_len, shift, nullptr,
+                            dh, coef, dneg, stream);
+}
+
+int rb_shared_softmax_bwd_items(const float* h, int64_t ldh, const float* table,
+                                const int64_t* target, const int64_t* neg,
+                                const int64_t* offsets, const int64_t* order, const float* lse,
+                                const float* dloss, const int64_t* n_live, int64_t M, int64_t B,
+                                int64_t d, int64_t V, int64_t n_neg, int64_t max_len, float shift,
+                                const float* item_shift, float* dh, float* coef, float* dneg,
+                                void* stream) {
+  return shared_softmax_bwd("rb_shared_softmax_bwd_items", true, h, ldh, table, target, neg,
+                            offsets, order, lse, dloss, n_live, M, B, d, V, n_neg, max_len, shift,
+                            item_shift, dh, coef, dneg, stream);
 }
 
 // ---- candidate-list scoring (include/recblr_candidates.h) ---------------------------

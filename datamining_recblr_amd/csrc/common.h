@@ -510,8 +510,8 @@ int launch_embedding_apply_scaled(const float* src, int64_t src_ld, int64_t src_
 int launch_sample_negatives(const int64_t* item_seq, int64_t seq_rs, const int64_t* lengths,
                             const int64_t* pos_items, const int64_t* offsets, const int64_t* inv,
                             int64_t B, int64_t L, int64_t n_neg, int64_t first, int64_t V,
-                            uint64_t seed, int64_t ntok, int64_t m_pad, int64_t* neg,
-                            hipStream_t st);
+                            uint64_t seed, int64_t ntok, int64_t m_pad, const int64_t* alias,
+                            int64_t* neg, hipStream_t st);   // alias: NULL = uniform
 int64_t pair_loss_workspace_bytes(int64_t M);
 int launch_pair_loss_fwd(const float* h, int64_t ldh, const float* tab, const int64_t* pos,
                          const int64_t* neg, int64_t M, int64_t d, int64_t V, int64_t n_neg,
@@ -526,14 +526,15 @@ int64_t shared_softmax_workspace_bytes(int64_t B, int64_t max_len);
 int launch_shared_softmax_fwd(const float* h, int64_t ldh, const float* tab, const int64_t* target,
                               const int64_t* neg, const int64_t* offsets, const int64_t* order,
                               int64_t M, int64_t B, int64_t d, int64_t V, int64_t n,
-                              int64_t max_len, float shift, float* lse, float* z0, float* loss,
-                              int64_t* n_live, void* workspace, hipStream_t st);
+                              int64_t max_len, float shift, const float* item_shift, float* lse,
+                              float* z0, float* loss, int64_t* n_live, void* workspace,
+                              hipStream_t st);   // item_shift: NULL = the scalar shift only
 int launch_shared_softmax_bwd(const float* h, int64_t ldh, const float* tab, const int64_t* target,
                               const int64_t* neg, const int64_t* offsets, const int64_t* order,
                               const float* lse, const float* dloss, const int64_t* n_live,
                               int64_t M, int64_t B, int64_t d, int64_t V, int64_t n,
-                              int64_t max_len, float shift, float* dh, float* coef, float* dneg,
-                              hipStream_t st);
+                              int64_t max_len, float shift, const float* item_shift, float* dh,
+                              float* coef, float* dneg, hipStream_t st);
 int launch_candidate_scores(const float* h, int64_t ldh, const float* tab, const int64_t* cand,
                             int64_t B, int64_t C, int64_t d, int64_t V, float* scores,
                             hipStream_t st);

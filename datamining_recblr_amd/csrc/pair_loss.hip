@@ -6,6 +6,14 @@
 //                         (its window's items and its target) sits in LDS,
 //                         every (position, negative) draw is one thread that
 //                         rejects Philox candidates against it;
+//   rb_sample_negatives_alias  the same kernel body with the candidates drawn
+//                         from an alias table instead of uniformly.  Attempt a
+//                         = 0 .. 15 takes the words (u, v) = (2 (a % 2), 2 (a %
+//                         2) + 1) of philox(counter = (b, t, j, a / 2)): the bin
+//                         is i = mulhi(u, R), its table word holds the
+//                         threshold (low 32 bits) and the alias bin (high 32
+//                         bits), the candidate is first + (v < threshold ? i :
+//                         alias).  One 8-byte read-only load per attempt;
 //   rb_pair_loss_fwd      x = h.E[pos] - h.E[neg], l = -log(gamma + sigmoid(x)),
 //                         a 16-lane group per row (16-B loads, the dot
 //                         products reduced inside the group), the mean over
@@ -37,6 +45,17 @@ __device__ __forceinline__ bool is_seen(const int* seen, int ns, uint32_t cand) 
   return s;
 }
 
+// the walk after 16 rejections: upward, cyclically, from the 16th candidate
+__device__ __forceinline__ int64_t walk_negative(const int* seen, int ns, uint32_t cand,
+                                                 uint32_t first, uint32_t R) {
+  uint32_t off = cand - first;
+  for (uint32_t k = 1; k < R; ++k) {
+    off = off + 1 == R ? 0u : off + 1;
+    if (!is_seen(seen, ns, first + off)) return (int64_t)(first + off);
+  }
+  return -1;   // every id of [first, V) is seen
+}
+
 // the negative of (b, t, j): attempt a is word a % 4 of philox(counter =
 // (b, t, j, a / 4)); the first unseen candidate of 16 wins, then the walk
 __device__ int64_t draw_negative(const int* seen, int ns, uint32_t b, uint32_t t, uint32_t j,
@@ -51,20 +70,39 @@ __device__ int64_t draw_negative(const int* seen, int ns, uint32_t b, uint32_t t
       if (!is_seen(seen, ns, cand)) return (int64_t)cand;
     }
   }
-  uint32_t off = cand - first;   // upward, cyclically, from the 16th candidate
-  for (uint32_t k = 1; k < R; ++k) {
-    off = off + 1 == R ? 0u : off + 1;
-    if (!is_seen(seen, ns, first + off)) return (int64_t)(first + off);
-  }
-  return -1;   // every id of [first, V) is seen
+  return walk_negative(seen, ns, cand, first, R);
 }
 
+// ... from the alias table [R]: attempt a is the words (2 (a % 2), 2 (a % 2) +
+// 1) of philox(counter = (b, t, j, a / 2)).  An alias bin past the table is
+// read as the last one, so a candidate never leaves [first, V).
+__device__ int64_t draw_negative_alias(const int* seen, int ns, uint32_t b, uint32_t t, uint32_t j,
+                                       uint32_t first, uint32_t R, uint32_t k0, uint32_t k1,
+                                       const int64_t* __restrict__ alias) {
+  uint32_t cand = first;
+  for (uint32_t g = 0; g < kAttempts / 2; ++g) {
+    const uint4 r = philox4x32_10(make_uint4(b, t, j, g), k0, k1);
+    const uint32_t u[2] = {r.x, r.z}, v[2] = {r.y, r.w};
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const uint32_t i = __umulhi(u[a], R);
+      const uint64_t e = (uint64_t)alias[i];
+      const uint32_t other = min((uint32_t)(e >> 32), R - 1);
+      cand = first + (v[a] < (uint32_t)e ? i : other);
+      if (!is_seen(seen, ns, cand)) return (int64_t)cand;
+    }
+  }
+  return walk_negative(seen, ns, cand, first, R);
+}
+
+template <bool kAlias>
 __global__ void __launch_bounds__(256)
 k_sample_negatives(const int64_t* __restrict__ item_seq, int64_t seq_rs,
                    const int64_t* __restrict__ lengths, const int64_t* __restrict__ pos_items,
                    const int64_t* __restrict__ offsets, const int64_t* __restrict__ inv, int64_t B,
                    int64_t L, int n_neg, int64_t first, int64_t V, uint32_t k0, uint32_t k1,
-                   int64_t ntok, int64_t m_pad, int64_t* __restrict__ neg) {
+                   int64_t ntok, int64_t m_pad, const int64_t* __restrict__ alias,
+                   int64_t* __restrict__ neg) {
   extern __shared__ int seen[];   // L + 1 ids
   const int64_t b = blockIdx.x;
   if (b >= B) {   // the workgroups past the batch: the padding rows [ntok, m_pad)
@@ -98,8 +136,13 @@ k_sample_negatives(const int64_t* __restrict__ item_seq, int64_t seq_rs,
     const int64_t t = t0 + w / n_neg, j = w % n_neg;
     const int64_t r = dense ? row0 + t : row0;
     if (r >= rows) continue;
-    neg[r * n_neg + j] = draw_negative(seen, ns, (uint32_t)b, (uint32_t)t, (uint32_t)j,
-                                       (uint32_t)first, (uint32_t)(V - first), k0, k1);
+    if constexpr (kAlias)
+      neg[r * n_neg + j] = draw_negative_alias(seen, ns, (uint32_t)b, (uint32_t)t, (uint32_t)j,
+                                               (uint32_t)first, (uint32_t)(V - first), k0, k1,
+                                               alias);
+    else
+      neg[r * n_neg + j] = draw_negative(seen, ns, (uint32_t)b, (uint32_t)t, (uint32_t)j,
+                                         (uint32_t)first, (uint32_t)(V - first), k0, k1);
   }
 }
 
@@ -291,14 +334,15 @@ int64_t pair_loss_workspace_bytes(int64_t M) {
 int launch_sample_negatives(const int64_t* item_seq, int64_t seq_rs, const int64_t* lengths,
                             const int64_t* pos_items, const int64_t* offsets, const int64_t* inv,
                             int64_t B, int64_t L, int64_t n_neg, int64_t first, int64_t V,
-                            uint64_t seed, int64_t ntok, int64_t m_pad, int64_t* neg,
-                            hipStream_t st) {
+                            uint64_t seed, int64_t ntok, int64_t m_pad, const int64_t* alias,
+                            int64_t* neg, hipStream_t st) {
   const int64_t pad_blocks = ((m_pad - ntok) * n_neg + 255) / 256;
-  hipLaunchKernelGGL(k_sample_negatives, dim3((unsigned)(B + pad_blocks)), dim3(256),
+  const auto kernel = alias ? k_sample_negatives<true> : k_sample_negatives<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(B + pad_blocks)), dim3(256),
                      (size_t)(L + 1) * sizeof(int), st, item_seq, seq_rs, lengths, pos_items,
                      offsets, inv, B, L, (int)n_neg, first, V, (uint32_t)seed,
-                     (uint32_t)(seed >> 32), ntok, m_pad, neg);
-  return launch_status("rb_sample_negatives");
+                     (uint32_t)(seed >> 32), ntok, m_pad, alias, neg);
+  return launch_status(alias ? "rb_sample_negatives_alias" : "rb_sample_negatives");
 }
 
 int launch_pair_loss_fwd(const float* h, int64_t ldh, const float* tab, const int64_t* pos,

@@ -28,6 +28,13 @@
 //                           sequence's row blocks in order.
 // No float atomics; every sum has a fixed order that depends on the row's
 // sequence and its position in it only.
+//
+//   rb_shared_softmax_fwd_items / _bwd_items   the same three kernel bodies
+//                           (kItems) with a per-item correction of the
+//                           proposal: a live column of id j scores z_j = (h_r .
+//                           E[j] + shift) + item_shift[j], one 4-byte gather
+//                           per column and 16-row tile; a dead or out-of-range
+//                           column reads nothing.
 #include "common.h"
 
 namespace rb {
@@ -89,11 +96,13 @@ __device__ __forceinline__ void ss_col_ids(const int64_t* __restrict__ neg, int6
   }
 }
 
+template <bool kItems>
 __global__ void __launch_bounds__(256)
 k_ss_fwd(const float* __restrict__ h, int64_t ldh, const float* __restrict__ tab,
          const int64_t* __restrict__ target, const int64_t* __restrict__ neg,
          const int64_t* __restrict__ offsets, const int64_t* __restrict__ order, int64_t M,
-         int64_t B, int d, int64_t V, int n, int RB, float shift, float* __restrict__ lse,
+         int64_t B, int d, int64_t V, int n, int RB, float shift,
+         const float* __restrict__ item_shift, float* __restrict__ lse,
          float* __restrict__ z0o, float* psum, int* pcnt, unsigned* ticket,
          float* __restrict__ loss, int64_t* __restrict__ n_live) {
   __shared__ float s_sum[4];
@@ -139,7 +148,8 @@ k_ss_fwd(const float* __restrict__ h, int64_t ldh, const float* __restrict__ tab
         for (int k = 0; k < 4; ++k) {
           bad |= in && (id[k] < -1 || id[k] >= V);
           if (id[k] >= 0 && id[k] < V) {
-            const float z = acc[k] + shift;
+            float z = acc[k] + shift;
+            if constexpr (kItems) z += item_shift[id[k]];
             if (z > m) {
               sum = sum * expf(m - z) + 1.0f;
               m = z;
@@ -220,13 +230,15 @@ k_ss_fwd(const float* __restrict__ h, int64_t ldh, const float* __restrict__ tab
 
 // dh_r = scale (sum_j p_rj E[neg_j] - (sum_j p_rj) E[target_r]), coef_r = -scale
 // sum_j p_rj (sum_j p_j = 1 - p_0 without the cancellation)
+template <bool kItems>
 __global__ void __launch_bounds__(256)
 k_ss_dh(const float* __restrict__ h, int64_t ldh, const float* __restrict__ tab,
         const int64_t* __restrict__ target, const int64_t* __restrict__ neg,
         const int64_t* __restrict__ offsets, const int64_t* __restrict__ order,
         const float* __restrict__ lse, const float* __restrict__ dloss,
         const int64_t* __restrict__ n_live, int64_t M, int64_t B, int d, int64_t V, int n, int RB,
-        float shift, float* __restrict__ dh, float* __restrict__ coef) {
+        float shift, const float* __restrict__ item_shift, float* __restrict__ dh,
+        float* __restrict__ coef) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int64_t s = blockIdx.x / RB;
   const int rb0 = blockIdx.x % RB;
@@ -260,7 +272,11 @@ k_ss_dh(const float* __restrict__ h, int64_t ldh, const float* __restrict__ tab,
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const bool ok = id[k] >= 0 && id[k] < V;
-        p[k] = live && ok ? expf(z[k] + shift - l) : 0.0f;
+        float zk = z[k] + shift;
+        if constexpr (kItems) {
+          if (ok) zk += item_shift[id[k]];
+        }
+        p[k] = live && ok ? expf(zk - l) : 0.0f;
         psum += p[k];
         p[k] *= scale;
         ep[k] = tab + (ok ? id[k] : 0) * d + c;
@@ -302,13 +318,14 @@ k_ss_dh(const float* __restrict__ h, int64_t ldh, const float* __restrict__ tab,
 // ([row][column]: lane = column c) and leaves P in Pt; then wave w owns the
 // 16-column tiles dt = w, w + 4 ... of dneg's d and adds the block's four row
 // tiles in order.
+template <bool kItems>
 __global__ void __launch_bounds__(256)
 k_ss_dneg(const float* __restrict__ h, int64_t ldh, const float* __restrict__ tab,
           const int64_t* __restrict__ target, const int64_t* __restrict__ neg,
           const int64_t* __restrict__ offsets, const int64_t* __restrict__ order,
           const float* __restrict__ lse, const float* __restrict__ dloss,
           const int64_t* __restrict__ n_live, int64_t M, int64_t B, int d, int64_t V, int n,
-          float shift, float* __restrict__ dneg) {
+          float shift, const float* __restrict__ item_shift, float* __restrict__ dneg) {
   extern __shared__ float ss_smem[];
   const int ldH = d + 4;
   float* Hs = ss_smem;                  // [64][ldH]
@@ -325,6 +342,10 @@ k_ss_dneg(const float* __restrict__ h, int64_t ldh, const float* __restrict__ ta
   const int64_t ida = ca < n ? neg[q.b * n + ca] : -1;
   const bool oka = ida >= 0 && ida < V;
   const float* ap = tab + (oka ? ida : 0) * d + 4 * g;
+  float isa = 0.0f;   // the lane's column's item_shift
+  if constexpr (kItems) {
+    if (oka) isa = item_shift[ida];
+  }
   rb_f32x4 acc[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) acc[i] = rb_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -344,7 +365,11 @@ k_ss_dneg(const float* __restrict__ h, int64_t ldh, const float* __restrict__ ta
       float p = 0.0f;
       if (row < q.end && oka) {
         const int64_t t = target[row];
-        if (t >= 0 && t < V) p = scale * expf(z[k] + shift - lse[row]);
+        if (t >= 0 && t < V) {
+          float zk = z[k] + shift;
+          if constexpr (kItems) zk += isa;
+          p = scale * expf(zk - lse[row]);
+        }
       }
       Pt[(wave * 16 + 4 * g + k) * kPtLd + c] = p;
     }
@@ -395,38 +420,41 @@ int64_t shared_softmax_workspace_bytes(int64_t B, int64_t max_len) {
 int launch_shared_softmax_fwd(const float* h, int64_t ldh, const float* tab, const int64_t* target,
                               const int64_t* neg, const int64_t* offsets, const int64_t* order,
                               int64_t M, int64_t B, int64_t d, int64_t V, int64_t n,
-                              int64_t max_len, float shift, float* lse, float* z0, float* loss,
-                              int64_t* n_live, void* workspace, hipStream_t st) {
+                              int64_t max_len, float shift, const float* item_shift, float* lse,
+                              float* z0, float* loss, int64_t* n_live, void* workspace,
+                              hipStream_t st) {
+  const char* fn = item_shift ? "rb_shared_softmax_fwd_items" : "rb_shared_softmax_fwd";
   char* ws = static_cast<char*>(workspace);
   const int RB = ss_row_blocks(max_len);
   const int64_t nb = B * RB;
   unsigned* ticket = reinterpret_cast<unsigned*>(ws);
   float* psum = reinterpret_cast<float*>(ws + 16);
   int* pcnt = reinterpret_cast<int*>(psum + nb);
-  if (hipMemsetAsync(ticket, 0, 16, st) != hipSuccess)
-    return launch_status("rb_shared_softmax_fwd");
-  hipLaunchKernelGGL(k_ss_fwd, dim3((unsigned)nb), dim3(256), 0, st, h, ldh, tab, target, neg,
-                     offsets, order, M, B, (int)d, V, (int)n, RB, shift, lse, z0, psum, pcnt,
-                     ticket, loss, n_live);
-  return launch_status("rb_shared_softmax_fwd");
+  if (hipMemsetAsync(ticket, 0, 16, st) != hipSuccess) return launch_status(fn);
+  hipLaunchKernelGGL(item_shift ? k_ss_fwd<true> : k_ss_fwd<false>, dim3((unsigned)nb), dim3(256),
+                     0, st, h, ldh, tab, target, neg, offsets, order, M, B, (int)d, V, (int)n, RB,
+                     shift, item_shift, lse, z0, psum, pcnt, ticket, loss, n_live);
+  return launch_status(fn);
 }
 
 int launch_shared_softmax_bwd(const float* h, int64_t ldh, const float* tab, const int64_t* target,
                               const int64_t* neg, const int64_t* offsets, const int64_t* order,
                               const float* lse, const float* dloss, const int64_t* n_live,
                               int64_t M, int64_t B, int64_t d, int64_t V, int64_t n,
-                              int64_t max_len, float shift, float* dh, float* coef, float* dneg,
-                              hipStream_t st) {
+                              int64_t max_len, float shift, const float* item_shift, float* dh,
+                              float* coef, float* dneg, hipStream_t st) {
+  const char* fn = item_shift ? "rb_shared_softmax_bwd_items" : "rb_shared_softmax_bwd";
   const int RB = ss_row_blocks(max_len);
-  hipLaunchKernelGGL(k_ss_dh, dim3((unsigned)(B * RB)), dim3(256), 0, st, h, ldh, tab, target, neg,
-                     offsets, order, lse, dloss, n_live, M, B, (int)d, V, (int)n, RB, shift, dh,
-                     coef);
-  if (int rc = launch_status("rb_shared_softmax_bwd")) return rc;
+  hipLaunchKernelGGL(item_shift ? k_ss_dh<true> : k_ss_dh<false>, dim3((unsigned)(B * RB)),
+                     dim3(256), 0, st, h, ldh, tab, target, neg, offsets, order, lse, dloss,
+                     n_live, M, B, (int)d, V, (int)n, RB, shift, item_shift, dh, coef);
+  if (int rc = launch_status(fn)) return rc;
   const int64_t NT = (n + 15) / 16;
   const size_t lds = (size_t)kSsRows * (d + 4 + kPtLd) * sizeof(float);
-  hipLaunchKernelGGL(k_ss_dneg, dim3((unsigned)(B * NT)), dim3(256), lds, st, h, ldh, tab, target,
-                     neg, offsets, order, lse, dloss, n_live, M, B, (int)d, V, (int)n, shift, dneg);
-  return launch_status("rb_shared_softmax_bwd");
+  hipLaunchKernelGGL(item_shift ? k_ss_dneg<true> : k_ss_dneg<false>, dim3((unsigned)(B * NT)),
+                     dim3(256), lds, st, h, ldh, tab, target, neg, offsets, order, lse, dloss,
+                     n_live, M, B, (int)d, V, (int)n, shift, item_shift, dneg);
+  return launch_status(fn);
 }
 
 }  // namespace rb

@@ -35,7 +35,8 @@ import numpy as np
 import torch
 
 __all__ = ["load_atomic", "kcore_filter", "remap_tokens", "SequentialData", "build_sequential",
-           "build_batch", "dense_windows", "SequentialLoader", "write_atomic", "from_atomic_file"]
+           "build_batch", "dense_windows", "train_item_counts", "SequentialLoader", "write_atomic",
+           "from_atomic_file"]
 
 
 def load_atomic(path: str, columns=("user_id", "item_id", "timestamp")) -> dict:
@@ -200,6 +201,31 @@ def dense_windows(desc: torch.Tensor, max_len: int) -> torch.Tensor:
     out = np.asarray(rows, dtype=np.int64)
     out = out[np.lexsort((out[:, 1], out[:, 0]))]
     return torch.from_numpy(out).to(desc.device)
+
+
+def train_item_counts(data: SequentialData) -> torch.Tensor:
+    """How often each item occurs in the train split: counts [n_items] int64
+    (on data's device) over the interactions that are a train sample's target
+    or one of its inputs — each user's run from its start to its last train
+    target, every interaction once (not once per prefix that holds it).  The
+    held-out valid and test targets are not counted, so an item only they
+    hold has count 0.  Feeds the popularity proposal of the sampled losses
+    (RecBLR.set_item_counts)."""
+    d = data.train.detach().cpu().numpy()
+    items = data.items.detach().cpu().numpy()
+    counts = np.zeros(data.n_items, dtype=np.int64)
+    if len(d):
+        d = d[np.argsort(d[:, 0], kind="stable")]
+        starts, first = np.unique(d[:, 0], return_index=True)
+        last = np.maximum.reduceat(d[:, 1], first)   # each user's last train target
+        # +1 at a user's run start, -1 after its last train target (the runs
+        # of two users do not overlap)
+        mark = np.zeros(len(items) + 1, dtype=np.int64)
+        mark[starts] += 1
+        mark[last + 1] -= 1
+        used = np.cumsum(mark[:-1]) > 0
+        counts = np.bincount(items[used], minlength=data.n_items).astype(np.int64)
+    return torch.from_numpy(counts).to(data.items.device)
 
 
 class SequentialLoader:

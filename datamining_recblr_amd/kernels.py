@@ -23,7 +23,8 @@ __all__ = [
     "embedding_bwd", "embedding_plan",
     "item_ce_fwd_h_rows", "item_ce_probs_h_rows", "item_ce_probs_h_both_rows",
     "next_item_targets", "next_item_targets_reference",
-    "sample_negatives", "sample_negatives_reference", "philox4x32_10", "pair_loss_fwd",
+    "sample_negatives", "sample_negatives_reference", "negative_sampler", "NegativeSampler",
+    "philox4x32_10", "pair_loss_fwd",
     "pair_loss_bwd", "embedding_bwd_scaled", "pair_loss_supported", "shared_softmax_fwd",
     "shared_softmax_bwd", "shared_softmax_supported", "MAX_SHARED_NEGATIVES",
     "candidate_scores", "candidate_topk", "candidate_ranks", "candidates_supported",
@@ -1180,7 +1181,8 @@ def pair_loss_supported(h: torch.Tensor, table: torch.Tensor) -> bool:
 def sample_negatives(item_seq: torch.Tensor, lengths: torch.Tensor, pos_items: torch.Tensor,
                      n_neg: int, first_item: int, num_items: int, seed: int,
                      offsets: torch.Tensor | None = None, inv: torch.Tensor | None = None,
-                     ntok: int | None = None, m_pad: int | None = None) -> torch.Tensor:
+                     ntok: int | None = None, m_pad: int | None = None,
+                     alias: torch.Tensor | None = None) -> torch.Tensor:
     """rb_sample_negatives: n_neg ids per position, uniform over [first_item,
     num_items) minus the row's seen set item_seq[b, :len_b] + {pos_items[b]}
     (the row's window, not the user's whole history); -1 when every id is
@@ -1189,9 +1191,19 @@ def sample_negatives(item_seq: torch.Tensor, lengths: torch.Tensor, pos_items: t
     ntok; the rows past ntok are -1); without them [B, n_neg], each row's last
     position — the dense call's rows at Packed.last.  The draw of (b, t,
     j) depends only on (seed, b, t, j) and the row: see
-    sample_negatives_reference."""
+    sample_negatives_reference.  alias (NegativeSampler.alias, int64
+    [num_items - first_item] on the device): the candidates come from that
+    table instead of the uniform draw (rb_sample_negatives_alias); the
+    rejection, the walk and the layouts are the same, and the draw then
+    depends on the table too."""
     for t, n in ((item_seq, "item_seq"), (lengths, "lengths"), (pos_items, "pos_items")):
         _check(t, n, torch.int64)
+    if alias is not None:
+        _check(alias, "alias", torch.int64)
+        if alias.shape != (int(num_items) - int(first_item),) or not alias.is_contiguous():
+            raise ValueError(f"alias must be a contiguous [num_items - first_item] = "
+                             f"[{int(num_items) - int(first_item)}] table, got "
+                             f"{tuple(alias.shape)}")
     if item_seq.dim() != 2 or item_seq.stride(1) != 1:
         item_seq = item_seq.contiguous()
     B, L = item_seq.shape
@@ -1210,11 +1222,13 @@ def sample_negatives(item_seq: torch.Tensor, lengths: torch.Tensor, pos_items: t
     else:
         ntok = m_pad = B
     out = torch.empty((m_pad, int(n_neg)), device=item_seq.device, dtype=torch.int64)
-    _launch("rb_sample_negatives", 8 * (B * L + out.numel()), item_seq.data_ptr(),
+    name = "rb_sample_negatives" if alias is None else "rb_sample_negatives_alias"
+    table = () if alias is None else (alias.data_ptr(),)
+    _launch(name, 8 * (B * L + out.numel()), item_seq.data_ptr(),
             item_seq.stride(0), lengths.contiguous().data_ptr(), pos_items.contiguous().data_ptr(),
             offsets.data_ptr() if offsets is not None else None,
             inv.data_ptr() if inv is not None else None, B, L, int(n_neg), int(first_item),
-            int(num_items), int(seed) & (2 ** 64 - 1), ntok, m_pad, out.data_ptr(),
+            int(num_items), int(seed) & (2 ** 64 - 1), ntok, m_pad, *table, out.data_ptr(),
             _stream(item_seq))
     return out
 
@@ -1238,13 +1252,103 @@ def philox4x32_10(counter, key):
     return c
 
 
+class NegativeSampler:
+    """A proposal over the ids [first_item, V) for sample_negatives (see
+    negative_sampler): alias int64 [V - first_item] (one word per bin: the low
+    32 bits the threshold, the high 32 bits the alias bin), item_shift fp32
+    [V] = -log(q) and q float64 [V], the probability with which the draw rule
+    proposes each id (0, and item_shift 0, below first_item).  q_num holds q
+    exactly: q[first_item + i] = q_num[i] / 2**64, Python integers."""
+
+    def __init__(self, alias, item_shift, q, first_item, q_num):
+        self.alias, self.item_shift, self.q = alias, item_shift, q
+        self.first_item, self.q_num = int(first_item), q_num
+
+    def to(self, device):
+        return NegativeSampler(self.alias.to(device), self.item_shift.to(device),
+                               self.q.to(device), self.first_item, self.q_num)
+
+
+def negative_sampler(counts, alpha: float = 0.75, smoothing: float = 1.0, first_item: int = 1,
+                     n_items: int | None = None) -> NegativeSampler:
+    """The popularity proposal of the sampled losses: id i in [first_item, V)
+    (V = n_items or len(counts)) is proposed in proportion to w_i = (counts[i]
+    + smoothing) ** alpha (word2vec's unigram ** 0.75; smoothing keeps the
+    items without a count — the ones only the held-out splits hold —
+    drawable).  Returns a NegativeSampler of CPU tensors (numpy only here).
+
+    The table is Vose's alias method in float64 over the R = V - first_item
+    bins; a bin's threshold is min(floor(p * 2**32), 2**32 - 1) and a full bin
+    aliases itself.  Attempt a of sample_negatives(alias=...) takes two Philox
+    words (u, v): the bin is i = mulhi(u, R) and the candidate first_item + (i
+    if v < threshold[i] else alias[i]).  q is the distribution of that rule,
+    from the table as built, in integer arithmetic: bin k receives ceil((k +
+    1) 2**32 / R) - ceil(k 2**32 / R) of the 2**32 values of u and passes
+    threshold[k] of the 2**32 values of v — so q is what the kernel draws
+    (before the rejection against a row's seen set), not what was asked for,
+    and sums to 1 exactly.  item_shift = float32(-log(q)) is the per-item
+    log-Q correction of scoring.shared_softmax_loss."""
+    import numpy as np
+
+    c = np.asarray(counts, dtype=np.float64).reshape(-1)
+    V = len(c) if n_items is None else int(n_items)
+    first = int(first_item)
+    R = V - first
+    if first < 0 or R < 1:
+        raise ValueError(f"negative_sampler: no id in [first_item, V) = [{first}, {V})")
+    if len(c) < V:
+        raise ValueError(f"negative_sampler: {len(c)} counts for {V} items")
+    with np.errstate(all="ignore"):
+        w = (c[first:V] + float(smoothing)) ** float(alpha)
+    if not (np.isfinite(w).all() and (w > 0).all()):
+        raise ValueError("negative_sampler: every weight (count + smoothing) ** alpha in range "
+                         "must be positive and finite")
+    p = w / w.sum() * R
+    if not np.isfinite(p).all():
+        raise ValueError("negative_sampler: the weights' sum is not finite")
+    # Vose: a bin below 1 is filled up by a bin above 1, which gives that much away
+    prob = np.ones(R, dtype=np.float64)
+    other = np.arange(R, dtype=np.int64)       # a full bin aliases itself
+    small = [i for i in range(R) if p[i] < 1.0]
+    large = [i for i in range(R) if p[i] >= 1.0]
+    while small and large:
+        s, l = small.pop(), large.pop()
+        prob[s], other[s] = p[s], l
+        p[l] = (p[l] + p[s]) - 1.0
+        (small if p[l] < 1.0 else large).append(l)
+    thresh = np.clip(np.floor(prob * 2.0 ** 32), 0.0, 2.0 ** 32 - 1).astype(np.uint64)
+    alias = ((other.astype(np.uint64) << np.uint64(32)) | thresh).view(np.int64)
+    # the rule's distribution, exactly: numerators over 2**64
+    edge = [-((-k << 32) // R) for k in range(R + 1)]      # ceil(k 2**32 / R)
+    num = [0] * R
+    for k, (t, o) in enumerate(zip(thresh.tolist(), other.tolist())):
+        words = edge[k + 1] - edge[k]
+        num[k] += words * t
+        num[o] += words * ((1 << 32) - t)
+    q = np.zeros(V, dtype=np.float64)
+    q[first:] = [x / (1 << 64) for x in num]
+    if not (q[first:] > 0).all():
+        raise ValueError("negative_sampler: an item's probability rounds to zero "
+                         "(its weight is below 2**-32 of the mean)")
+    shift = np.zeros(V, dtype=np.float32)
+    shift[first:] = (-np.log(q[first:])).astype(np.float32)
+    return NegativeSampler(torch.from_numpy(alias), torch.from_numpy(shift), torch.from_numpy(q),
+                           first, num)
+
+
 def sample_negatives_reference(item_seq, lengths, pos_items, n_neg, first_item, num_items, seed,
-                               offsets=None, inv=None, ntok=None, m_pad=None, stats=None):
+                               offsets=None, inv=None, ntok=None, m_pad=None, stats=None,
+                               alias=None):
     """sample_negatives restated on the host (numpy, its own Philox): the
     checked reference, and the CPU path of the data loader.  Same arguments;
     returns a CPU int64 tensor.  stats: a dict
     that receives how many draws were settled by the 16 attempts
-    ("attempts"), by the walk ("walk"), or found every id seen ("exhausted")."""
+    ("attempts"), by the walk ("walk"), or found every id seen ("exhausted").
+    Uniform (alias None): attempt a is word a % 4 of philox(counter = (b, t, j,
+    a // 4)) mapped to first_item + mulhi(word, R).  With alias
+    (NegativeSampler.alias): attempt a takes (u, v) = words (2 (a % 2), 2 (a %
+    2) + 1) of philox(counter = (b, t, j, a // 2)), the bin i = mulhi(u, R) and
+    the candidate first_item + (i if v < threshold[i] else alias[i])."""
     import numpy as np
 
     seq = item_seq.detach().cpu().numpy().astype(np.int64)
@@ -1262,6 +1366,12 @@ def sample_negatives_reference(item_seq, lengths, pos_items, n_neg, first_item, 
         rows = int(ntok) if m_pad is None else int(m_pad)
     else:
         rows = B
+    if alias is not None:
+        words64 = alias.detach().cpu().numpy().astype(np.int64).view(np.uint64)
+        if words64.shape != (R,):
+            raise ValueError(f"alias must be [num_items - first_item] = [{R}]")
+        thresh = words64 & np.uint64(0xFFFFFFFF)
+        other = np.minimum(words64 >> np.uint64(32), np.uint64(R - 1)).astype(np.int64)
     out = np.full((rows, n_neg), -1, dtype=np.int64)
     count = {"attempts": 0, "walk": 0, "exhausted": 0}
     for b in range(B):
@@ -1273,10 +1383,16 @@ def sample_negatives_reference(item_seq, lengths, pos_items, n_neg, first_item, 
         res = np.full(tt.shape, -2, dtype=np.int64)   # -2: not settled yet
         cand = np.zeros(tt.shape, dtype=np.int64)
         for a in range(SAMPLE_ATTEMPTS):
-            if a % 4 == 0:
-                words = philox4x32_10((np.full(tt.shape, b), tt, jj, np.full(tt.shape, a // 4)),
+            per = 4 if alias is None else 2   # attempts per Philox call
+            if a % per == 0:
+                words = philox4x32_10((np.full(tt.shape, b), tt, jj, np.full(tt.shape, a // per)),
                                       key)
-            cand = first + ((words[a % 4] * np.uint64(R)) >> np.uint64(32)).astype(np.int64)
+            if alias is None:
+                cand = first + ((words[a % 4] * np.uint64(R)) >> np.uint64(32)).astype(np.int64)
+            else:
+                u, v = words[2 * (a % 2)], words[2 * (a % 2) + 1]
+                i = ((u * np.uint64(R)) >> np.uint64(32)).astype(np.int64)
+                cand = first + np.where(v < thresh[i], i, other[i])
             free = (res == -2) & ~np.isin(cand, list(seen))
             res[free] = cand[free]
         count["attempts"] += int((res != -2).sum())
@@ -1390,16 +1506,30 @@ def _shared_operands(h, table, target, neg, offsets, order):
     return M, d, B, n, table.shape[0]
 
 
+def _item_shift_operand(item_shift, V):
+    """The launch-name suffix and the extra argument of the _items entry points
+    (none for item_shift None)."""
+    if item_shift is None:
+        return "", ()
+    _check(item_shift, "item_shift")
+    if item_shift.shape != (V,) or not item_shift.is_contiguous():
+        raise ValueError(f"item_shift must be a contiguous [V] = [{V}] tensor, got "
+                         f"{tuple(item_shift.shape)}")
+    return "_items", (item_shift.data_ptr(),)
+
+
 def shared_softmax_fwd(h: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
                        neg: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor,
-                       shift: float, max_len: int):
+                       shift: float, max_len: int, item_shift: torch.Tensor | None = None):
     """rb_shared_softmax_fwd: (loss [], n_live [] int64, lse [M], z0 [M]) of the
     packed rows h [M, d] (unit-stride rows, any 16-B aligned row stride)
     against table [V, d]: target [M] int64 (-1 = ignored row), neg [B, n] int64
     (one list per batch row, -1 = dead column), offsets [B + 1] / order [B] the
     pack plan.  max_len: an upper estimate of the longest sequence (sizes the
-    grid only)."""
+    grid only).  item_shift fp32 [V]: the per-item term of a column's score,
+    z_j = (h . E[j] + shift) + item_shift[j] (rb_shared_softmax_fwd_items)."""
     M, d, B, n, V = _shared_operands(h, table, target, neg, offsets, order)
+    sfx, items = _item_shift_operand(item_shift, V)
     dev = h.device
     lse = torch.zeros((M,), device=dev, dtype=torch.float32)
     z0 = torch.zeros((M,), device=dev, dtype=torch.float32)
@@ -1408,30 +1538,33 @@ def shared_softmax_fwd(h: torch.Tensor, table: torch.Tensor, target: torch.Tenso
     max_len = max(int(max_len), 1)
     ws_bytes = int(_lib.load().rb_shared_softmax_workspace(B, max_len))
     ws = torch.empty((ws_bytes,), device=dev, dtype=torch.uint8)
-    _launch("rb_shared_softmax_fwd", 4 * (2 * M + B * n) * d, h.data_ptr(), h.stride(0),
+    _launch("rb_shared_softmax_fwd" + sfx, 4 * (2 * M + B * n) * d, h.data_ptr(), h.stride(0),
             table.data_ptr(), target.data_ptr(), neg.data_ptr(), offsets.data_ptr(),
-            order.data_ptr(), M, B, d, V, n, max_len, float(shift), lse.data_ptr(), z0.data_ptr(),
-            loss.data_ptr(), n_live.data_ptr(), ws.data_ptr(), ws_bytes, _stream(h))
+            order.data_ptr(), M, B, d, V, n, max_len, float(shift), *items, lse.data_ptr(),
+            z0.data_ptr(), loss.data_ptr(), n_live.data_ptr(), ws.data_ptr(), ws_bytes,
+            _stream(h))
     return loss, n_live, lse, z0
 
 
 def shared_softmax_bwd(h: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
                        neg: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor,
                        lse: torch.Tensor, dloss: torch.Tensor, n_live: torch.Tensor,
-                       shift: float, max_len: int):
+                       shift: float, max_len: int, item_shift: torch.Tensor | None = None):
     """rb_shared_softmax_bwd: (dh [M, d], coef [M], dneg [B, n, d]); the table's
     gradient is coef[r] * h_r scattered by target plus dneg's rows scattered by
-    neg.  Rows and lists the plan does not cover are zero."""
+    neg.  Rows and lists the plan does not cover are zero.  item_shift: the
+    forward's (rb_shared_softmax_bwd_items); it has no gradient."""
     M, d, B, n, V = _shared_operands(h, table, target, neg, offsets, order)
+    sfx, items = _item_shift_operand(item_shift, V)
     dev = h.device
     dh = torch.zeros((M, d), device=dev, dtype=torch.float32)
     coef = torch.zeros((M,), device=dev, dtype=torch.float32)
     dneg = torch.zeros((B, n, d), device=dev, dtype=torch.float32)
-    _launch("rb_shared_softmax_bwd", 4 * (3 * M + 2 * B * n) * d, h.data_ptr(), h.stride(0),
+    _launch("rb_shared_softmax_bwd" + sfx, 4 * (3 * M + 2 * B * n) * d, h.data_ptr(), h.stride(0),
             table.data_ptr(), target.data_ptr(), neg.data_ptr(), offsets.data_ptr(),
             order.data_ptr(), lse.data_ptr(), dloss.data_ptr(), n_live.data_ptr(), M, B, d, V, n,
-            max(int(max_len), 1), float(shift), dh.data_ptr(), coef.data_ptr(), dneg.data_ptr(),
-            _stream(h))
+            max(int(max_len), 1), float(shift), *items, dh.data_ptr(), coef.data_ptr(),
+            dneg.data_ptr(), _stream(h))
     return dh, coef, dneg
 
 

@@ -33,7 +33,7 @@ from .blocks import (ResidualGrad, add_dropout_layer_norm, draw_seed, embed_drop
                      feed_forward, linear_add_dropout_layer_norm)
 from .kernels import (MAX_NEGATIVES, MAX_SHARED_NEGATIVES, Packed, grl_max_tiles, grl_pieces,
                       next_item_targets, next_item_targets_reference, sample_negatives_reference,
-                      pack_plan, sample_negatives)
+                      negative_sampler, pack_plan, sample_negatives)
 from .linear import HipLinearForward, fire_hooks, has_hooks, linear
 from .recbole_compat import BPRLoss, SequentialRecommender, install_interaction_hook
 from .recurrence import bd_lru, fused_ok, pow2_pad_len, row_pad_lens
@@ -329,6 +329,31 @@ class RecBLR(SequentialRecommender):
         if self.dense_negatives and not self.train_all_positions:
             raise ValueError("dense_negatives needs train_all_positions: True (the negatives "
                              "are sampled at every position of a row)")
+        # the proposal the sampled negatives are drawn from: 'uniform', or
+        # 'popularity' — in proportion to (train count + dense_sampling_smoothing)
+        # ** dense_sampling_alpha, from the counts given to set_item_counts; not
+        # reference keys
+        def key(name, default):
+            try:
+                value = config[name]
+            except (KeyError, TypeError):
+                value = None
+            return default if value is None else value
+
+        self.dense_sampling = key("dense_sampling", "uniform")
+        if self.dense_sampling not in ("uniform", "popularity"):
+            raise ValueError(f"dense_sampling must be 'uniform' or 'popularity', got "
+                             f"{self.dense_sampling!r}")
+        self.dense_sampling_alpha = float(key("dense_sampling_alpha", 0.75))
+        self.dense_sampling_smoothing = float(key("dense_sampling_smoothing", 1.0))
+        if not (math.isfinite(self.dense_sampling_alpha)
+                and math.isfinite(self.dense_sampling_smoothing)
+                and self.dense_sampling_smoothing >= 0):
+            raise ValueError("dense_sampling_alpha must be finite and dense_sampling_smoothing "
+                             "finite and >= 0")
+        if self.dense_sampling == "popularity" and not self.dense_negatives:
+            raise ValueError("dense_sampling 'popularity' needs dense_negatives >= 1 (it is the "
+                             "proposal of the sampled losses)")
         if self.bd_lru_only:  # RecBLR.py:33-35
             self.disable_conv1d = True
             self.disable_ffn = True
@@ -358,7 +383,39 @@ class RecBLR(SequentialRecommender):
             self.loss_fct = nn.CrossEntropyLoss()
         else:
             raise NotImplementedError("Make sure 'loss_type' in ['BPR', 'CE']!")
+        # the popularity proposal (set_item_counts): derived from the data, so
+        # not part of the state_dict
+        self.register_buffer("neg_alias", None, persistent=False)
+        self.register_buffer("neg_item_shift", None, persistent=False)
         self.apply(self._init_weights)
+
+    def set_item_counts(self, counts):
+        """Build the popularity proposal of dense_sampling 'popularity' from
+        counts [n_items] (how often each item occurs in the train split,
+        data.train_item_counts): kernels.negative_sampler with the model's
+        dense_sampling_alpha and dense_sampling_smoothing over the ids [1,
+        n_items), kept on the model's device as the non-persistent buffers
+        neg_alias and neg_item_shift.  Returns the NegativeSampler (host
+        tensors; .q is the proposal's exact distribution)."""
+        if torch.is_tensor(counts):
+            counts = counts.detach().cpu().numpy()
+        sampler = negative_sampler(counts, self.dense_sampling_alpha,
+                                   self.dense_sampling_smoothing, 1, self.n_items)
+        dev = self.item_embedding.weight.device
+        self.neg_alias = sampler.alias.to(dev)
+        self.neg_item_shift = sampler.item_shift.to(dev)
+        return sampler
+
+    def _proposal(self):
+        """(alias, item_shift) of the sampled losses' proposal: (None, None)
+        for the uniform one."""
+        if self.dense_sampling != "popularity":
+            return None, None
+        if self.neg_alias is None:
+            raise RuntimeError("dense_sampling 'popularity' needs the items' train counts: call "
+                               "model.set_item_counts(data.train_item_counts(dataset)) first "
+                               "(trainer.fit does)")
+        return self.neg_alias, self.neg_item_shift
 
     @staticmethod
     def _init_weights(module):
@@ -543,15 +600,19 @@ class RecBLR(SequentialRecommender):
         window and target.  RecBole rejects against the user's whole history;
         a row here knows only its window.  With one negative per position
         this equals the reference's BPR calculate_loss on the batch expanded
-        to one row per prefix with those negatives as NEG_ITEM_ID."""
+        to one row per prefix with those negatives as NEG_ITEM_ID.
+        dense_sampling 'popularity': the candidates come from the popularity
+        proposal (set_item_counts) instead; the pairwise loss has no proposal
+        correction, it simply meets harder negatives."""
         item_seq, lengths = interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN]
+        alias, _ = self._proposal()
         h, seq = self.forward_all(item_seq, lengths)
         pos_items = interaction[self.POS_ITEM_ID].to(torch.int64)
         target = next_item_targets(seq.ids, seq.offsets, seq.order, pos_items)
         if negatives is None:
             negatives = sample_negatives(item_seq.to(torch.int64), lengths.to(torch.int64),
                                          pos_items, max(self.dense_negatives, 1), 1, self.n_items,
-                                         draw_seed(), seq.offsets, seq.inv, seq.ntok)
+                                         draw_seed(), seq.offsets, seq.inv, seq.ntok, alias=alias)
         elif negatives.dim() != 2 or negatives.shape[0] < seq.ntok:
             raise ValueError(f"negatives must be [{seq.ntok} or more rows, n] in packed order, "
                              f"got {tuple(negatives.shape)}")
@@ -570,8 +631,17 @@ class RecBLR(SequentialRecommender):
         list is a valid list for each of its positions.  shift =
         log((n_items - 1) / n), the log-Q correction that makes sum_j
         exp(z_j) an estimate of the full softmax's sum over the other items
-        (sampled_softmax_correct: False gives shift = 0)."""
+        (sampled_softmax_correct: False gives shift = 0).
+        dense_sampling 'popularity': the candidates come from the popularity
+        proposal q (set_item_counts) and the correction is per item, z_j = h_t
+        . E[neg_j] - log(n q_j): shift = -log(n) plus item_shift = -log(q), the
+        uniform formula's generalisation (both dropped with
+        sampled_softmax_correct: False).  Rejecting against the row's window
+        renormalises the proposal per row by 1 / (1 - q(seen)); as on the
+        uniform path (which uses n_items - 1, not the unseen count) that factor
+        is ignored."""
         item_seq, lengths = interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN]
+        alias, item_shift = self._proposal()
         h, seq = self.forward_all(item_seq, lengths)
         pos_items = interaction[self.POS_ITEM_ID].to(torch.int64)
         # rows on the host (an encoder run elsewhere): the host restatements
@@ -580,14 +650,20 @@ class RecBLR(SequentialRecommender):
         target = targets(seq.ids, seq.offsets, seq.order, pos_items)
         if negatives is None:
             negatives = draw(item_seq.to(torch.int64), lengths.to(torch.int64), pos_items,
-                             max(self.dense_negatives, 1), 1, self.n_items, draw_seed())
+                             max(self.dense_negatives, 1), 1, self.n_items, draw_seed(),
+                             alias=alias)
         elif negatives.dim() != 2 or negatives.shape[0] != item_seq.shape[0]:
             raise ValueError(f"negatives must be [{item_seq.shape[0]}, n] in batch-row order, "
                              f"got {tuple(negatives.shape)}")
         n = negatives.shape[1]
-        shift = math.log((self.n_items - 1) / n) if self.sampled_softmax_correct else 0.0
+        if not self.sampled_softmax_correct:
+            shift, item_shift = 0.0, None
+        elif item_shift is not None:
+            shift = -math.log(n)
+        else:
+            shift = math.log((self.n_items - 1) / n)
         return shared_softmax_loss(h, self.item_embedding.weight, target, negatives, seq.offsets,
-                                   seq.order, shift, max_len=seq.L)
+                                   seq.order, shift, max_len=seq.L, item_shift=item_shift)
 
     def calculate_loss(self, interaction):
         if self.train_all_positions:

@@ -458,11 +458,13 @@ def pair_loss(h: torch.Tensor, table: torch.Tensor, pos: torch.Tensor, neg: torc
 
 def shared_softmax_reference(h: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
                              neg: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor,
-                             shift: float = 0.0) -> torch.Tensor:
+                             shift: float = 0.0, item_shift: torch.Tensor | None = None
+                             ) -> torch.Tensor:
     """shared_softmax_loss in torch ops, any device and dtype: the CPU path,
     the fallback for shapes the kernels refuse, and the tests' reference.  The
     sequences are padded to the longest one and scored against their own
-    lists with one batched product."""
+    lists with one batched product.  item_shift [V] is added after shift, as
+    the kernels add it, in the scores' dtype; it takes no gradient."""
     V, (B, n) = table.shape[0], neg.shape
     lens = offsets[1:] - offsets[:-1]
     rows = torch.arange(int(offsets[0]), int(offsets[-1]), device=h.device)
@@ -475,6 +477,8 @@ def shared_softmax_reference(h: torch.Tensor, table: torch.Tensor, target: torch
     lists = neg[order]                                       # [B, n], packed-sequence order
     col_ok = (lists >= 0) & (lists < V)
     z = torch.bmm(padded, table[lists.clamp(0, V - 1)].transpose(1, 2))[seq_of, t_in] + shift
+    if item_shift is not None:
+        z = z + item_shift.detach().to(z.dtype)[lists.clamp(0, V - 1)][seq_of]
     z = torch.where(col_ok[seq_of], z, torch.full_like(z, float("-inf")))
     row_ok = (tr >= 0) & (tr < V)
     z0 = (hr * table[tr.clamp(0, V - 1)]).sum(-1)
@@ -491,20 +495,20 @@ class _SharedSoftmax(torch.autograd.Function):
     targets and the plain apply of dneg over the lists."""
 
     @staticmethod
-    def forward(ctx, h, table, target, neg, offsets, order, shift, max_len):
+    def forward(ctx, h, table, target, neg, offsets, order, shift, max_len, item_shift=None):
         table = table.contiguous()
         if h.stride(1) != 1 or h.stride(0) % 4 or h.data_ptr() % 16:
             h = h.contiguous()
         target, neg = target.contiguous(), neg.contiguous()
         offsets, order = offsets.contiguous(), order.contiguous()
         loss, n_live, lse, _ = kernels.shared_softmax_fwd(h, table, target, neg, offsets, order,
-                                                          shift, max_len)
+                                                          shift, max_len, item_shift)
         ctx.plans = None
         if ctx.needs_input_grad[1]:
             V, d = table.shape
             ctx.plans = (kernels.embedding_plan(target, V, d),
                          kernels.embedding_plan(neg.reshape(-1), V, d))
-        ctx.shift, ctx.max_len = shift, max_len
+        ctx.shift, ctx.max_len, ctx.item_shift = shift, max_len, item_shift
         ctx.save_for_backward(h, table, target, neg, offsets, order, lse, n_live)
         ctx.mark_non_differentiable(n_live)
         return loss, n_live
@@ -515,7 +519,7 @@ class _SharedSoftmax(torch.autograd.Function):
         plans, ctx.plans = ctx.plans, None
         dh, coef, dneg = kernels.shared_softmax_bwd(h, table, target, neg, offsets, order, lse,
                                                     dloss.float().contiguous(), n_live,
-                                                    ctx.shift, ctx.max_len)
+                                                    ctx.shift, ctx.max_len, ctx.item_shift)
         dtable = None
         if plans is not None:
             V, d = table.shape
@@ -523,13 +527,13 @@ class _SharedSoftmax(torch.autograd.Function):
             dtable += kernels.embedding_bwd(neg.reshape(-1), dneg.reshape(-1, d), V,
                                             padding_idx=None, plan=plans[1])
         return ((dh if ctx.needs_input_grad[0] else None), dtable, None, None, None, None, None,
-                None)
+                None, None)
 
 
 def shared_softmax_loss(h: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
                         neg: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor,
                         shift: float = 0.0, return_live: bool = False, *,
-                        max_len: int | None = None):
+                        max_len: int | None = None, item_shift: torch.Tensor | None = None):
     """Sampled softmax of the packed rows h [M, d] against table [V, d] with
     the negatives shared by the rows of a sequence: neg [B, n] holds one list
     per batch row, and packed sequence s (rows offsets[s] .. offsets[s + 1])
@@ -551,7 +555,12 @@ def shared_softmax_loss(h: torch.Tensor, table: torch.Tensor, target: torch.Tens
     so the result is bitwise reproducible.  return_live: also the live-row
     count (a device scalar, no sync).  max_len: an upper estimate of the
     longest sequence (it sizes the launch; without it the lengths are read
-    back once).  CPU tensors, other dtypes, d no multiple of 16 up to 224 and
+    back once).  item_shift [V]: a per-item correction for a proposal that is
+    not uniform — a column of id j scores z_j = (h_r . table[j] + shift) +
+    item_shift[j]; with ids drawn with probability q_j (kernels.
+    negative_sampler), shift = -log(n) and item_shift = -log(q) generalise the
+    uniform formula.  It takes no gradient and is read only at the live
+    columns' ids.  CPU tensors, other dtypes, d no multiple of 16 up to 224 and
     n > 256 take shared_softmax_reference."""
     if (h.dim() != 2 or target.shape != (h.shape[0],) or neg.dim() != 2 or neg.shape[1] < 1
             or offsets.shape != (neg.shape[0] + 1,) or order.shape != (neg.shape[0],)):
@@ -560,16 +569,21 @@ def shared_softmax_loss(h: torch.Tensor, table: torch.Tensor, target: torch.Tens
                          f"{tuple(neg.shape)}, {tuple(offsets.shape)} and {tuple(order.shape)}")
     target, neg = target.to(torch.int64), neg.to(torch.int64)
     offsets, order = offsets.to(torch.int64), order.to(torch.int64)
+    if item_shift is not None and item_shift.shape != (table.shape[0],):
+        raise ValueError(f"item_shift must be [V] = [{table.shape[0]}], got "
+                         f"{tuple(item_shift.shape)}")
     if not kernels.shared_softmax_supported(h, table, neg.shape[1]):
-        loss = shared_softmax_reference(h, table, target, neg, offsets, order, shift)
+        loss = shared_softmax_reference(h, table, target, neg, offsets, order, shift, item_shift)
         if not return_live:
             return loss
         covered = target[int(offsets[0]):int(offsets[-1])]
         return loss, ((covered >= 0) & (covered < table.shape[0])).sum()
     if max_len is None:
         max_len = int((offsets[1:] - offsets[:-1]).max())
+    if item_shift is not None:
+        item_shift = item_shift.detach().to(device=h.device, dtype=torch.float32).contiguous()
     loss, n_live = _SharedSoftmax.apply(h, table, target, neg, offsets, order, float(shift),
-                                        int(max_len))
+                                        int(max_len), item_shift)
     return (loss, n_live) if return_live else loss
 
 

@@ -18,7 +18,7 @@ import time
 import torch
 import torch.distributed as dist
 
-from .data import SequentialLoader
+from .data import SequentialLoader, train_item_counts
 from .distributed import DistEnv, wrap_ddp
 from .scoring import rank_metrics
 
@@ -69,10 +69,15 @@ def fit(model, data, env: DistEnv, epochs: int = 100, batch_size: int = 2048,
     train_all_positions, takes the loss at every position of it (the CE, or
     with dense_negatives the sampled pairwise loss, or with dense_loss
     'sampled_softmax' the sampled softmax over negatives shared per row; the
-    loop is the same for all three).  A loss_type 'BPR' model
+    loop is the same for all three; a model with dense_sampling 'popularity'
+    and no proposal yet gets it from data.train_item_counts).  A loss_type 'BPR' model
     gets one sampled negative per row from the loader (NEG_ITEM_ID)."""
     if dense and not getattr(model, "train_all_positions", False):
         raise ValueError("fit(dense=True) needs a model built with train_all_positions=True")
+    # dense_sampling 'popularity': the proposal comes from the train split's counts
+    if (getattr(model, "dense_sampling", "uniform") == "popularity"
+            and getattr(model, "neg_alias", None) is None):
+        model.set_item_counts(train_item_counts(data))
     step = wrap_ddp(model, env)
     # RecBole's learner 'adam' (torch.optim.Adam semantics): one native launch,
     # or torch.optim.Adam (RECBLR_ADAM=torch, or parameters it cannot take)

@@ -46,6 +46,25 @@ int rb_sample_negatives(const int64_t* item_seq, int64_t seq_rs, const int64_t* 
                         int64_t B, int64_t L, int64_t n_neg, int64_t first_item, int64_t V,
                         uint64_t seed, int64_t ntok, int64_t m_pad, int64_t* neg, void* stream);
 
+/* rb_sample_negatives with a proposal other than the uniform one: alias [V -
+ * first_item] int64 (device, 8-B aligned) is an alias table over the bins i =
+ * id - first_item, one word per bin: the low 32 bits an unsigned threshold,
+ * the high 32 bits the bin's alias (an alias past the table is read as its
+ * last bin).  Everything else is rb_sample_negatives': the seen set, the 16
+ * attempts, the walk upward from the 16th candidate, -1, both layouts.  Only
+ * the candidate of attempt a differs, and an attempt takes two Philox words:
+ *   (u, v) = words (2 (a % 2), 2 (a % 2) + 1) of Philox4x32-10(counter = (b, t,
+ *   j, a / 2), key = seed);  i = mulhi(u, V - first_item);  the candidate is
+ *   first_item + (v < threshold[i] ? i : alias[i]).
+ * The table is only read (one 8-byte load per attempt).  kernels.
+ * negative_sampler builds it (Vose's method) together with the exact
+ * probability of every id under this rule. */
+int rb_sample_negatives_alias(const int64_t* item_seq, int64_t seq_rs, const int64_t* lengths,
+                              const int64_t* pos_items, const int64_t* offsets,
+                              const int64_t* inv, int64_t B, int64_t L, int64_t n_neg,
+                              int64_t first_item, int64_t V, uint64_t seed, int64_t ntok,
+                              int64_t m_pad, const int64_t* alias, int64_t* neg, void* stream);
+
 /* Bytes of rb_pair_loss_fwd's workspace for M rows (0 for M <= 0). */
 int64_t rb_pair_loss_workspace(int64_t M);
 
@@ -123,6 +142,32 @@ int rb_shared_softmax_bwd(const float* h, int64_t ldh, const float* table,
                           const int64_t* n_live, int64_t M, int64_t B, int64_t d, int64_t V,
                           int64_t n_neg, int64_t max_len, float shift, float* dh, float* coef,
                           float* dneg, void* stream);
+
+/* The same two with a per-item correction of the proposal: item_shift [V]
+ * (device fp32, finite at every id a list holds), and a live column of id j
+ * scores
+ *   z_j = (h_r . table[j] + shift) + item_shift[j]
+ * in that order; z0 is unshifted as above.  With negatives drawn with
+ * probability q_j each, shift = -log(n_neg) and item_shift[j] = -log(q_j) make
+ * sum_j exp(z_j) an estimate of the full softmax's sum.  A dead column or an id
+ * outside [0, V) reads nothing of item_shift.  Everything else, the sums'
+ * orders included, is rb_shared_softmax_fwd / _bwd's; item_shift has no
+ * gradient. */
+int rb_shared_softmax_fwd_items(const float* h, int64_t ldh, const float* table,
+                                const int64_t* target, const int64_t* neg,
+                                const int64_t* offsets, const int64_t* order, int64_t M,
+                                int64_t B, int64_t d, int64_t V, int64_t n_neg, int64_t max_len,
+                                float shift, const float* item_shift, float* lse, float* z0,
+                                float* loss, int64_t* n_live, void* workspace,
+                                int64_t workspace_bytes, void* stream);
+
+int rb_shared_softmax_bwd_items(const float* h, int64_t ldh, const float* table,
+                                const int64_t* target, const int64_t* neg,
+                                const int64_t* offsets, const int64_t* order, const float* lse,
+                                const float* dloss, const int64_t* n_live, int64_t M, int64_t B,
+                                int64_t d, int64_t V, int64_t n_neg, int64_t max_len, float shift,
+                                const float* item_shift, float* dh, float* coef, float* dneg,
+                                void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,9 +20,15 @@ windows are warm-up.  The two loss kernels are then timed by HIP events in a
 pass of their own and set against their byte floor at 8 TB/s: (2 + n) M d 4
 bytes for the forward, the same plus the dh write for the backward.
 
+--popularity adds the dense pairs steps with the negatives drawn from the
+popularity proposal (dense_pairs_pop_n{n}; counts: bench_sampled.zipf_counts)
+and the sampler alone at every position with and without the alias table
+(sample_uniform_n{n}, sample_pop_n{n}); "popularity" in the result holds each
+one's ratio to its uniform leg and the two samplers by HIP events.
+
     python tools/bench_pairs.py [--batch 2048] [--seq-len 200] [--hidden 128]
                                 [--items 10544] [--windows 9] [--steps 5]
-                                [--out result.json]
+                                [--popularity] [--out result.json]
 
 Prints one JSON line.  Needs the GPU; there is no CPU path.
 """
@@ -40,6 +46,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from bench_dense import window_ms  # noqa: E402
+from bench_sampled import zipf_counts  # noqa: E402
 from datamining_recblr_amd import kernels, scoring  # noqa: E402
 from datamining_recblr_amd.distributed import synthetic_interaction  # noqa: E402
 from datamining_recblr_amd.model import RecBLR  # noqa: E402
@@ -60,6 +67,8 @@ def main() -> None:
     ap.add_argument("--windows", type=int, default=9)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup-windows", type=int, default=2)
+    ap.add_argument("--popularity", action="store_true",
+                    help="add the popularity proposal's legs beside the uniform ones")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -81,15 +90,19 @@ def main() -> None:
             opt.step()
         return run
 
-    def pairs_loss(n):
+    def pairs_loss(n, sampling="uniform"):
         def loss(interaction):
-            model.dense_negatives = n
+            model.dense_negatives, model.dense_sampling = n, sampling
             return model.calculate_loss_pairs(interaction)
         return loss
 
     legs = {"ordinary": step(model.calculate_loss), "dense_ce": step(model.calculate_loss_dense)}
     for n in NEGATIVES:
         legs[f"dense_pairs_n{n}"] = step(pairs_loss(n))
+    if a.popularity:   # the same step with the negatives drawn from the popularity proposal
+        model.set_item_counts(zipf_counts(a.items))
+        for n in NEGATIVES:
+            legs[f"dense_pairs_pop_n{n}"] = step(pairs_loss(n, "popularity"))
 
     # ---- the loss alone on the dense step's rows (detached) -------------------------
     with torch.no_grad():
@@ -132,6 +145,17 @@ def main() -> None:
     for n in NEGATIVES:
         legs[f"loss_kernels_n{n}"] = loss_kernels(n)
         legs[f"loss_torch_n{n}"] = loss_torch(n)
+
+    def sample(n, alias):   # the sampler alone, every position of every row
+        def run():
+            kernels.sample_negatives(inter["item_id_list"], inter["item_length"], pos_items, n, 1,
+                                     a.items, 99, seq.offsets, seq.inv, ntok, alias=alias)
+        return run
+
+    if a.popularity:
+        for n in NEGATIVES:
+            legs[f"sample_uniform_n{n}"] = sample(n, None)
+            legs[f"sample_pop_n{n}"] = sample(n, model.neg_alias)
 
     # the two compositions compute the same thing (sampled negatives are never -1 here)
     check = {}
@@ -188,6 +212,27 @@ def main() -> None:
            "max_rel_diff_kernels_vs_torch_dh_dtable": check,
            "loss_kernels": floors,
            "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2**30, 2)}
+    if a.popularity:
+        def versus(pop, uniform):
+            gap = abs(med[pop] - med[uniform])
+            own = max(max(times[k]) - min(times[k]) for k in (pop, uniform))
+            return {"ratio": round(med[pop] / med[uniform], 3), "within_spread": gap <= own}
+
+        sampler_us = {}
+        for n in NEGATIVES:
+            with kernels.kernel_timing(only={"rb_sample_negatives",
+                                             "rb_sample_negatives_alias"}) as t:
+                for _ in range(20):
+                    sample(n, None)()
+                    sample(n, model.neg_alias)()
+            sampler_us[f"n{n}"] = {k: round(v["avg_ms"] * 1e3, 1) for k, v in t.summary().items()}
+        res["popularity"] = {
+            "counts": "zipf_counts(items): floor(1e5 / rank), alpha 0.75, smoothing 1",
+            "dense_step": {f"n{n}": versus(f"dense_pairs_pop_n{n}", f"dense_pairs_n{n}")
+                           for n in NEGATIVES},
+            "sampler": {f"n{n}": versus(f"sample_pop_n{n}", f"sample_uniform_n{n}")
+                        for n in NEGATIVES},
+            "sampler_us": sampler_us}
     line = json.dumps(res)
     print(line)
     if a.out:

@@ -20,9 +20,27 @@ Reported per leg: the median window, its min and max, and the repeat-to-repeat
 spread (max - min) / median; kernels_vs_torch says whether the kernels' slowest
 window still beats the composition's fastest one.
 
+--popularity adds, in the same alternation, the popularity proposal's legs at
+n in 16, 64, 256 (counts: zipf_counts, a Zipf-like synthetic distribution over
+the items):
+
+  * loss_kernels_pop_n{n}  the loss on lists drawn from the alias table, with
+                           the per-item correction (rb_shared_softmax_fwd_items
+                           / _bwd_items);
+  * loss_kernels_poplists_n{n}, loss_kernels_items_n{n}
+                           the two halves of that change alone: the popularity
+                           lists with the scalar shift, and the uniform lists
+                           with the per-item term;
+  * dense_sampled_pop_n{n} the dense step of a dense_sampling 'popularity' model;
+  * sample_uniform_n{n}, sample_pop_n{n}
+                           the sampler alone, one list per row;
+
+and "popularity" in the result: each leg's ratio to its uniform leg, whether the
+difference is inside the two legs' own spreads, and the samplers by HIP events.
+
     python tools/bench_sampled.py [--batch 2048] [--seq-len 200] [--hidden 128]
                                   [--items 10544] [--windows 7] [--steps 3]
-                                  [--out result.json]
+                                  [--popularity] [--out result.json]
 
 Prints one JSON line.  Needs the GPU; there is no CPU path.
 """
@@ -49,6 +67,19 @@ from datamining_recblr_amd.recbole_compat import SyntheticDataset  # noqa: E402
 
 NEGATIVES = (16, 64, 128, 256)
 PAIRS_N = 16
+POPULARITY_NEGATIVES = (16, 64, 256)
+
+
+def zipf_counts(n_items: int, seed: int = 0, top: float = 1e5):
+    """Zipf-like synthetic train counts [n_items]: the item of popularity rank
+    r = 1, 2 ... has floor(top / r) occurrences, the ranks dealt to the ids 1 ..
+    n_items - 1 by a seeded permutation (id 0, the padding id, has none)."""
+    import numpy as np
+
+    counts = np.zeros(n_items, dtype=np.int64)
+    ranks = np.random.default_rng(seed).permutation(n_items - 1) + 1
+    counts[1:] = np.floor(top / ranks).astype(np.int64)
+    return counts
 
 
 def main() -> None:
@@ -61,6 +92,8 @@ def main() -> None:
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup-windows", type=int, default=2)
+    ap.add_argument("--popularity", action="store_true",
+                    help="add the popularity proposal's legs beside the uniform ones")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -82,9 +115,9 @@ def main() -> None:
             opt.step()
         return run
 
-    def with_n(method, n):
+    def with_n(method, n, sampling="uniform"):
         def loss(interaction):
-            model.dense_negatives = n
+            model.dense_negatives, model.dense_sampling = n, sampling
             return method(interaction)
         return loss
 
@@ -92,6 +125,11 @@ def main() -> None:
             f"dense_pairs_n{PAIRS_N}": step(with_n(model.calculate_loss_pairs, PAIRS_N))}
     for n in NEGATIVES:
         legs[f"dense_sampled_n{n}"] = step(with_n(model.calculate_loss_sampled, n))
+    if a.popularity:
+        model.set_item_counts(zipf_counts(a.items))
+        for n in POPULARITY_NEGATIVES:
+            legs[f"dense_sampled_pop_n{n}"] = step(with_n(model.calculate_loss_sampled, n,
+                                                          "popularity"))
 
     # ---- the loss alone on the dense step's rows (detached) -------------------------
     with torch.no_grad():
@@ -142,6 +180,35 @@ def main() -> None:
         legs[f"loss_kernels_n{n}"] = loss_kernels(n)
         legs[f"loss_torch_n{n}"] = loss_torch(n)
 
+    # ---- the popularity proposal: its lists, the per-item correction, the sampler ------
+    if a.popularity:
+        alias, item_shift = model.neg_alias, model.neg_item_shift
+        pop_lists = {n: kernels.sample_negatives(item_seq, lengths, pos_items, n, 1, a.items,
+                                                 1234 + n, alias=alias)
+                     for n in POPULARITY_NEGATIVES}
+
+        def loss_kernels_pop(n, lists_=pop_lists, shift_=item_shift):
+            def run():
+                rows.grad = table.grad = None
+                scoring.shared_softmax_loss(rows, table, target, lists_[n], seq.offsets,
+                                            seq.order, -math.log(n), max_len=a.seq_len,
+                                            item_shift=shift_).backward()
+            return run
+
+        def sample(n, table_):
+            def run():
+                kernels.sample_negatives(item_seq, lengths, pos_items, n, 1, a.items, 77,
+                                         alias=table_)
+            return run
+
+        for n in POPULARITY_NEGATIVES:
+            legs[f"loss_kernels_pop_n{n}"] = loss_kernels_pop(n)
+            # the two halves of the difference: the lists alone (scalar shift), the term alone
+            legs[f"loss_kernels_poplists_n{n}"] = loss_kernels_pop(n, pop_lists, None)
+            legs[f"loss_kernels_items_n{n}"] = loss_kernels_pop(n, lists, item_shift)
+            legs[f"sample_uniform_n{n}"] = sample(n, None)
+            legs[f"sample_pop_n{n}"] = sample(n, alias)
+
     # the two compositions compute the same thing
     check = {}
     for n in NEGATIVES:
@@ -189,6 +256,53 @@ def main() -> None:
            "max_rel_diff_kernels_vs_torch_dh_dtable": check,
            "launch_us": launches,
            "peak_mem_gib": round(torch.cuda.max_memory_allocated(dev) / 2**30, 2)}
+    if a.popularity:
+        def versus(pop, uniform):
+            """The popularity leg against the uniform one: the medians' ratio
+            and whether the difference is inside the legs' own spreads."""
+            gap = abs(med[pop] - med[uniform])
+            own = max(max(times[k]) - min(times[k]) for k in (pop, uniform))
+            return {"ratio": round(med[pop] / med[uniform], 3), "within_spread": gap <= own}
+
+        pop_names = {"rb_shared_softmax_fwd_items", "rb_shared_softmax_bwd_items",
+                     "rb_embedding_bwd_scaled", "rb_embedding_bwd", "rb_sample_negatives",
+                     "rb_sample_negatives_alias"}
+        pop_launches = {}
+        for n in POPULARITY_NEGATIVES:
+            with kernels.kernel_timing(only=pop_names) as t:
+                for _ in range(10):
+                    loss_kernels_pop(n)()
+                    sample(n, None)()
+                    sample(n, alias)()
+            pop_launches[f"n{n}"] = {k: round(v["avg_ms"] * 1e3, 1)
+                                     for k, v in t.summary().items()}
+            for key, fn in (("popularity_lists_scalar_shift", loss_kernels_pop(n, pop_lists, None)),
+                            ("uniform_lists_item_shift", loss_kernels_pop(n, lists, item_shift))):
+                with kernels.kernel_timing(only=names | pop_names) as t:
+                    for _ in range(10):
+                        fn()
+                pop_launches[f"n{n}_{key}"] = {k: round(v["avg_ms"] * 1e3, 1)
+                                               for k, v in t.summary().items()}
+        uniq = {f"n{n}": [int(torch.unique(lists[n]).numel()), int(torch.unique(pop_lists[n]).numel())]
+                for n in POPULARITY_NEGATIVES}
+        res["popularity"] = {
+            "counts": "zipf_counts(items): floor(1e5 / rank), alpha 0.75, smoothing 1",
+            "item_shift_min_max": [round(float(item_shift[1:].min()), 3),
+                                   round(float(item_shift[1:].max()), 3)],
+            "loss": {f"n{n}": versus(f"loss_kernels_pop_n{n}", f"loss_kernels_n{n}")
+                     for n in POPULARITY_NEGATIVES},
+            "loss_popularity_lists_scalar_shift": {
+                f"n{n}": versus(f"loss_kernels_poplists_n{n}", f"loss_kernels_n{n}")
+                for n in POPULARITY_NEGATIVES},
+            "loss_uniform_lists_item_shift": {
+                f"n{n}": versus(f"loss_kernels_items_n{n}", f"loss_kernels_n{n}")
+                for n in POPULARITY_NEGATIVES},
+            "dense_step": {f"n{n}": versus(f"dense_sampled_pop_n{n}", f"dense_sampled_n{n}")
+                           for n in POPULARITY_NEGATIVES},
+            "sampler": {f"n{n}": versus(f"sample_pop_n{n}", f"sample_uniform_n{n}")
+                        for n in POPULARITY_NEGATIVES},
+            "distinct_ids_uniform_vs_popularity": uniq,
+            "launch_us": pop_launches}
     line = json.dumps(res)
     print(line)
     if a.out:
