@@ -9,56 +9,30 @@
 //   rb_candidate_ranks    per row, the listed entries scoring above / equal to
 //                         the row's target (integer counts).
 //
-// One scoring core serves the three: a 16-lane group per (row, id), 16-B
-// loads, the dot product reduced inside the group — pair_loss.hip's
-// arithmetic.  A pair's score is a pure function of h_b's and table[id]'s d
+// One scoring core serves the three and the pairwise loss (row_group.h): a
+// 16-lane group per (row, id), 16-B loads, the dot product reduced inside the
+// group.  A pair's score is a pure function of h_b's and table[id]'s d
 // floats: its bits do not depend on the id's place in the list, on B or C,
 // or on the entry point, so two equal table rows tie exactly and the top-k's
 // and the ranks' comparisons are the plain scores'.  No float atomics.
 #include "common.h"
+#include "row_group.h"
 
 namespace rb {
 namespace {
 
-constexpr int kGroup = 16;            // lanes per (row, id) pair
-constexpr int kGroups = 256 / kGroup;
 constexpr int kRankChunk = 1024;      // candidates per workgroup of the ranks kernel
 constexpr unsigned long long kDropped = ~0ull;   // sorts behind every selectable key
 
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = kGroup / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kGroup);
-  return v;
-}
-
-__device__ __forceinline__ int group_or(int v) {
-#pragma unroll
-  for (int o = kGroup / 2; o > 0; o >>= 1) v |= __shfl_xor(v, o, kGroup);
-  return v;
-}
-
-template <int NV4>
-__device__ __forceinline__ void load_row(float4 (&o)[NV4], const float* p, int l, int d) {
-#pragma unroll
-  for (int k = 0; k < NV4; ++k) {
-    const int col = 4 * (l + kGroup * k);
-    o[k] = col < d ? *reinterpret_cast<const float4*>(p + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-
-// The score of (h row, table row): the only place a score is computed.  The
-// caller passes an id inside [0, V) (clamped) and masks the result, so every
-// lane of the wave takes part in the shuffles and nothing out of range is read.
+// The score of (h row, table row id).  The caller passes an id inside [0, V)
+// (clamped) and masks the result, so every lane of the wave takes part in the
+// shuffles and nothing out of range is read.
 template <int NV4>
 __device__ __forceinline__ float score(const float4 (&hv)[NV4], const float* tab, int64_t id,
                                        int l, int d) {
   float4 e[NV4];
   load_row<NV4>(e, tab + id * d, l, d);
-  float s = 0.0f;
-#pragma unroll
-  for (int k = 0; k < NV4; ++k)
-    s += (hv[k].x * e[k].x + hv[k].y * e[k].y) + (hv[k].z * e[k].z + hv[k].w * e[k].w);
-  return group_sum(s);
+  return dot_rows<NV4>(hv, e);
 }
 
 // ---- scores -----------------------------------------------------------------------
@@ -234,9 +208,6 @@ k_cand_ranks(const float* __restrict__ h, int64_t ldh, const float* __restrict__
   }
 }
 
-// float4 loads per lane of a 16-lane group: d <= 64 * NV4
-int row_vecs(int64_t d) { return d <= 64 ? 1 : d <= 128 ? 2 : d <= 256 ? 4 : 8; }
-
 int pow2_at_least(int64_t n) {
   int p = 1;
   while (p < n) p <<= 1;
@@ -252,7 +223,7 @@ int launch_candidate_scores(const float* h, int64_t ldh, const float* tab, const
   // few pairs: one per group, so that a single row's list still spreads over the device
   const int per = n <= (int64_t)num_cus() * 4 * kGroups ? 1 : 4;
   const int64_t nb = (n + (int64_t)per * kGroups - 1) / ((int64_t)per * kGroups);
-  dispatch_int<1, 2, 4, 8>(row_vecs(d), [&](auto nv) {
+  dispatch_row_vecs(d, [&](auto nv) {
     hipLaunchKernelGGL((k_cand_scores<decltype(nv)::value>), dim3((unsigned)nb), dim3(256), 0, st,
                        h, ldh, tab, cand, n, C, (int)d, V, per, scores);
   });
@@ -265,7 +236,7 @@ int launch_candidate_topk(const float* h, int64_t ldh, const float* tab, const i
                           hipStream_t st) {
   const int P = pow2_at_least(C);
   const size_t lds = (size_t)P * 8 + (size_t)E * 4;   // <= 32 KB + 16 KB
-  dispatch_int<1, 2, 4, 8>(row_vecs(d), [&](auto nv) {
+  dispatch_row_vecs(d, [&](auto nv) {
     hipLaunchKernelGGL((k_cand_topk<decltype(nv)::value>), dim3((unsigned)B), dim3(256), lds, st,
                        h, ldh, tab, cand, (int)C, P, (int)d, V, first, k, exclude, (int)E, ids,
                        scores);
@@ -280,7 +251,7 @@ int launch_candidate_ranks(const float* h, int64_t ldh, const float* tab, const 
   if (hipMemsetAsync(n_gt, 0, (size_t)B * 8, st) != hipSuccess ||
       hipMemsetAsync(n_eq, 0, (size_t)B * 8, st) != hipSuccess)
     return launch_status("rb_candidate_ranks");
-  dispatch_int<1, 2, 4, 8>(row_vecs(d), [&](auto nv) {
+  dispatch_row_vecs(d, [&](auto nv) {
     hipLaunchKernelGGL((k_cand_ranks<decltype(nv)::value>), dim3((unsigned)(B * chunks)),
                        dim3(256), 0, st, h, ldh, tab, target, cand, C, (int)chunks, (int)d, V,
                        first, reinterpret_cast<unsigned long long*>(n_gt),

@@ -1202,6 +1202,16 @@ __global__ __launch_bounds__(256) void k_ce_probs_h(const _Float16* __restrict__
 // ---- host side ---------------------------------------------------------------------
 size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 
+// the regions of a workspace, back to back from 256-B boundaries
+struct WsCursor {
+  size_t off = 0;
+  size_t take(size_t bytes) {
+    const size_t r = off;
+    off = al256(off + bytes);
+    return r;
+  }
+};
+
 struct Grid2 {
   int64_t blocks, splits, per;  // blocks over the fixed axis, splits of the streamed axis
   unsigned wgs() const { return (unsigned)(blocks * ((splits + 7) / 8 * 8)); }  // see place()
@@ -1225,16 +1235,15 @@ struct CeWs {
 CeWs ce_layout(int64_t B, int64_t V, int64_t D) {
   const Grid2 f = plan(B, ntiles(V)), w = plan(V, ntiles(B));
   CeWs o{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t r = off; off = al256(off + bytes); return r; };
-  o.ts = take(B * 4);
-  o.m = take(f.splits * B * 4);
-  o.s = take(f.splits * B * 4);
-  o.rows = take(B * 4);
-  o.ticket = take(4);
-  o.de = take(f.splits * B * D * 4);
-  o.dw = take(w.splits * V * D * 4);
-  o.total = off;
+  WsCursor c;
+  o.ts = c.take(B * 4);
+  o.m = c.take(f.splits * B * 4);
+  o.s = c.take(f.splits * B * 4);
+  o.rows = c.take(B * 4);
+  o.ticket = c.take(4);
+  o.de = c.take(f.splits * B * D * 4);
+  o.dw = c.take(w.splits * V * D * 4);
+  o.total = c.off;
   return o;
 }
 
@@ -1245,12 +1254,11 @@ struct RankWs {
 RankWs rank_layout(int64_t B, int64_t V) {
   const Grid2 f = plan(B, ntiles(V));
   RankWs o{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t r = off; off = al256(off + bytes); return r; };
-  o.ts = take(B * 4);
-  o.gt = take(f.splits * B * 4);
-  o.eq = take(f.splits * B * 4);
-  o.total = off;
+  WsCursor c;
+  o.ts = c.take(B * 4);
+  o.gt = c.take(f.splits * B * 4);
+  o.eq = c.take(f.splits * B * 4);
+  o.total = c.off;
   return o;
 }
 
@@ -1261,94 +1269,19 @@ struct TopkWs {
 TopkWs topk_layout(int64_t B, int64_t V, int64_t k) {
   const Grid2 f = plan(B, ntiles(V));
   TopkWs o{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t r = off; off = al256(off + bytes); return r; };
-  o.sc = take(f.splits * B * k * 4);
-  o.id = take(f.splits * B * k * 4);
-  o.total = off;
+  WsCursor c;
+  o.sc = c.take(f.splits * B * k * 4);
+  o.id = c.take(f.splits * B * k * 4);
+  o.total = c.off;
   return o;
 }
 
-#define RB_ITEM_DISPATCH(D, FN, ...)              \
-  switch (D) {                                    \
-    case 16: FN<16>(__VA_ARGS__); break;          \
-    case 32: FN<32>(__VA_ARGS__); break;          \
-    case 64: FN<64>(__VA_ARGS__); break;          \
-    case 128: FN<128>(__VA_ARGS__); break;        \
-    case 256: FN<256>(__VA_ARGS__); break;        \
-    default: return fail("item scores: d must be 16, 32, 64, 128 or 256"); \
-  }
-
-template <int D>
-void target_dot_t(const float* E, const float* W, const int64_t* tgt, int64_t B, int64_t V,
-                  float* ts, hipStream_t st) {
-  hipLaunchKernelGGL(k_target_dot<D>, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, E, W,
-                     tgt, B, V, ts);
-}
-
-template <int D>
-void ce_fwd_t(const float* E, const float* W, const int64_t* tgt, int64_t B, int64_t V,
-              const Grid2& g, float* m, float* s, float* ts, unsigned* ticket, hipStream_t st) {
-  hipLaunchKernelGGL(k_ce_fwd<D>, dim3(g.wgs()), dim3(256), 0, st,
-                     E, W, tgt, B, V, g.per, g.blocks, g.splits, m, s, ts, ticket);
-}
-
-template <int D>
-void ce_bwd_seq_t(const float* E, const float* W, const float* lse, const int64_t* tgt,
-                  const float* dloss, float inv_n, int64_t B, int64_t V, const Grid2& g,
-                  float* part, hipStream_t st) {
-  hipLaunchKernelGGL(k_ce_bwd_seq<D>, dim3(g.wgs()), dim3(256), 0,
-                     st, E, W, lse, tgt, dloss, inv_n, B, V, g.per, g.blocks, g.splits, part);
-}
-
-template <int D>
-void ce_bwd_item_t(const float* E, const float* W, const float* lse, const int64_t* tgt,
-                   const float* dloss, float inv_n, int64_t B, int64_t V, const Grid2& g,
-                   float* part, hipStream_t st) {
-  hipLaunchKernelGGL(k_ce_bwd_item<D>, dim3(g.wgs()), dim3(256), 0,
-                     st, E, W, lse, tgt, dloss, inv_n, B, V, g.per, g.blocks, g.splits, part);
-}
-
-template <int D>
-void rank_t(const float* E, const float* W, const float* ts, const int64_t* tgt, int64_t B,
-            int64_t V, int64_t first, const Grid2& g, int* gt, int* eq, hipStream_t st) {
-  hipLaunchKernelGGL(k_item_rank<D>, dim3(g.wgs()), dim3(256), 0,
-                     st, E, W, ts, tgt, B, V, first, g.per, g.blocks, g.splits, gt, eq);
-}
-
-template <int D>
-void topk_t(const float* E, const float* W, int64_t B, int64_t V, int64_t first, int k,
-            const int64_t* ex, int64_t NE, const Grid2& g, float* sc, int* id, hipStream_t st) {
-  if (k <= 32)
-    hipLaunchKernelGGL((k_item_topk<D, 32>), dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, k,
-                       ex, NE, g.per, g.blocks, g.splits, sc, id);
-  else
-    hipLaunchKernelGGL((k_item_topk<D, 64>), dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, k,
-                       ex, NE, g.per, g.blocks, g.splits, sc, id);
-}
-
-template <int D>
-void scores_t(const float* E, const float* W, int64_t B, int64_t V, const Grid2& g, float* out,
-              hipStream_t st) {
-  hipLaunchKernelGGL((k_item_scores<D, false>), dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, g.per,
-                     g.blocks, g.splits, out, V, nullptr, nullptr, nullptr, 0.0f, (int64_t)0);
-}
-
-template <int D>
-void probs_t(const float* E, const float* W, int64_t B, int64_t V, const Grid2& g, float* out,
-             int64_t ld, const float* lse, const int64_t* tgt, const float* dloss, float inv_n,
-             int64_t v_off, hipStream_t st) {
-  hipLaunchKernelGGL((k_item_scores<D, true>), dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, g.per,
-                     g.blocks, g.splits, out, ld, lse, tgt, dloss, inv_n, v_off);
-}
-
-template <int D>
-void ce_fwd_h_t(const void* Ei, const int* Ee, const void* Wi, const int* We, const int64_t* tgt,
-                int64_t B, int64_t V, const Grid2& g, float* m, float* s, float* ts,
-                unsigned* ticket, hipStream_t st) {
-  hipLaunchKernelGGL(k_ce_fwd_h<D>, dim3(g.wgs()), dim3(256), 0, st, (const _Float16*)Ei, Ee,
-                     (const _Float16*)Wi, We, tgt, B, V, g.per, g.blocks, g.splits, m, s, ts,
-                     ticket);
+// f(std::integral_constant<int, D>{}) for the kernels' feature depths; any
+// other d is an error
+template <class F>
+int for_item_dim(int64_t D, F&& f) {
+  if (dispatch_int<16, 32, 64, 128, 256>((int)D, f)) return 0;
+  return fail("item scores: d must be 16, 32, 64, 128 or 256");
 }
 
 // The one launch of k_ce_probs_h.  The kernel's first output is P^T whenever it
@@ -1420,8 +1353,10 @@ int launch_item_ce_fwd(const float* E, const float* W, const int64_t* tgt, int64
   return ce_fwd_passes<false>(
       "rb_item_ce_fwd", tgt, B, V, D, lse, loss, ws, ws_bytes, 0.0f, 0, st,
       [&](const Grid2& g, float* m, float* s, float* ts, unsigned* ticket) {
-        RB_ITEM_DISPATCH(D, ce_fwd_t, E, W, tgt, B, V, g, m, s, ts, ticket, st);
-        return 0;
+        return for_item_dim(D, [&](auto dc) {
+          hipLaunchKernelGGL(k_ce_fwd<dc>, dim3(g.wgs()), dim3(256), 0, st, E, W, tgt, B, V, g.per,
+                             g.blocks, g.splits, m, s, ts, ticket);
+        });
       });
 }
 
@@ -1435,13 +1370,21 @@ int launch_item_ce_bwd(const float* E, const float* W, const int64_t* tgt, const
   if (dE) {
     float* part = reinterpret_cast<float*>(w + L.de);
     const Grid2 g = plan(B, ntiles(V));
-    RB_ITEM_DISPATCH(D, ce_bwd_seq_t, E, W, lse, tgt, dloss, inv_n, B, V, g, part, st);
+    if (int rc = for_item_dim(D, [&](auto dc) {
+          hipLaunchKernelGGL(k_ce_bwd_seq<dc>, dim3(g.wgs()), dim3(256), 0, st, E, W, lse, tgt,
+                             dloss, inv_n, B, V, g.per, g.blocks, g.splits, part);
+        }))
+      return rc;
     sum_parts(part, g.splits, B * D, dE, st);
   }
   if (dW) {
     float* part = reinterpret_cast<float*>(w + L.dw);
     const Grid2 g = plan(V, ntiles(B));
-    RB_ITEM_DISPATCH(D, ce_bwd_item_t, E, W, lse, tgt, dloss, inv_n, B, V, g, part, st);
+    if (int rc = for_item_dim(D, [&](auto dc) {
+          hipLaunchKernelGGL(k_ce_bwd_item<dc>, dim3(g.wgs()), dim3(256), 0, st, E, W, lse, tgt,
+                             dloss, inv_n, B, V, g.per, g.blocks, g.splits, part);
+        }))
+      return rc;
     sum_parts(part, g.splits, V * D, dW, st);
   }
   return launch_status("rb_item_ce_bwd");
@@ -1457,8 +1400,13 @@ int launch_item_rank(const float* E, const float* W, const int64_t* tgt, int64_t
   int* gt = reinterpret_cast<int*>(w + L.gt);
   int* eq = reinterpret_cast<int*>(w + L.eq);
   const Grid2 g = plan(B, ntiles(V));
-  RB_ITEM_DISPATCH(D, target_dot_t, E, W, tgt, B, V, ts, st);
-  RB_ITEM_DISPATCH(D, rank_t, E, W, ts, tgt, B, V, first, g, gt, eq, st);
+  if (int rc = for_item_dim(D, [&](auto dc) {
+        hipLaunchKernelGGL(k_target_dot<dc>, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, E,
+                           W, tgt, B, V, ts);
+        hipLaunchKernelGGL(k_item_rank<dc>, dim3(g.wgs()), dim3(256), 0, st, E, W, ts, tgt, B, V,
+                           first, g.per, g.blocks, g.splits, gt, eq);
+      }))
+    return rc;
   hipLaunchKernelGGL(k_rank_rows, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, gt, eq,
                      g.splits, ts, B, n_gt, n_eq);
   return launch_status("rb_item_rank");
@@ -1477,7 +1425,13 @@ int launch_item_topk(const float* E, const float* W, int64_t B, int64_t V, int64
   float* sc = reinterpret_cast<float*>(w + L.sc);
   int* id = reinterpret_cast<int*>(w + L.id);
   const Grid2 g = plan(B, ntiles(V));
-  RB_ITEM_DISPATCH(D, topk_t, E, W, B, V, first, (int)k, ex, NE, g, sc, id, st);
+  if (int rc = for_item_dim(D, [&](auto dc) {
+        // the candidate list's LDS capacity per (row, split)
+        const auto kernel = k <= 32 ? k_item_topk<dc, 32> : k_item_topk<dc, 64>;
+        hipLaunchKernelGGL(kernel, dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, (int)k, ex,
+                           NE, g.per, g.blocks, g.splits, sc, id);
+      }))
+    return rc;
   hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, sc, id,
                      g.splits, B, (int)k, ids, scores);
   return launch_status("rb_item_topk");
@@ -1488,7 +1442,11 @@ int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, con
                          float* out, int64_t ld, hipStream_t st) {
   const Grid2 g = plan(B, ntiles(V));
   const float inv_n = 1.0f / (float)B;
-  RB_ITEM_DISPATCH(D, probs_t, E, W, B, V, g, out, ld, lse, tgt, dloss, inv_n, v_off, st);
+  if (int rc = for_item_dim(D, [&](auto dc) {
+        hipLaunchKernelGGL((k_item_scores<dc, true>), dim3(g.wgs()), dim3(256), 0, st, E, W, B, V,
+                           g.per, g.blocks, g.splits, out, ld, lse, tgt, dloss, inv_n, v_off);
+      }))
+    return rc;
   return launch_status("rb_item_ce_probs");
 }
 
@@ -1511,8 +1469,11 @@ int launch_item_ce_fwd_h(const void* Ei, const int* Ee, const void* Wi, const in
                          float* loss, void* ws, int64_t ws_bytes, bool rows_mode, float inv_n,
                          int accumulate, hipStream_t st) {
   const auto partials = [&](const Grid2& g, float* m, float* s, float* ts, unsigned* ticket) {
-    RB_ITEM_DISPATCH(D, ce_fwd_h_t, Ei, Ee, Wi, We, tgt, B, V, g, m, s, ts, ticket, st);
-    return 0;
+    return for_item_dim(D, [&](auto dc) {
+      hipLaunchKernelGGL(k_ce_fwd_h<dc>, dim3(g.wgs()), dim3(256), 0, st, (const _Float16*)Ei, Ee,
+                         (const _Float16*)Wi, We, tgt, B, V, g.per, g.blocks, g.splits, m, s, ts,
+                         ticket);
+    });
   };
   if (rows_mode)
     return ce_fwd_passes<true>("rb_item_ce_fwd_h_rows", tgt, B, V, D, lse, loss, ws, ws_bytes,
@@ -1533,15 +1494,22 @@ int launch_item_ce_probs_h(const void* Ei, const int* Ee, const void* Wi, const 
   const Grid2 g = plan(B, ntiles(V));
   // the rows forms take the caller's normaliser, the others the batch mean
   const float inv_n = o.rows ? o.inv_n : 1.0f / (float)B;
-  RB_ITEM_DISPATCH(D, probs_h_t, mode, o.rows, Ei, Ee, Wi, We, B, V, g, o, lse, tgt, dloss, inv_n,
-                   v_off, st);
+  if (int rc = for_item_dim(D, [&](auto dc) {
+        probs_h_t<dc>(mode, o.rows, Ei, Ee, Wi, We, B, V, g, o, lse, tgt, dloss, inv_n, v_off, st);
+      }))
+    return rc;
   return launch_status(kNames[o.rows][mode]);
 }
 
 int launch_item_scores(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
                        float* out, hipStream_t st) {
   const Grid2 g = plan(B, ntiles(V));
-  RB_ITEM_DISPATCH(D, scores_t, E, W, B, V, g, out, st);
+  if (int rc = for_item_dim(D, [&](auto dc) {
+        hipLaunchKernelGGL((k_item_scores<dc, false>), dim3(g.wgs()), dim3(256), 0, st, E, W, B, V,
+                           g.per, g.blocks, g.splits, out, V, nullptr, nullptr, nullptr, 0.0f,
+                           (int64_t)0);
+      }))
+    return rc;
   return launch_status("rb_item_scores");
 }
 

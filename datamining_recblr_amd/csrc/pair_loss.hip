@@ -15,22 +15,21 @@
 //                         bits), the candidate is first + (v < threshold ? i :
 //                         alias).  One 8-byte read-only load per attempt;
 //   rb_pair_loss_fwd      x = h.E[pos] - h.E[neg], l = -log(gamma + sigmoid(x)),
-//                         a 16-lane group per row (16-B loads, the dot
-//                         products reduced inside the group), the mean over
-//                         the live pairs from per-workgroup partials that the
-//                         last workgroup to arrive adds in workgroup order;
+//                         a 16-lane group per row (row_group.h: the scoring
+//                         core the candidate kernels share), the mean over
+//                         the live pairs by loss_tail.h;
 //   rb_pair_loss_bwd      dh and the per-(row, id column) coefficients the
 //                         table's gradient is applied with
 //                         (rb_embedding_bwd_apply_scaled, embedding.hip).
 // No float atomics: every sum has a fixed order.
 #include "common.h"
+#include "loss_tail.h"
+#include "row_group.h"
 
 namespace rb {
 namespace {
 
 constexpr int kAttempts = 16;        // rejection attempts before the walk
-constexpr int kGroup = 16;           // lanes per row in the loss kernels
-constexpr int kGroups = 256 / kGroup;
 constexpr int kRowsPerGroup = 4;
 constexpr int kRowsPerWg = kGroups * kRowsPerGroup;   // 64
 constexpr float kLn2 = 0.6931471805599453f;
@@ -147,30 +146,6 @@ k_sample_negatives(const int64_t* __restrict__ item_seq, int64_t seq_rs,
 }
 
 // ---- the loss ---------------------------------------------------------------------
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int o = kGroup / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kGroup);
-  return v;
-}
-
-template <int NV4>
-__device__ __forceinline__ void load_row(float4 (&o)[NV4], const float* p, int l, int d) {
-#pragma unroll
-  for (int k = 0; k < NV4; ++k) {
-    const int col = 4 * (l + kGroup * k);
-    o[k] = col < d ? *reinterpret_cast<const float4*>(p + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-
-template <int NV4>
-__device__ __forceinline__ float dot_rows(const float4 (&a)[NV4], const float4 (&b)[NV4]) {
-  float s = 0.0f;
-#pragma unroll
-  for (int k = 0; k < NV4; ++k)
-    s += (a[k].x * b[k].x + a[k].y * b[k].y) + (a[k].z * b[k].z + a[k].w * b[k].w);
-  return group_sum(s);
-}
-
 // sigmoid(x) and 1 - sigmoid(x) without cancellation (x >= 0: e = exp(-x) <=
 // 1 and 1 - s = e s; x < 0: s <= 1/2).  exp(-x) = inf gives s = 0 exactly.
 __device__ __forceinline__ void sigm2(float x, float& s, float& oms) {
@@ -188,11 +163,6 @@ k_pair_fwd(const float* __restrict__ h, int64_t ldh, const float* __restrict__ t
            const int64_t* __restrict__ pos, const int64_t* __restrict__ neg, int64_t M, int d,
            int64_t V, int n_neg, float gamma, float* __restrict__ diff, float* psum, int* pcnt,
            unsigned* ticket, float* __restrict__ loss, int64_t* __restrict__ n_live) {
-  __shared__ float s_sum[kGroups];
-  __shared__ int s_cnt[kGroups];
-  __shared__ float red[256];
-  __shared__ long long redc[256];
-  __shared__ bool last;
   const int g = threadIdx.x / kGroup, l = threadIdx.x % kGroup;
   float sum = 0.0f;
   int cnt = 0;
@@ -223,48 +193,7 @@ k_pair_fwd(const float* __restrict__ h, int64_t ldh, const float* __restrict__ t
       if (in && l == 0) diff[r * n_neg + j] = live ? x : 0.0f;
     }
   }
-  if (l == 0) {
-    s_sum[g] = sum;
-    s_cnt[g] = cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float a = 0.0f;
-    int c = 0;
-    for (int k = 0; k < kGroups; ++k) {
-      a += s_sum[k];
-      c += s_cnt[k];
-    }
-    psum[blockIdx.x] = a;
-    pcnt[blockIdx.x] = c;
-    __threadfence();
-    last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
-  float a = 0.0f;
-  long long c = 0;
-  for (unsigned k = threadIdx.x; k < gridDim.x; k += 256) {
-    a += psum[k];
-    c += pcnt[k];
-  }
-  red[threadIdx.x] = a;
-  redc[threadIdx.x] = c;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      red[threadIdx.x] += red[threadIdx.x + w];
-      redc[threadIdx.x] += redc[threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const long long n = redc[0];
-    loss[0] = red[0] / (float)(n > 0 ? n : 1);
-    n_live[0] = n;
-    *ticket = 0u;
-  }
+  mean_loss_tail<kGroups>(sum, cnt, psum, pcnt, ticket, loss, n_live);
 }
 
 template <int NV4>
@@ -320,16 +249,11 @@ k_pair_bwd(const float* __restrict__ tab, const int64_t* __restrict__ pos,
   }
 }
 
-size_t pair_partials_off() { return 16; }   // the ticket's own 16-B block first
 int64_t pair_blocks(int64_t M) { return (M + kRowsPerWg - 1) / kRowsPerWg; }
-// float4 loads per lane of a 16-lane group: d <= 64 * NV4
-int row_vecs(int64_t d) { return d <= 64 ? 1 : d <= 128 ? 2 : d <= 256 ? 4 : 8; }
 
 }  // namespace
 
-int64_t pair_loss_workspace_bytes(int64_t M) {
-  return (int64_t)pair_partials_off() + pair_blocks(M) * 8;
-}
+int64_t pair_loss_workspace_bytes(int64_t M) { return LossTailWs::bytes(pair_blocks(M)); }
 
 int launch_sample_negatives(const int64_t* item_seq, int64_t seq_rs, const int64_t* lengths,
                             const int64_t* pos_items, const int64_t* offsets, const int64_t* inv,
@@ -349,16 +273,13 @@ int launch_pair_loss_fwd(const float* h, int64_t ldh, const float* tab, const in
                          const int64_t* neg, int64_t M, int64_t d, int64_t V, int64_t n_neg,
                          float gamma, float* diff, float* loss, int64_t* n_live, void* workspace,
                          hipStream_t st) {
-  char* ws = static_cast<char*>(workspace);
   const int64_t nb = pair_blocks(M);
-  unsigned* ticket = reinterpret_cast<unsigned*>(ws);
-  float* psum = reinterpret_cast<float*>(ws + pair_partials_off());
-  int* pcnt = reinterpret_cast<int*>(psum + nb);
-  if (hipMemsetAsync(ticket, 0, 16, st) != hipSuccess) return launch_status("rb_pair_loss_fwd");
-  dispatch_int<1, 2, 4, 8>(row_vecs(d), [&](auto nv) {
-    hipLaunchKernelGGL((k_pair_fwd<decltype(nv)::value>), dim3((unsigned)nb), dim3(256), 0, st, h, ldh, tab,
-                       pos, neg, M, (int)d, V, (int)n_neg, gamma, diff, psum, pcnt, ticket, loss,
-                       n_live);
+  const LossTailWs ws(workspace, nb);
+  if (!ws.reset(st)) return launch_status("rb_pair_loss_fwd");
+  dispatch_row_vecs(d, [&](auto nv) {
+    hipLaunchKernelGGL((k_pair_fwd<decltype(nv)::value>), dim3((unsigned)nb), dim3(256), 0, st, h,
+                       ldh, tab, pos, neg, M, (int)d, V, (int)n_neg, gamma, diff, ws.psum, ws.pcnt,
+                       ws.ticket, loss, n_live);
   });
   return launch_status("rb_pair_loss_fwd");
 }
@@ -368,9 +289,9 @@ int launch_pair_loss_bwd(const float* tab, const int64_t* pos, const int64_t* ne
                          int64_t d, int64_t V, int64_t n_neg, float gamma, float* dh, float* coef,
                          hipStream_t st) {
   const int64_t nb = pair_blocks(M);
-  dispatch_int<1, 2, 4, 8>(row_vecs(d), [&](auto nv) {
-    hipLaunchKernelGGL((k_pair_bwd<decltype(nv)::value>), dim3((unsigned)nb), dim3(256), 0, st, tab, pos, neg,
-                       diff, dloss, n_live, M, (int)d, V, (int)n_neg, gamma, dh, coef);
+  dispatch_row_vecs(d, [&](auto nv) {
+    hipLaunchKernelGGL((k_pair_bwd<decltype(nv)::value>), dim3((unsigned)nb), dim3(256), 0, st, tab,
+                       pos, neg, diff, dloss, n_live, M, (int)d, V, (int)n_neg, gamma, dh, coef);
   });
   return launch_status("rb_pair_loss_bwd");
 }

@@ -14,10 +14,8 @@
 //                           a wave one 16-row tile of it: per 16-column tile
 //                           the scores come out transposed (lane = row, the
 //                           four registers = columns 4g + q), the log-sum-exp
-//                           runs online in registers, and the mean goes
-//                           through per-workgroup partials that the last
-//                           workgroup to arrive adds in workgroup order
-//                           (k_pair_fwd's scheme);
+//                           runs online in registers, and the mean over the
+//                           live rows is loss_tail.h's;
 //   rb_shared_softmax_bwd   two kernels.  k_ss_dh recomputes the same score
 //                           tiles, forms p_j = exp(z_j - lse) in the MFMA's A
 //                           layout and accumulates dh = P E_neg on the MFMA,
@@ -36,6 +34,7 @@
 //                           per column and 16-row tile; a dead or out-of-range
 //                           column reads nothing.
 #include "common.h"
+#include "loss_tail.h"
 
 namespace rb {
 namespace {
@@ -105,11 +104,6 @@ k_ss_fwd(const float* __restrict__ h, int64_t ldh, const float* __restrict__ tab
          const float* __restrict__ item_shift, float* __restrict__ lse,
          float* __restrict__ z0o, float* psum, int* pcnt, unsigned* ticket,
          float* __restrict__ loss, int64_t* __restrict__ n_live) {
-  __shared__ float s_sum[4];
-  __shared__ int s_cnt[4];
-  __shared__ float red[256];
-  __shared__ long long redc[256];
-  __shared__ bool last;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int64_t s = blockIdx.x / RB;
   const int rb0 = blockIdx.x % RB;
@@ -184,48 +178,7 @@ k_ss_fwd(const float* __restrict__ h, int64_t ldh, const float* __restrict__ tab
       wcnt += cnt;
     }
   }
-  if (lane == 0) {
-    s_sum[wave] = wsum;
-    s_cnt[wave] = wcnt;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float a = 0.0f;
-    int k = 0;
-    for (int w = 0; w < 4; ++w) {
-      a += s_sum[w];
-      k += s_cnt[w];
-    }
-    psum[blockIdx.x] = a;
-    pcnt[blockIdx.x] = k;
-    __threadfence();
-    last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-  }
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
-  float a = 0.0f;
-  long long k = 0;
-  for (unsigned i = threadIdx.x; i < gridDim.x; i += 256) {
-    a += psum[i];
-    k += pcnt[i];
-  }
-  red[threadIdx.x] = a;
-  redc[threadIdx.x] = k;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      red[threadIdx.x] += red[threadIdx.x + w];
-      redc[threadIdx.x] += redc[threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const long long nl = redc[0];
-    loss[0] = red[0] / (float)(nl > 0 ? nl : 1);
-    n_live[0] = nl;
-    *ticket = 0u;
-  }
+  mean_loss_tail<4>(wsum, wcnt, psum, pcnt, ticket, loss, n_live);   // a slot per wave
 }
 
 // dh_r = scale (sum_j p_rj E[neg_j] - (sum_j p_rj) E[target_r]), coef_r = -scale
@@ -414,7 +367,7 @@ int ss_row_blocks(int64_t max_len) {
 int64_t shared_softmax_blocks(int64_t B, int64_t max_len) { return B * ss_row_blocks(max_len); }
 
 int64_t shared_softmax_workspace_bytes(int64_t B, int64_t max_len) {
-  return 16 + shared_softmax_blocks(B, max_len) * 8;
+  return LossTailWs::bytes(shared_softmax_blocks(B, max_len));
 }
 
 int launch_shared_softmax_fwd(const float* h, int64_t ldh, const float* tab, const int64_t* target,
@@ -424,16 +377,13 @@ int launch_shared_softmax_fwd(const float* h, int64_t ldh, const float* tab, con
                               float* z0, float* loss, int64_t* n_live, void* workspace,
                               hipStream_t st) {
   const char* fn = item_shift ? "rb_shared_softmax_fwd_items" : "rb_shared_softmax_fwd";
-  char* ws = static_cast<char*>(workspace);
   const int RB = ss_row_blocks(max_len);
   const int64_t nb = B * RB;
-  unsigned* ticket = reinterpret_cast<unsigned*>(ws);
-  float* psum = reinterpret_cast<float*>(ws + 16);
-  int* pcnt = reinterpret_cast<int*>(psum + nb);
-  if (hipMemsetAsync(ticket, 0, 16, st) != hipSuccess) return launch_status(fn);
+  const LossTailWs ws(workspace, nb);
+  if (!ws.reset(st)) return launch_status(fn);
   hipLaunchKernelGGL(item_shift ? k_ss_fwd<true> : k_ss_fwd<false>, dim3((unsigned)nb), dim3(256),
                      0, st, h, ldh, tab, target, neg, offsets, order, M, B, (int)d, V, (int)n, RB,
-                     shift, item_shift, lse, z0, psum, pcnt, ticket, loss, n_live);
+                     shift, item_shift, lse, z0, ws.psum, ws.pcnt, ws.ticket, loss, n_live);
   return launch_status(fn);
 }
 

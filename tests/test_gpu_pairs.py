@@ -187,6 +187,45 @@ def test_pair_loss_refused_width_takes_the_torch_path(cuda):
     close(loss, _ref64(h, tab, pos, neg)[0], "loss (torch path)")
 
 
+@pytest.mark.parametrize("d", [4, 68, 132, 260])
+def test_pair_diff_is_the_candidate_scores_difference_bit_for_bit(cuda, d):
+    """The pairwise loss and the candidate kernels score a pair with one
+    function (csrc/row_group.h): diff = score(pos) - score(neg) of
+    rb_candidate_scores, one exact fp32 subtraction on both sides, so the
+    comparison is of bits.  One d per count of 16-B loads per lane (1, 2, 4,
+    8), each with lanes past d that load zeros; M = 70: two workgroups, the
+    second partly empty; h read in place through a row stride of d + 4."""
+    from datamining_recblr_amd import kernels
+
+    M, Vt, n = 70, 50, 3
+    h, tab, pos, neg = _case(M, Vt, d, n, cuda, 20 + d, (9,), ((33, 1),))
+    wide = torch.zeros(M, d + 4, device=cuda)
+    wide[:, :d] = h
+    _, _, diff = kernels.pair_loss_fwd(wide[:, :d], tab, pos, neg, GAMMA)
+    scores = kernels.candidate_scores(wide[:, :d], tab, torch.cat([pos[:, None], neg], 1))
+    live = (pos >= 0)[:, None] & (neg >= 0)
+    assert int(live.sum()) == M * n - n - 1
+    assert torch.equal(diff[live], (scores[:, :1] - scores[:, 1:])[live])
+    assert (diff[9] == 0).all() and diff[33, 1] == 0 and (diff[live] != 0).any()
+
+
+def test_pair_loss_mean_over_more_than_256_workgroups(cuda):
+    """258 workgroups: the last one to arrive re-reads the partials with a
+    stride of 256, so its loop takes a second step.  The reference is the fp64
+    mean of the per-pair terms of the kernel's own diff."""
+    from datamining_recblr_amd import kernels
+
+    M = 64 * 257 + 3
+    h, tab, pos, neg = _case(M, 8, 4, 1, cuda, 13, (0, 64 * 256, M - 1), ((5, 0), (64 * 257, 0)))
+    loss, n_live, diff = kernels.pair_loss_fwd(h, tab, pos, neg, GAMMA)
+    again = kernels.pair_loss_fwd(h, tab, pos, neg, GAMMA)
+    live = (pos >= 0)[:, None] & (neg >= 0)
+    assert int(n_live) == int(live.sum()) == M - 5
+    assert torch.equal(loss, again[0]) and torch.equal(n_live, again[1])
+    terms = -torch.log(GAMMA + torch.sigmoid(diff.double()))
+    close(loss, terms[live].mean(), "loss")
+
+
 # ---- 3. saturation -------------------------------------------------------------------
 def test_pair_loss_saturated(cuda):
     """|x| in [100, 104] on both signs: h_r = x_r (E[pos] - E[neg]) / |E[pos] -

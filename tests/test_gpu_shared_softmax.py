@@ -139,6 +139,35 @@ def test_two_calls_give_the_same_bits(cuda, n):
     assert all(torch.equal(x, y) for x, y in zip(one, two))
 
 
+def test_mean_over_more_than_256_workgroups(cuda):
+    """260 sequences of one and two rows, a workgroup each: the last one to
+    arrive re-reads the partials with a stride of 256, so its loop takes a
+    second step.  The reference is the fp64 mean of the kernel's own lse - z0
+    over the live rows, under this file's bound."""
+    from datamining_recblr_amd import kernels
+
+    B, d = 260, 16
+    g = torch.Generator().manual_seed(7)
+    offsets, order = plan([1 + b % 2 for b in range(B)])
+    M = int(offsets[-1])
+    h, tab = 0.5 * torch.randn(M, d, generator=g), 0.5 * torch.randn(V, d, generator=g)
+    target = torch.randint(0, V, (M,), generator=g)
+    neg = torch.randint(0, V, (B, 1), generator=g)
+    target[[0, 200, M - 1]] = -1
+    args = [t.to(cuda) for t in (h, tab, target, neg, offsets, order)]
+    loss, n_live, lse, z0 = kernels.shared_softmax_fwd(*args, SHIFT, 2)
+    again = kernels.shared_softmax_fwd(*args, SHIFT, 2)
+    live = args[2] >= 0
+    assert int(n_live) == int(live.sum()) == M - 3
+    assert torch.equal(loss, again[0]) and torch.equal(n_live, again[1])
+    want = (lse.double() - z0.double())[live].mean()
+    err, err32 = abs(float(loss) - float(want)), abs(float((lse - z0)[live].mean()) - float(want))
+    bound = max(4 * err32, ULPS * abs(float(want)))
+    print(f"loss: kernel err {err:.3e}, fp32 torch err {err32:.3e}, ref {float(want):.3e}, "
+          f"bound {bound:.3e}")
+    assert err <= bound, f"loss: {err:.3e} > {bound:.3e}"
+
+
 def test_unsupported_shapes_take_the_reference(cuda):
     from datamining_recblr_amd import kernels, scoring
 
