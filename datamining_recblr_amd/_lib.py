@@ -100,6 +100,9 @@ PAIR_SIGNATURES = parse_header(_read(os.path.join(os.path.dirname(HEADER_PATH),
 # candidate-list scoring (include/recblr_candidates.h): likewise
 CANDIDATE_SIGNATURES = parse_header(_read(os.path.join(os.path.dirname(HEADER_PATH),
                                                        "recblr_candidates.h")))
+# catalogue filters (include/recblr_filters.h): likewise
+FILTER_SIGNATURES = parse_header(_read(os.path.join(os.path.dirname(HEADER_PATH),
+                                                    "recblr_filters.h")))
 # the experimental library (experimental/recblr_exp.h: opt-in kernels that
 # measured slower than the default path; never loaded unless requested)
 EXP_SIGNATURES = parse_header(_read(os.path.join(_HERE, "experimental", "recblr_exp.h")))
@@ -141,7 +144,8 @@ def load(path: str | None = None) -> ctypes.CDLL:
     """Load (once) and return the native library with typed prototypes.  An
     explicit path is loaded afresh and not cached."""
     return _load(path or LIB_PATH,
-                 {**SIGNATURES, **DENSE_SIGNATURES, **PAIR_SIGNATURES, **CANDIDATE_SIGNATURES},
+                 {**SIGNATURES, **DENSE_SIGNATURES, **PAIR_SIGNATURES, **CANDIDATE_SIGNATURES,
+                  **FILTER_SIGNATURES},
                  "HIP extension not built",
                  "rb_version",
                  "ABI mismatch: library {} vs binding {}; rebuild", cache=path is None,

@@ -469,14 +469,61 @@ int64_t rb_item_rank_workspace(int64_t B, int64_t V, int64_t d) {
   return item_rank_workspace_bytes(B, V);
 }
 
+namespace {
+// what rb_item_rank and rb_item_rank_allowed check alike
+int check_item_rank(const char* fn, const float* seq, const float* items, const int64_t* target,
+                    int64_t B, int64_t V, int64_t d, int64_t first_item,
+                    const int64_t* n_greater, const void* workspace) {
+  if (int rc = check_items(fn, seq, items, B, V, d)) return rc;
+  if (!target || !n_greater || !workspace) return fail(fn, "null pointer");
+  if (first_item < 0) return fail(fn, "first_item must be >= 0");
+  return 0;
+}
+
+// ... and rb_item_topk and rb_item_topk_allowed
+int check_item_topk(const char* fn, const float* seq, const float* items, int64_t B, int64_t V,
+                    int64_t d, int64_t k, int64_t first_item, const int64_t* exclude, int64_t E,
+                    const int64_t* ids, const float* scores, const void* workspace) {
+  if (int rc = check_items(fn, seq, items, B, V, d)) return rc;
+  if (!ids || !scores || !workspace) return fail(fn, "null pointer");
+  if (k < 1 || k > 64) return fail(fn, "k must be in [1, 64]");
+  if (first_item < 0) return fail(fn, "first_item must be >= 0");
+  if (E < 0) return fail(fn, "E must be >= 0");
+  if (E > 0 && !exclude) return fail(fn, "null pointer (exclude with E > 0)");
+  return 0;
+}
+
+// the allow-bitmaps of include/recblr_filters.h (after the checks above: V > 0)
+int check_allow(const char* fn, const int32_t* allow, int64_t F, int64_t words, int64_t V) {
+  if (!allow) return fail(fn, "null pointer (allow)");
+  if (F < 1) return fail(fn, "F must be >= 1");
+  if (words != (V + 31) / 32) return fail(fn, "words must be ceil(V / 32)");
+  return 0;
+}
+}  // namespace
+
 int rb_item_rank(const float* seq, const float* items, const int64_t* target, int64_t B,
                  int64_t V, int64_t d, int64_t first_item, int64_t* n_greater, int64_t* n_equal,
                  void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = check_items("rb_item_rank", seq, items, B, V, d)) return rc;
-  if (!target || !n_greater || !workspace) return fail("rb_item_rank: null pointer");
-  if (first_item < 0) return fail("rb_item_rank: first_item must be >= 0");
+  if (int rc = check_item_rank("rb_item_rank", seq, items, target, B, V, d, first_item,
+                               n_greater, workspace))
+    return rc;
   return launch_item_rank(seq, items, target, B, V, d, first_item, n_greater, n_equal, workspace,
                           workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+}
+
+int rb_item_rank_allowed(const float* seq, const float* items, const int64_t* target, int64_t B,
+                         int64_t V, int64_t d, int64_t first_item, int64_t* n_greater,
+                         int64_t* n_equal, void* workspace, int64_t workspace_bytes,
+                         void* stream, const int32_t* allow, int64_t F, int64_t words,
+                         const int64_t* allow_rows) {
+  const char* fn = "rb_item_rank_allowed";
+  if (int rc = check_item_rank(fn, seq, items, target, B, V, d, first_item, n_greater, workspace))
+    return rc;
+  if (int rc = check_allow(fn, allow, F, words, V)) return rc;
+  return launch_item_rank_allowed(seq, items, target, B, V, d, first_item, n_greater, n_equal,
+                                  workspace, workspace_bytes, allow, F, words, allow_rows,
+                                  reinterpret_cast<hipStream_t>(stream));
 }
 
 int64_t rb_item_topk_workspace(int64_t B, int64_t V, int64_t d, int64_t k) {
@@ -487,15 +534,28 @@ int64_t rb_item_topk_workspace(int64_t B, int64_t V, int64_t d, int64_t k) {
 int rb_item_topk(const float* seq, const float* items, int64_t B, int64_t V, int64_t d, int64_t k,
                  int64_t first_item, const int64_t* exclude, int64_t E, int64_t* ids,
                  float* scores, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = check_items("rb_item_topk", seq, items, B, V, d)) return rc;
-  if (!ids || !scores || !workspace) return fail("rb_item_topk: null pointer");
-  if (k < 1 || k > 64) return fail("rb_item_topk: k must be in [1, 64]");
-  if (first_item < 0) return fail("rb_item_topk: first_item must be >= 0");
-  if (E < 0) return fail("rb_item_topk: E must be >= 0");
-  if (E > 0 && !exclude) return fail("rb_item_topk: null pointer (exclude with E > 0)");
+  if (int rc = check_item_topk("rb_item_topk", seq, items, B, V, d, k, first_item, exclude, E, ids,
+                               scores, workspace))
+    return rc;
   return launch_item_topk(seq, items, B, V, d, k, first_item, E > 0 ? exclude : nullptr, E, ids,
                           scores, workspace, workspace_bytes,
                           reinterpret_cast<hipStream_t>(stream));
+}
+
+int rb_item_topk_allowed(const float* seq, const float* items, int64_t B, int64_t V, int64_t d,
+                         int64_t k, int64_t first_item, const int64_t* exclude, int64_t E,
+                         int64_t* ids, float* scores, void* workspace, int64_t workspace_bytes,
+                         void* stream, const int32_t* allow, int64_t F, int64_t words,
+                         const int64_t* allow_rows) {
+  const char* fn = "rb_item_topk_allowed";
+  if (int rc = check_item_topk(fn, seq, items, B, V, d, k, first_item, exclude, E, ids, scores,
+                               workspace))
+    return rc;
+  if (int rc = check_allow(fn, allow, F, words, V)) return rc;
+  return launch_item_topk_allowed(seq, items, B, V, d, k, first_item,
+                                  E > 0 ? exclude : nullptr, E, ids, scores, workspace,
+                                  workspace_bytes, allow, F, words, allow_rows,
+                                  reinterpret_cast<hipStream_t>(stream));
 }
 
 int rb_item_ce_probs(const float* seq, const float* items, const int64_t* target,

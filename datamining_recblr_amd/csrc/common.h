@@ -12,6 +12,7 @@
 #include "../../include/recblr_dense.h"
 #include "../../include/recblr_pairs.h"
 #include "../../include/recblr_candidates.h"
+#include "../../include/recblr_filters.h"
 
 namespace rb {
 
@@ -561,6 +562,16 @@ int64_t item_topk_workspace_bytes(int64_t B, int64_t V, int64_t k);
 int launch_item_topk(const float* E, const float* W, int64_t B, int64_t V, int64_t D, int64_t k,
                      int64_t first, const int64_t* ex, int64_t NE, int64_t* ids, float* scores,
                      void* ws, int64_t ws_bytes, hipStream_t st);
+// the two above under per-row allow-bitmaps (include/recblr_filters.h); same workspaces
+int launch_item_rank_allowed(const float* E, const float* W, const int64_t* tgt, int64_t B,
+                             int64_t V, int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq,
+                             void* ws, int64_t ws_bytes, const int* allow, int64_t F,
+                             int64_t words, const int64_t* allow_rows, hipStream_t st);
+int launch_item_topk_allowed(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
+                             int64_t k, int64_t first, const int64_t* ex, int64_t NE,
+                             int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
+                             const int* allow, int64_t F, int64_t words,
+                             const int64_t* allow_rows, hipStream_t st);
 int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, const float* lse,
                          const float* dloss, int64_t B, int64_t V, int64_t D, int64_t v_off,
                          float* out, int64_t ld, hipStream_t st);

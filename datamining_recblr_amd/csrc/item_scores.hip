@@ -217,12 +217,48 @@ __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2
   m = M;
 }
 
+// ---- allow-bitmaps: a filter is one 32-bit word per 32-item tile --------------------
+// words [F, W] int32 (bit i of word w of filter f: item 32 w + i is allowed),
+// rows [B] int64 or null: the filter each row selects.
+struct AllowArgs {
+  const int* words;
+  int64_t F, W;
+  const int64_t* rows;
+};
+
+// One row's view of its filter.  rows null: filter 0.  f == -1: every item is
+// allowed; f outside [-1, F): none is.  The filter and word indices are
+// clamped for the load and the loaded word masked, so nothing is ever read out
+// of range.
+struct AllowRow {
+  const int* w;
+  int64_t last;
+  unsigned keep, force;   // the row's word = (loaded & keep) | force
+  __device__ __forceinline__ AllowRow(const AllowArgs& a, int64_t b) {
+    const int64_t f = a.rows ? a.rows[b] : 0;
+    w = a.words + max<int64_t>(0, min<int64_t>(f, a.F - 1)) * a.W;
+    last = a.W - 1;
+    keep = (f >= 0 && f < a.F) ? ~0u : 0u;
+    force = f == -1 ? ~0u : 0u;
+  }
+  __device__ __forceinline__ unsigned word(int64_t t) const {
+    return ((unsigned)w[max<int64_t>(0, min<int64_t>(t, last))] & keep) | force;
+  }
+};
+
+// bit r of the result = bit crow(r, h) of a tile's word: a lane's 16 items
+__device__ __forceinline__ unsigned lane_bits(unsigned a, int h) {
+  a >>= 4 * h;
+  return (a & 0xfu) | ((a >> 4) & 0xf0u) | ((a >> 8) & 0xf00u) | ((a >> 12) & 0xf000u);
+}
+
 // ---- target scores: the MFMA chain order, one thread per row ------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_target_dot(const float* __restrict__ E,
-                                                    const float* __restrict__ W,
-                                                    const int64_t* __restrict__ tgt, int64_t B,
-                                                    int64_t V, float* __restrict__ ts) {
+// kAllow: a target its row's filter does not allow counts as out of range
+template <int D, bool kAllow>
+__device__ __forceinline__ void target_dot(const float* __restrict__ E,
+                                           const float* __restrict__ W,
+                                           const int64_t* __restrict__ tgt, int64_t B, int64_t V,
+                                           float* __restrict__ ts, const AllowArgs& al) {
   constexpr int KH = D / 2;
   const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
@@ -230,6 +266,12 @@ __global__ __launch_bounds__(256) void k_target_dot(const float* __restrict__ E,
   if (t < 0 || t >= V) {
     ts[b] = NAN;
     return;
+  }
+  if constexpr (kAllow) {
+    if (!((AllowRow(al, b).word(t >> 5) >> (t & 31)) & 1u)) {
+      ts[b] = NAN;
+      return;
+    }
   }
   float e0[KH], e1[KH], w0[KH], w1[KH];
   ld_half<KH>(e0, E + b * D, 0);
@@ -245,6 +287,22 @@ __global__ __launch_bounds__(256) void k_target_dot(const float* __restrict__ E,
   ts[b] = acc;
 }
 
+template <int D>
+__global__ __launch_bounds__(256) void k_target_dot(const float* __restrict__ E,
+                                                    const float* __restrict__ W,
+                                                    const int64_t* __restrict__ tgt, int64_t B,
+                                                    int64_t V, float* __restrict__ ts) {
+  target_dot<D, false>(E, W, tgt, B, V, ts, AllowArgs{});
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_target_dot_allowed(const float* __restrict__ E,
+                                                            const float* __restrict__ W,
+                                                            const int64_t* __restrict__ tgt,
+                                                            int64_t B, int64_t V,
+                                                            float* __restrict__ ts, AllowArgs al) {
+  target_dot<D, true>(E, W, tgt, B, V, ts, al);
+}
 
 // Workgroup placement.  The grid is 1-D over RB fixed-row blocks x S splits
 // of the streamed operand (S padded to a multiple of 8).  Workgroups are
@@ -561,14 +619,16 @@ __global__ __launch_bounds__(256) void k_sum_parts(const float* __restrict__ par
 }
 
 // ---- ranks: #items scoring above / equal to the target -----------------------------
-template <int D>
-__global__ __launch_bounds__(256) void k_item_rank(const float* __restrict__ E,
-                                                   const float* __restrict__ W,
-                                                   const float* __restrict__ ts,
-                                                   const int64_t* __restrict__ tgt, int64_t B,
-                                                   int64_t V, int64_t first, int64_t per, int64_t RB, int64_t NS,
-                                                   int* __restrict__ gt_part,
-                                                   int* __restrict__ eq_part) {
+// kAllow: only items that the row's filter allows are counted; tile t of the
+// items is word t of the filter, read one tile ahead of its use.
+template <int D, bool kAllow>
+__device__ __forceinline__ void item_rank(const float* __restrict__ E,
+                                          const float* __restrict__ W,
+                                          const float* __restrict__ ts,
+                                          const int64_t* __restrict__ tgt, int64_t B, int64_t V,
+                                          int64_t first, int64_t per, int64_t RB, int64_t NS,
+                                          int* __restrict__ gt_part, int* __restrict__ eq_part,
+                                          const AllowArgs& al) {
   constexpr int KH = D / 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
   Place pl;
@@ -580,15 +640,23 @@ __global__ __launch_bounds__(256) void k_item_rank(const float* __restrict__ E,
   const float tsb = ts[bc];
   const int64_t tb = tgt[bc];
   int gt = 0, eq = 0;
+  const AllowRow ar(al, kAllow ? bc : 0);
+  unsigned aw = kAllow ? ar.word(pl.split * per) : 0u;   // the next tile's word
   stream_tiles<D, false>(W, V, per, pl.split, nullptr, nullptr,
                          [&](int64_t t, const float* tile, const float*, const int64_t*) {
     const int64_t v0 = t * kTile;
+    unsigned am = 0xffffu;
+    if constexpr (kAllow) {
+      am = lane_bits(aw, h);
+      aw = ar.word(t + 1);
+    }
     const f32x16 x = lds_dot<D, KH, true>(tile, j, h, eb);
     const int lo = rel32(first, v0), hi = rel32(V, v0), tt = rel32(tb, v0);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int c = crow(r, h);
-      const bool ok = (c >= lo) & (c < hi) & (c != tt);
+      bool ok = (c >= lo) & (c < hi) & (c != tt);
+      if constexpr (kAllow) ok &= (am >> r) & 1u;
       gt += (ok & (x[r] > tsb)) ? 1 : 0;
       eq += (ok & (x[r] == tsb)) ? 1 : 0;
     }
@@ -599,6 +667,25 @@ __global__ __launch_bounds__(256) void k_item_rank(const float* __restrict__ E,
     gt_part[pl.split * B + b] = gt;
     eq_part[pl.split * B + b] = eq;
   }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_item_rank(const float* __restrict__ E,
+                                                   const float* __restrict__ W,
+                                                   const float* __restrict__ ts,
+                                                   const int64_t* __restrict__ tgt, int64_t B,
+                                                   int64_t V, int64_t first, int64_t per, int64_t RB, int64_t NS,
+                                                   int* __restrict__ gt_part,
+                                                   int* __restrict__ eq_part) {
+  item_rank<D, false>(E, W, ts, tgt, B, V, first, per, RB, NS, gt_part, eq_part, AllowArgs{});
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_item_rank_allowed(
+    const float* __restrict__ E, const float* __restrict__ W, const float* __restrict__ ts,
+    const int64_t* __restrict__ tgt, int64_t B, int64_t V, int64_t first, int64_t per, int64_t RB,
+    int64_t NS, int* __restrict__ gt_part, int* __restrict__ eq_part, AllowArgs al) {
+  item_rank<D, true>(E, W, ts, tgt, B, V, first, per, RB, NS, gt_part, eq_part, al);
 }
 
 __global__ __launch_bounds__(256) void k_rank_rows(const int* __restrict__ gt_part,
@@ -645,20 +732,19 @@ __device__ __forceinline__ bool beats(float s, int id, float s2, int id2) {
   return s > s2 || (s == s2 && id < id2);
 }
 
-template <int D, int KP>
-__global__ __launch_bounds__(256) void k_item_topk(const float* __restrict__ E,
-                                                   const float* __restrict__ W, int64_t B,
-                                                   int64_t V, int64_t first, int k,
-                                                   const int64_t* __restrict__ ex, int64_t NE,
-                                                   int64_t per, int64_t RB, int64_t NS,
-                                                   float* __restrict__ c_sc,
-                                                   int* __restrict__ c_id) {
+// kAllow: tile t of the items is word t of the row's filter, so the filter is
+// one AND into the pass mask per tile, ahead of the admission loop: an item the
+// filter drops is never a candidate, and a sparse filter shortens the loop.
+// The word is read one tile ahead of its use.
+template <int D, int KP, bool kAllow>
+__device__ __forceinline__ void item_topk(const float* __restrict__ E,
+                                          const float* __restrict__ W, int64_t B, int64_t V,
+                                          int64_t first, int k, const int64_t* __restrict__ ex,
+                                          int64_t NE, int64_t per, int64_t RB, int64_t NS,
+                                          float* __restrict__ c_sc, int* __restrict__ c_id,
+                                          float* l_sc, int* l_id, unsigned* l_ex,
+                                          const AllowArgs& al) {
   constexpr int KH = D / 2, NR = kWaves * kTile, XW = kExBits / 32;
-  // entry i / map word w of row r at [i * NR + r] / [w * NR + r]: lanes of a
-  // wave touching the same entry or word hit distinct banks
-  __shared__ float l_sc[KP * NR];
-  __shared__ int l_id[KP * NR];
-  __shared__ unsigned l_ex[XW * NR];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
   Place pl;
   if (!place(RB, NS, pl)) return;
@@ -721,9 +807,16 @@ __global__ __launch_bounds__(256) void k_item_topk(const float* __restrict__ E,
     thr_id = wi;
     thr_pos = wp;
   };
+  const AllowRow ar(al, kAllow ? bc : 0);
+  unsigned aw = kAllow ? ar.word(pl.split * per) : 0u;   // the next tile's word
   stream_tiles<D, false>(W, V, per, pl.split, nullptr, nullptr,
                          [&](int64_t t, const float* tile, const float*, const int64_t*) {
     const int64_t v0 = t * kTile;
+    unsigned am = 0xffffu;
+    if constexpr (kAllow) {
+      am = lane_bits(aw, h);
+      aw = ar.word(t + 1);
+    }
     const f32x16 x = lds_dot<D, KH, true>(tile, j, h, eb);
     const int lo = rel32(first, v0), hi = rel32(V, v0);
     unsigned m = 0;   // bit r: score r passes the cheap filter
@@ -732,6 +825,7 @@ __global__ __launch_bounds__(256) void k_item_topk(const float* __restrict__ E,
       const int c = crow(r, h);
       m |= ((c >= lo) & (c < hi) & (x[r] >= thr)) ? 1u << r : 0u;
     }
+    if constexpr (kAllow) m &= am;
     // wave-uniform loop: every lane takes its lowest passing score per turn
     while (__builtin_amdgcn_ballot_w64(m != 0) != 0) {
       const bool p = m != 0;
@@ -758,6 +852,38 @@ __global__ __launch_bounds__(256) void k_item_topk(const float* __restrict__ E,
       c_id[o + i] = l_id[i * NR + row];
     }
   }
+}
+
+// The kernels' LDS (the arrays belong to the kernel, not to item_topk: a kernel's
+// LDS layout follows its own variables): entry i / map word w of row r at
+// [i * NR + r] / [w * NR + r], so lanes of a wave touching the same entry or
+// word hit distinct banks.
+#define TOPK_LDS                                              \
+  __shared__ float l_sc[KP * kWaves * kTile];                 \
+  __shared__ int l_id[KP * kWaves * kTile];                   \
+  __shared__ unsigned l_ex[kExBits / 32 * kWaves * kTile]
+
+template <int D, int KP>
+__global__ __launch_bounds__(256) void k_item_topk(const float* __restrict__ E,
+                                                   const float* __restrict__ W, int64_t B,
+                                                   int64_t V, int64_t first, int k,
+                                                   const int64_t* __restrict__ ex, int64_t NE,
+                                                   int64_t per, int64_t RB, int64_t NS,
+                                                   float* __restrict__ c_sc,
+                                                   int* __restrict__ c_id) {
+  TOPK_LDS;
+  item_topk<D, KP, false>(E, W, B, V, first, k, ex, NE, per, RB, NS, c_sc, c_id, l_sc, l_id, l_ex,
+                          AllowArgs{});
+}
+
+template <int D, int KP>
+__global__ __launch_bounds__(256) void k_item_topk_allowed(
+    const float* __restrict__ E, const float* __restrict__ W, int64_t B, int64_t V, int64_t first,
+    int k, const int64_t* __restrict__ ex, int64_t NE, int64_t per, int64_t RB, int64_t NS,
+    float* __restrict__ c_sc, int* __restrict__ c_id, AllowArgs al) {
+  TOPK_LDS;
+  item_topk<D, KP, true>(E, W, B, V, first, k, ex, NE, per, RB, NS, c_sc, c_id, l_sc, l_id, l_ex,
+                         al);
 }
 
 // One wave per row: the row's S lists of k candidates (all ids distinct: the
@@ -1390,51 +1516,104 @@ int launch_item_ce_bwd(const float* E, const float* W, const int64_t* tgt, const
   return launch_status("rb_item_ce_bwd");
 }
 
-int launch_item_rank(const float* E, const float* W, const int64_t* tgt, int64_t B, int64_t V,
-                     int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq, void* ws,
-                     int64_t ws_bytes, hipStream_t st) {
+namespace {
+// rb_item_rank (al null) and rb_item_rank_allowed: one workspace, one plan
+int item_rank_launch(const char* fn, const float* E, const float* W, const int64_t* tgt,
+                     int64_t B, int64_t V, int64_t D, int64_t first, int64_t* n_gt,
+                     int64_t* n_eq, void* ws, int64_t ws_bytes, const AllowArgs* al,
+                     hipStream_t st) {
   const RankWs L = rank_layout(B, V);
-  if (ws_bytes < (int64_t)L.total) return fail("rb_item_rank: workspace too small");
+  if (ws_bytes < (int64_t)L.total) return fail((std::string(fn) + ": workspace too small").c_str());
   char* w = static_cast<char*>(ws);
   float* ts = reinterpret_cast<float*>(w + L.ts);
   int* gt = reinterpret_cast<int*>(w + L.gt);
   int* eq = reinterpret_cast<int*>(w + L.eq);
   const Grid2 g = plan(B, ntiles(V));
+  const dim3 rows((unsigned)((B + 255) / 256));
   if (int rc = for_item_dim(D, [&](auto dc) {
-        hipLaunchKernelGGL(k_target_dot<dc>, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, E,
-                           W, tgt, B, V, ts);
-        hipLaunchKernelGGL(k_item_rank<dc>, dim3(g.wgs()), dim3(256), 0, st, E, W, ts, tgt, B, V,
-                           first, g.per, g.blocks, g.splits, gt, eq);
+        if (al) {
+          hipLaunchKernelGGL(k_target_dot_allowed<dc>, rows, dim3(256), 0, st, E, W, tgt, B, V, ts,
+                             *al);
+          hipLaunchKernelGGL(k_item_rank_allowed<dc>, dim3(g.wgs()), dim3(256), 0, st, E, W, ts,
+                             tgt, B, V, first, g.per, g.blocks, g.splits, gt, eq, *al);
+        } else {
+          hipLaunchKernelGGL(k_target_dot<dc>, rows, dim3(256), 0, st, E, W, tgt, B, V, ts);
+          hipLaunchKernelGGL(k_item_rank<dc>, dim3(g.wgs()), dim3(256), 0, st, E, W, ts, tgt, B, V,
+                             first, g.per, g.blocks, g.splits, gt, eq);
+        }
       }))
     return rc;
-  hipLaunchKernelGGL(k_rank_rows, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, gt, eq,
-                     g.splits, ts, B, n_gt, n_eq);
-  return launch_status("rb_item_rank");
+  hipLaunchKernelGGL(k_rank_rows, rows, dim3(256), 0, st, gt, eq, g.splits, ts, B, n_gt, n_eq);
+  return launch_status(fn);
+}
+}  // namespace
+
+int launch_item_rank(const float* E, const float* W, const int64_t* tgt, int64_t B, int64_t V,
+                     int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq, void* ws,
+                     int64_t ws_bytes, hipStream_t st) {
+  return item_rank_launch("rb_item_rank", E, W, tgt, B, V, D, first, n_gt, n_eq, ws, ws_bytes,
+                          nullptr, st);
+}
+
+int launch_item_rank_allowed(const float* E, const float* W, const int64_t* tgt, int64_t B,
+                             int64_t V, int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq,
+                             void* ws, int64_t ws_bytes, const int* allow, int64_t F,
+                             int64_t words, const int64_t* allow_rows, hipStream_t st) {
+  const AllowArgs al{allow, F, words, allow_rows};
+  return item_rank_launch("rb_item_rank_allowed", E, W, tgt, B, V, D, first, n_gt, n_eq, ws,
+                          ws_bytes, &al, st);
 }
 
 int64_t item_topk_workspace_bytes(int64_t B, int64_t V, int64_t k) {
   return (int64_t)topk_layout(B, V, k).total;
 }
 
-int launch_item_topk(const float* E, const float* W, int64_t B, int64_t V, int64_t D, int64_t k,
-                     int64_t first, const int64_t* ex, int64_t NE, int64_t* ids, float* scores,
-                     void* ws, int64_t ws_bytes, hipStream_t st) {
+namespace {
+// rb_item_topk (al null) and rb_item_topk_allowed: one workspace, one plan
+int item_topk_launch(const char* fn, const float* E, const float* W, int64_t B, int64_t V,
+                     int64_t D, int64_t k, int64_t first, const int64_t* ex, int64_t NE,
+                     int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
+                     const AllowArgs* al, hipStream_t st) {
   const TopkWs L = topk_layout(B, V, k);
-  if (ws_bytes < (int64_t)L.total) return fail("rb_item_topk: workspace too small");
+  if (ws_bytes < (int64_t)L.total) return fail((std::string(fn) + ": workspace too small").c_str());
   char* w = static_cast<char*>(ws);
   float* sc = reinterpret_cast<float*>(w + L.sc);
   int* id = reinterpret_cast<int*>(w + L.id);
   const Grid2 g = plan(B, ntiles(V));
   if (int rc = for_item_dim(D, [&](auto dc) {
         // the candidate list's LDS capacity per (row, split)
-        const auto kernel = k <= 32 ? k_item_topk<dc, 32> : k_item_topk<dc, 64>;
-        hipLaunchKernelGGL(kernel, dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, (int)k, ex,
-                           NE, g.per, g.blocks, g.splits, sc, id);
+        if (al) {
+          const auto kernel = k <= 32 ? k_item_topk_allowed<dc, 32> : k_item_topk_allowed<dc, 64>;
+          hipLaunchKernelGGL(kernel, dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, (int)k,
+                             ex, NE, g.per, g.blocks, g.splits, sc, id, *al);
+        } else {
+          const auto kernel = k <= 32 ? k_item_topk<dc, 32> : k_item_topk<dc, 64>;
+          hipLaunchKernelGGL(kernel, dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, (int)k,
+                             ex, NE, g.per, g.blocks, g.splits, sc, id);
+        }
       }))
     return rc;
   hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, sc, id,
                      g.splits, B, (int)k, ids, scores);
-  return launch_status("rb_item_topk");
+  return launch_status(fn);
+}
+}  // namespace
+
+int launch_item_topk(const float* E, const float* W, int64_t B, int64_t V, int64_t D, int64_t k,
+                     int64_t first, const int64_t* ex, int64_t NE, int64_t* ids, float* scores,
+                     void* ws, int64_t ws_bytes, hipStream_t st) {
+  return item_topk_launch("rb_item_topk", E, W, B, V, D, k, first, ex, NE, ids, scores, ws,
+                          ws_bytes, nullptr, st);
+}
+
+int launch_item_topk_allowed(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
+                             int64_t k, int64_t first, const int64_t* ex, int64_t NE,
+                             int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
+                             const int* allow, int64_t F, int64_t words,
+                             const int64_t* allow_rows, hipStream_t st) {
+  const AllowArgs al{allow, F, words, allow_rows};
+  return item_topk_launch("rb_item_topk_allowed", E, W, B, V, D, k, first, ex, NE, ids, scores,
+                          ws, ws_bytes, &al, st);
 }
 
 int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, const float* lse,

@@ -89,14 +89,22 @@ def evaluate_unseen(model, item_id_lists, targets, topk=(10,), batch_size: int =
 
 
 @torch.no_grad()
-def full_sort_metrics(model, batches, topk=(10, 20)):
+def full_sort_metrics(model, batches, topk=(10, 20), allow=None, allow_rows_key=None):
     """RecBole full-sort Hit/NDCG/MRR@k over leave-one-out batches
-    (interaction dicts with ITEM_SEQ, ITEM_SEQ_LEN and POS_ITEM_ID)."""
+    (interaction dicts with ITEM_SEQ, ITEM_SEQ_LEN and POS_ITEM_ID).  allow
+    (scoring.item_filters) ranks each target among the items of a catalogue
+    filter only; allow_rows_key names the batches' entry that holds each row's
+    filter index (None: filter 0 for every row).  A target that its row's
+    filter does not allow is dropped, as an invalid target is."""
     was_training = model.training
     model.eval()
     gts, eqs = [], []
     for inter in batches:
-        g, e = model.full_sort_rank(inter)
+        if allow is None:
+            g, e = model.full_sort_rank(inter)
+        else:
+            rows = inter[allow_rows_key] if allow_rows_key is not None else None
+            g, e = model.full_sort_rank(inter, allow=allow, allow_rows=rows)
         gts.append(g.cpu())
         eqs.append(e.cpu())
     model.train(was_training)
@@ -105,7 +113,7 @@ def full_sort_metrics(model, batches, topk=(10, 20)):
 
 @torch.no_grad()
 def recommend(model, item_id_lists, k: int = 10, batch_size: int = 1024,
-              exclude_seen: bool = True, device=None):
+              exclude_seen: bool = True, device=None, allow=None, allow_rows=None):
     """Each user's k best items from their input id sequence.
 
     item_id_lists: per-user id sequences (ints in [0, n_items)), batched by
@@ -115,8 +123,22 @@ def recommend(model, item_id_lists, k: int = 10, batch_size: int = 1024,
     (ids int64 [n, k], scores fp32 [n, k]) on the CPU in the callers' order,
     by (score descending, id ascending), id -1 / score -inf where fewer than k
     items are selectable (scoring.top_items).  The model's train/eval mode is
-    left as found."""
+    left as found.
+
+    allow (scoring.item_filters) restricts every list to a catalogue filter;
+    allow_rows [n] names each user's filter in the callers' order (None:
+    filter 0 for everyone, -1: no filter for that user) and follows the users
+    through the length sort."""
     device = device or next(model.parameters()).device
+    if allow_rows is not None:
+        if allow is None:
+            raise ValueError("allow_rows without allow")
+        allow_rows = torch.as_tensor(allow_rows, dtype=torch.int64).cpu()
+        if allow_rows.shape != (len(item_id_lists),):
+            raise ValueError(f"allow_rows must be [{len(item_id_lists)}], got "
+                             f"{tuple(allow_rows.shape)}")
+    if allow is not None:
+        allow = allow.to(device)
     was_training = model.training
     model.eval()
     n = len(item_id_lists)
@@ -135,7 +157,9 @@ def recommend(model, item_id_lists, k: int = 10, batch_size: int = 1024,
                 seq[r, :len(row)] = torch.as_tensor(row, dtype=torch.int64)
             seq = seq.to(device)
             out = model.forward(seq, lens[idx].to(device), exact_lengths=True)
-            i, sc = top_items(out, table, k, first_item=1, exclude=seq if exclude_seen else None)
+            i, sc = top_items(out, table, k, first_item=1, exclude=seq if exclude_seen else None,
+                              allow=allow,
+                              allow_rows=allow_rows[idx] if allow_rows is not None else None)
             ids[idx] = i.cpu()
             scores[idx] = sc.cpu()
     finally:

@@ -696,6 +696,7 @@ def embedding_plan(idx, num_rows, d, stream=None):
 # MFMA roofline).
 FLOP_KERNELS = frozenset({"rb_item_ce_fwd", "rb_item_ce_bwd", "rb_item_ce_probs", "rb_item_rank",
                           "rb_item_scores", "rb_item_topk", "rb_item_ce_fwd_h", "rb_item_ce_probs_h",
+                          "rb_item_rank_allowed", "rb_item_topk_allowed",
                           "rb_item_ce_probs_h_t", "rb_item_ce_probs_h_both",
                           "rb_item_ce_fwd_h_rows", "rb_item_ce_probs_h_rows",
                           "rb_item_ce_probs_h_both_rows"})
@@ -996,32 +997,67 @@ def group_absmax(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def item_rank(seq, items, target, first_item=1, want_equal=True):
+def _allow_args(allow, allow_rows, B, V, device):
+    """The four trailing arguments of rb_item_*_allowed, and the tensors that
+    back them: allow int32 [F, ceil(V/32)] (scoring.ItemFilters.words),
+    allow_rows int64 [B] or None (filter 0 for every row).  Values of
+    allow_rows are the kernel's business (-1: no filter; out of range: the row
+    selects nothing) and are not read here."""
+    _check(allow, "allow", dtype=torch.int32)
+    if allow.dim() != 2 or allow.shape[0] < 1 or allow.shape[1] != (V + 31) // 32:
+        raise ValueError(f"allow must be int32 [F >= 1, {(V + 31) // 32}], got "
+                         f"{tuple(allow.shape)}")
+    if allow.device != device:
+        raise ValueError("allow must be on the same device")
+    allow = allow.contiguous()
+    if allow_rows is not None:
+        _check(allow_rows, "allow_rows", dtype=torch.int64)
+        if allow_rows.shape != (B,) or allow_rows.device != device:
+            raise ValueError(f"allow_rows must be int64 [B] on the same device, got "
+                             f"{tuple(allow_rows.shape)}")
+        allow_rows = allow_rows.contiguous()
+    return (allow, allow_rows), (allow.data_ptr(), allow.shape[0], allow.shape[1],
+                                 allow_rows.data_ptr() if allow_rows is not None else None)
+
+
+def item_rank(seq, items, target, first_item=1, want_equal=True, allow=None, allow_rows=None):
     """(n_greater, n_equal) int64 [B]: items in [first_item, V) other than the
-    target scoring above / equal to it (-1 for an out-of-range target)."""
+    target scoring above / equal to it (-1 for an out-of-range target).
+    allow / allow_rows: per-row allow-bitmaps (_allow_args,
+    rb_item_rank_allowed) — only allowed items count, and a target its row's
+    filter does not allow gives -1."""
     seq, items, target = _item_operands(seq, items, target)
     B, d = seq.shape
     V = items.shape[0]
+    if allow is None and allow_rows is not None:
+        raise ValueError("allow_rows without allow")
     lib = _lib.load()
     ws_bytes = int(lib.rb_item_rank_workspace(B, V, d))
     ws = torch.empty((ws_bytes,), device=seq.device, dtype=torch.uint8)
     gt = torch.empty((B,), device=seq.device, dtype=torch.int64)
     eq = torch.empty((B,), device=seq.device, dtype=torch.int64) if want_equal else None
-    _launch("rb_item_rank", 2 * B * V * d, seq.data_ptr(), items.data_ptr(), target.data_ptr(),
-            B, V, d, int(first_item), gt.data_ptr(), eq.data_ptr() if eq is not None else None,
-            ws.data_ptr(), ws_bytes, _stream(seq), _flops=True)
+    args = (seq.data_ptr(), items.data_ptr(), target.data_ptr(), B, V, d, int(first_item),
+            gt.data_ptr(), eq.data_ptr() if eq is not None else None, ws.data_ptr(), ws_bytes,
+            _stream(seq))
+    if allow is None:
+        _launch("rb_item_rank", 2 * B * V * d, *args, _flops=True)
+    else:
+        _keep, extra = _allow_args(allow, allow_rows, B, V, seq.device)
+        _launch("rb_item_rank_allowed", 2 * B * V * d, *args, *extra, _flops=True)
     return gt, eq
 
 
 ITEM_TOPK_MAX = 64
 
 
-def item_topk(seq, items, k, first_item=1, exclude=None):
+def item_topk(seq, items, k, first_item=1, exclude=None, allow=None, allow_rows=None):
     """(ids int64 [B, k], scores fp32 [B, k]): each row's k best items in
     [first_item, V) not listed in exclude [B, E] (int64; entries outside
     [0, V) ignored), by (score descending, id ascending), scores bit-identical
     to item_scores'; id -1 / score -inf where fewer than k are selectable.
-    No [B, V] buffer (rb_item_topk)."""
+    No [B, V] buffer (rb_item_topk).  allow / allow_rows: per-row
+    allow-bitmaps (_allow_args, rb_item_topk_allowed) — the selection runs
+    over the items that the row's filter allows."""
     seq, items, _ = _item_operands(seq, items)
     B, d = seq.shape
     V = items.shape[0]
@@ -1035,14 +1071,21 @@ def item_topk(seq, items, k, first_item=1, exclude=None):
             raise ValueError(f"exclude must be [B, E], got {tuple(exclude.shape)}")
         exclude = exclude.contiguous()
         E = exclude.shape[1]
+    if allow is None and allow_rows is not None:
+        raise ValueError("allow_rows without allow")
     lib = _lib.load()
     ws_bytes = int(lib.rb_item_topk_workspace(B, V, d, k))
     ws = torch.empty((ws_bytes,), device=seq.device, dtype=torch.uint8)
     ids = torch.empty((B, k), device=seq.device, dtype=torch.int64)
     scores = torch.empty((B, k), device=seq.device, dtype=torch.float32)
-    _launch("rb_item_topk", 2 * B * V * d, seq.data_ptr(), items.data_ptr(), B, V, d, k,
-            int(first_item), exclude.data_ptr() if E > 0 else None, E, ids.data_ptr(),
-            scores.data_ptr(), ws.data_ptr(), ws_bytes, _stream(seq), _flops=True)
+    args = (seq.data_ptr(), items.data_ptr(), B, V, d, k, int(first_item),
+            exclude.data_ptr() if E > 0 else None, E, ids.data_ptr(), scores.data_ptr(),
+            ws.data_ptr(), ws_bytes, _stream(seq))
+    if allow is None:
+        _launch("rb_item_topk", 2 * B * V * d, *args, _flops=True)
+    else:
+        _keep, extra = _allow_args(allow, allow_rows, B, V, seq.device)
+        _launch("rb_item_topk_allowed", 2 * B * V * d, *args, *extra, _flops=True)
     return ids, scores
 
 

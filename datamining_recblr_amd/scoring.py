@@ -26,7 +26,10 @@ RECBLR_CE_PIPE), ranking and scores on the fp32 pipe:
     target, from which Hit@k, MRR@k and NDCG@k follow exactly;
   * full_sort_scores: the score matrix itself when a caller needs it;
   * top_items: each row's k best items (a recommendation list), with
-    seen-item exclusion, selected inside the scoring kernel.
+    seen-item exclusion, selected inside the scoring kernel;
+  * item_filters: catalogue filters as bitmaps (ItemFilters), which top_items
+    and target_ranks take per row (allow, allow_rows): one filter word per
+    32-item tile of the sweep, ANDed into the tile's pass mask.
 
 And against chosen items only (csrc/candidates.hip: a 16-lane group per (row,
 id), no [B, C, d] gather, no sweep over the table):
@@ -50,7 +53,7 @@ from .linear import _timed
 __all__ = ["item_cross_entropy", "item_cross_entropy_rows", "full_sort_scores", "target_ranks", "rank_metrics",
            "top_items", "supported", "pair_loss", "pair_loss_reference", "shared_softmax_loss",
            "shared_softmax_reference", "candidate_scores",
-           "order_candidates", "top_candidates", "candidate_ranks"]
+           "order_candidates", "top_candidates", "candidate_ranks", "ItemFilters", "item_filters"]
 
 
 def supported(seq: torch.Tensor, table: torch.Tensor) -> bool:
@@ -595,26 +598,140 @@ def full_sort_scores(seq: torch.Tensor, table: torch.Tensor) -> torch.Tensor:
     return seq @ table.t()
 
 
+# ---- catalogue filters: allow-lists as bitmaps (include/recblr_filters.h) -----------
+class ItemFilters:
+    """F named allow-lists over a catalogue of n_items items, as bitmaps: words
+    int32 [F, ceil(n_items / 32)] contiguous, bit i of word w of row f set iff
+    filter f allows item 32 w + i (bit 31 is the sign bit), bits at or beyond
+    n_items zero.  One word is one 32-item tile of the full-sort kernels, which
+    AND it into the tile's pass mask (top_items, target_ranks; a request row
+    picks its filter with allow_rows).  Built by item_filters."""
+
+    __slots__ = ("words", "n_items")
+
+    def __init__(self, words: torch.Tensor, n_items: int):
+        n_items = int(n_items)
+        if (words.dtype != torch.int32 or words.dim() != 2 or words.shape[0] < 1
+                or n_items < 1 or words.shape[1] != (n_items + 31) // 32):
+            raise ValueError(f"words must be int32 [F >= 1, ceil({n_items} / 32)], got "
+                             f"{words.dtype} {tuple(words.shape)}")
+        self.words = words.contiguous()
+        self.n_items = n_items
+
+    @property
+    def n_filters(self) -> int:
+        return self.words.shape[0]
+
+    def to(self, device) -> "ItemFilters":
+        """The same filters on `device` (itself when already there)."""
+        words = self.words.to(device)
+        return self if words is self.words else ItemFilters(words, self.n_items)
+
+    def mask(self) -> torch.Tensor:
+        """bool [F, n_items]: True where the filter allows the item."""
+        bits = torch.arange(32, device=self.words.device, dtype=torch.int64)
+        m = (self.words.to(torch.int64)[:, :, None] >> bits) & 1
+        return m.view(self.n_filters, -1)[:, :self.n_items].bool()
+
+    def count(self) -> torch.Tensor:
+        """int64 [F]: allowed items per filter."""
+        return self.mask().sum(1)
+
+
+def item_filters(allowed, n_items: int | None = None, device=None) -> ItemFilters:
+    """Filters as data: ItemFilters from a bool tensor [F, V], a bool tensor
+    [V] (F = 1), or a sequence of F id sequences over n_items items (ids
+    outside [0, n_items) raise ValueError; duplicates are fine).  Plain torch
+    ops on the input's device; the words then move to `device`.  Rebuilding
+    one filter after a stock change is this call on one [V] mask and a copy
+    into words[f]."""
+    if isinstance(allowed, torch.Tensor):
+        if allowed.dtype != torch.bool or allowed.dim() not in (1, 2):
+            raise ValueError(f"allowed must be a bool tensor [F, V] or [V], got {allowed.dtype} "
+                             f"{tuple(allowed.shape)}")
+        mask = allowed if allowed.dim() == 2 else allowed[None]
+        if n_items is not None and int(n_items) != mask.shape[1]:
+            raise ValueError(f"n_items = {n_items} but the mask covers {mask.shape[1]} items")
+    else:
+        if n_items is None:
+            raise ValueError("id lists need n_items")
+        lists = [torch.as_tensor(ids, dtype=torch.int64).reshape(-1) for ids in allowed]
+        mask = torch.zeros((len(lists), int(n_items)), dtype=torch.bool)
+        for f, ids in enumerate(lists):
+            if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= int(n_items)):
+                raise ValueError(f"filter {f}: ids must lie in [0, {int(n_items)})")
+            mask[f, ids] = True
+    F_, V = mask.shape
+    if F_ < 1 or V < 1:
+        raise ValueError(f"need at least one filter and one item, got {tuple(mask.shape)}")
+    # bit i of a word through int64 (bit 31 set is 2^31), then wrapped into int32
+    bits = F.pad(mask, (0, -V % 32)).view(F_, -1, 32).to(torch.int64)
+    words = (bits << torch.arange(32, device=mask.device, dtype=torch.int64)).sum(-1)
+    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+    return ItemFilters(words if device is None else words.to(device), V)
+
+
+def _check_allow(allow, allow_rows, B: int, V: int, device):
+    """top_items' and target_ranks' filter arguments -> (allow on `device`,
+    allow_rows int64 [B] on `device` or None).  allow_rows is moved, not read:
+    no sync and no range check (-1: no filter; a value outside [-1, F): the row
+    selects nothing)."""
+    if allow is None:
+        if allow_rows is not None:
+            raise ValueError("allow_rows without allow")
+        return None, None
+    if not isinstance(allow, ItemFilters):
+        raise TypeError("allow must be an ItemFilters (scoring.item_filters)")
+    if allow.n_items != V:
+        raise ValueError(f"allow covers {allow.n_items} items, the table has {V}")
+    if allow_rows is not None:
+        if not isinstance(allow_rows, torch.Tensor) or allow_rows.shape != (B,):
+            raise ValueError(f"allow_rows must be [B] = [{B}], got "
+                             f"{tuple(getattr(allow_rows, 'shape', ()))}")
+        allow_rows = allow_rows.to(device=device, dtype=torch.int64)
+    return allow.to(device), allow_rows
+
+
+def _allowed_mask(allow: ItemFilters, allow_rows, B: int) -> torch.Tensor:
+    """bool [B, V]: what each row's filter allows, by the kernels' rule."""
+    mask = allow.mask()
+    if allow_rows is None:
+        return mask[:1].expand(B, -1)
+    n = allow.n_filters
+    ok = mask[allow_rows.clamp(0, n - 1)] & ((allow_rows >= 0) & (allow_rows < n))[:, None]
+    return ok | (allow_rows == -1)[:, None]
+
+
 def target_ranks(seq: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
-                 first_item: int = 1):
+                 first_item: int = 1, allow: ItemFilters | None = None,
+                 allow_rows: torch.Tensor | None = None):
     """(n_greater, n_equal) over items [first_item, V) other than the target.
 
     first_item = 1 excludes the padding item 0, as RecBole's full-sort
     evaluation does (scores[:, 0] = -inf) and as run_with_unseen.py:237 does
-    (scores[1:])."""
+    (scores[1:]).  allow / allow_rows (top_items' arguments): only the items
+    that the row's filter allows are counted, and a target that it does not
+    allow gives -1, -1, which rank_metrics drops."""
     if not supported(seq, table):
         raise kernels.RecBLRNativeError("target_ranks needs fp32 CUDA tensors with d in "
                                         f"{kernels.ITEM_DIMS}")
-    return kernels.item_rank(seq.detach(), table.detach(), target, first_item=first_item)
+    allow, allow_rows = _check_allow(allow, allow_rows, seq.shape[0], table.shape[0], seq.device)
+    if allow is None:
+        return kernels.item_rank(seq.detach(), table.detach(), target, first_item=first_item)
+    return kernels.item_rank(seq.detach(), table.detach(), target, first_item=first_item,
+                             allow=allow.words, allow_rows=allow_rows)
 
 
-def _top_items_torch(seq, table, k, first_item, exclude):
+def _top_items_torch(seq, table, k, first_item, exclude, allow=None, allow_rows=None):
     """top_items' contract in plain torch (any device, any d, any k)."""
     scores = seq.float() @ table.float().t()
     B, V = scores.shape
     dev = scores.device
     drop = torch.isnan(scores)
     drop[:, :min(max(int(first_item), 0), V)] = True
+    allow, allow_rows = _check_allow(allow, allow_rows, B, V, dev)
+    if allow is not None:
+        drop |= ~_allowed_mask(allow, allow_rows, B)
     if exclude is not None and exclude.numel() > 0:
         ex = exclude.to(device=dev, dtype=torch.int64)
         ok = (ex >= 0) & (ex < V)
@@ -639,7 +756,8 @@ def _top_items_torch(seq, table, k, first_item, exclude):
 
 @torch.no_grad()
 def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 1,
-              exclude: torch.Tensor | None = None):
+              exclude: torch.Tensor | None = None, allow: ItemFilters | None = None,
+              allow_rows: torch.Tensor | None = None):
     """Each row's k best items: (ids int64 [B, k], scores fp32 [B, k]).
 
     Selects over items in [first_item, V) not listed in exclude [B, E] (int64;
@@ -651,7 +769,17 @@ def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 
     score -inf.  On fp32 GPU tensors with d in kernels.ITEM_DIMS and k <= 64
     the selection runs inside the scoring kernel (rb_item_topk: no [B, V]
     buffer, scores bit-identical to full_sort_scores'); anything else takes a
-    plain torch path with the same contract."""
+    plain torch path with the same contract.
+
+    allow (an ItemFilters over the table's V items, from item_filters)
+    restricts the selection to a catalogue filter: "in stock", "sold in this
+    region", "on this category page".  allow_rows [B] (int64, any device; moved
+    to the GPU but never read on the host) names each row's filter: None means
+    filter 0 for every row, -1 no filter for that row (the unfiltered result,
+    bit for bit), and a value outside [-1, F) selects nothing (k times -1 /
+    -inf).  exclude, first_item and the NaN rule apply on top.  In the kernel
+    a filter costs one word load per (row, 32-item tile) and a sparse one
+    saves selection work (rb_item_topk_allowed)."""
     k = int(k)
     if k < 1:
         raise ValueError(f"k = {k} must be positive")
@@ -659,12 +787,17 @@ def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 
         raise ValueError(f"first_item = {first_item} must be >= 0")
     if exclude is not None and (exclude.dim() != 2 or exclude.shape[0] != seq.shape[0]):
         raise ValueError(f"exclude must be [B, E], got {tuple(exclude.shape)}")
+    allow, allow_rows = _check_allow(allow, allow_rows, seq.shape[0], table.shape[0], seq.device)
     if supported(seq, table) and k <= kernels.ITEM_TOPK_MAX:
         if exclude is not None:
             exclude = exclude.to(device=seq.device, dtype=torch.int64)
+        if allow is None:
+            return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
+                                     exclude=exclude)
         return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
-                                 exclude=exclude)
-    return _top_items_torch(seq.detach(), table.detach(), k, first_item, exclude)
+                                 exclude=exclude, allow=allow.words, allow_rows=allow_rows)
+    return _top_items_torch(seq.detach(), table.detach(), k, first_item, exclude, allow,
+                            allow_rows)
 
 
 # ---- candidate lists: scoring chosen items (csrc/candidates.hip) --------------------

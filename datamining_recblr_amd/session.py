@@ -953,7 +953,7 @@ def prefill(model, state: SessionState, item_seq, item_seq_len, slots=None,
 
 @torch.no_grad()
 def recommend(model, state: SessionState, items=None, slots=None, k: int = 10,
-              exclude_seen: bool = True, first_item: int = 1):
+              exclude_seen: bool = True, first_item: int = 1, allow=None, allow_rows=None):
     """Click in, recommendation list out: ``(ids int64 [B, k], scores fp32
     [B, k])``, each row's k best items by ``scoring.top_items`` for its slot's
     seq_output after the call's events.
@@ -971,12 +971,17 @@ def recommend(model, state: SessionState, items=None, slots=None, k: int = 10,
     -inf in every position (masked on the device, no sync).  slots, the
     refusals and the fallbacks are ``step``'s; a state on the CPU runs the
     whole call in torch ops.  ``state.status`` is left as the step or append
-    left it."""
+    left it.
+
+    allow (``scoring.item_filters``) and allow_rows [B] restrict each row to a
+    catalogue filter, as ``scoring.top_items`` takes them: the row's filter
+    index, None for filter 0 everywhere, -1 for no filter."""
     from .scoring import top_items
 
     p, y, seen, dead = _serve_rows(model, state, items, slots, exclude_seen, "recommend")
     ids, scores = top_items(y, p.t["item_embedding.weight"], k, first_item,
-                            exclude=seen if exclude_seen else None)
+                            exclude=seen if exclude_seen else None, allow=allow,
+                            allow_rows=allow_rows)
     ids.masked_fill_(dead[:, None], -1)
     scores.masked_fill_(dead[:, None], float("-inf"))
     return ids, scores
