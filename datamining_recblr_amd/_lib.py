@@ -103,6 +103,9 @@ CANDIDATE_SIGNATURES = parse_header(_read(os.path.join(os.path.dirname(HEADER_PA
 # catalogue filters (include/recblr_filters.h): likewise
 FILTER_SIGNATURES = parse_header(_read(os.path.join(os.path.dirname(HEADER_PATH),
                                                     "recblr_filters.h")))
+# diversity caps (include/recblr_groups.h): likewise
+GROUP_SIGNATURES = parse_header(_read(os.path.join(os.path.dirname(HEADER_PATH),
+                                                   "recblr_groups.h")))
 # the experimental library (experimental/recblr_exp.h: opt-in kernels that
 # measured slower than the default path; never loaded unless requested)
 EXP_SIGNATURES = parse_header(_read(os.path.join(_HERE, "experimental", "recblr_exp.h")))
@@ -145,7 +148,7 @@ def load(path: str | None = None) -> ctypes.CDLL:
     explicit path is loaded afresh and not cached."""
     return _load(path or LIB_PATH,
                  {**SIGNATURES, **DENSE_SIGNATURES, **PAIR_SIGNATURES, **CANDIDATE_SIGNATURES,
-                  **FILTER_SIGNATURES},
+                  **FILTER_SIGNATURES, **GROUP_SIGNATURES},
                  "HIP extension not built",
                  "rb_version",
                  "ABI mismatch: library {} vs binding {}; rebuild", cache=path is None,

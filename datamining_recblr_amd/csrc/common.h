@@ -13,6 +13,7 @@
 #include "../../include/recblr_pairs.h"
 #include "../../include/recblr_candidates.h"
 #include "../../include/recblr_filters.h"
+#include "../../include/recblr_groups.h"
 
 namespace rb {
 
@@ -572,6 +573,15 @@ int launch_item_topk_allowed(const float* E, const float* W, int64_t B, int64_t 
                              int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
                              const int* allow, int64_t F, int64_t words,
                              const int64_t* allow_rows, hipStream_t st);
+// launch_item_topk with at most m items of a group per list (include/recblr_groups.h);
+// allow null: no filter
+int64_t item_topk_grouped_workspace_bytes(int64_t B, int64_t V, int64_t k);
+int launch_item_topk_grouped(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
+                             int64_t k, int64_t first, const int64_t* ex, int64_t NE,
+                             int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
+                             const int* allow, int64_t F, int64_t words,
+                             const int64_t* allow_rows, const int* groups, int64_t m,
+                             hipStream_t st);
 int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, const float* lse,
                          const float* dloss, int64_t B, int64_t V, int64_t D, int64_t v_off,
                          float* out, int64_t ld, hipStream_t st);

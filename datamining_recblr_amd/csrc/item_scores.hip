@@ -736,14 +736,36 @@ __device__ __forceinline__ bool beats(float s, int id, float s2, int id2) {
 // one AND into the pass mask per tile, ahead of the admission loop: an item the
 // filter drops is never a candidate, and a sparse filter shortens the loop.
 // The word is read one tile ahead of its use.
-template <int D, int KP, bool kAllow>
+//
+// kGroup (include/recblr_groups.h): at most gr.m entries of one group in a
+// list.  Every entry carries its group (16 bits in LDS, kNoGroup for an
+// uncapped item and for an empty slot), and the list stays the k best of U =
+// each group's m best items seen so far plus every uncapped item.  A candidate
+// that passes the threshold and whose group already holds m entries replaces
+// that group's worst entry if it beats it (also while the list has empty
+// slots), else it is dropped; any other candidate replaces the list's worst as
+// before.  The group's count and worst come from one scan of the k entries.
+// Replacing an entry that is not the list's worst leaves the threshold as it
+// is (the newcomer beats an entry that the worst does not beat), so only a
+// replaced worst is followed by the rescan.  A tile's 32 group ids are read
+// one per lane, one tile ahead, and a candidate's id is fetched by shuffle.
+constexpr int kNoGroup = 0xffff;
+
+struct GroupArgs {
+  const int* ids;   // [V], -1 (uncapped) or a group in [0, RB_GROUP_ID_MAX]
+  int m;
+};
+
+template <int D, int KP, bool kAllow, bool kGroup = false>
 __device__ __forceinline__ void item_topk(const float* __restrict__ E,
                                           const float* __restrict__ W, int64_t B, int64_t V,
                                           int64_t first, int k, const int64_t* __restrict__ ex,
                                           int64_t NE, int64_t per, int64_t RB, int64_t NS,
                                           float* __restrict__ c_sc, int* __restrict__ c_id,
                                           float* l_sc, int* l_id, unsigned* l_ex,
-                                          const AllowArgs& al) {
+                                          const AllowArgs& al, int* __restrict__ c_g = nullptr,
+                                          unsigned short* l_g = nullptr,
+                                          const GroupArgs& gr = GroupArgs{}) {
   constexpr int KH = D / 2, NR = kWaves * kTile, XW = kExBits / 32;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
   Place pl;
@@ -761,6 +783,7 @@ __device__ __forceinline__ void item_topk(const float* __restrict__ E,
     for (int i = 0; i < k; ++i) {
       l_sc[i * NR + row] = -INFINITY;
       l_id[i * NR + row] = kNoItem;
+      if constexpr (kGroup) l_g[i * NR + row] = kNoGroup;
     }
   }
   if (NE > 0) {
@@ -787,11 +810,36 @@ __device__ __forceinline__ void item_topk(const float* __restrict__ E,
       if (exr[e] == (int64_t)id) return true;
     return false;
   };
-  auto try_insert = [&](float s, int id) {   // h = 0 lanes only
+  auto try_insert = [&](float s, int id, int g) {   // h = 0 lanes only
     if (!beats(s, id, thr, thr_id)) return;
     if (NE > 0 && excluded(id)) return;
-    l_sc[thr_pos * NR + row] = s;
-    l_id[thr_pos * NR + row] = id;
+    int pos = thr_pos;
+    if constexpr (kGroup) {
+      if (g != kNoGroup) {
+        int cnt = 0, gi = 0;   // the group's entries and the worst of them
+        float gs = 0.0f;
+        for (int i = 0; i < k; ++i) {
+          const float a = l_sc[i * NR + row];
+          const int c = l_id[i * NR + row];
+          if (l_g[i * NR + row] == g) {
+            if (cnt == 0 || beats(gs, gi, a, c)) {
+              gs = a;
+              gi = c;
+              pos = i;
+            }
+            ++cnt;
+          }
+        }
+        if (cnt < gr.m) pos = thr_pos;
+        else if (!beats(s, id, gs, gi)) return;
+      }
+      l_g[pos * NR + row] = (unsigned short)g;
+    }
+    l_sc[pos * NR + row] = s;
+    l_id[pos * NR + row] = id;
+    if constexpr (kGroup) {
+      if (pos != thr_pos) return;
+    }
     float ws = s;
     int wi = id, wp = thr_pos;
     for (int i = 0; i < k; ++i) {
@@ -809,6 +857,12 @@ __device__ __forceinline__ void item_topk(const float* __restrict__ E,
   };
   const AllowRow ar(al, kAllow ? bc : 0);
   unsigned aw = kAllow ? ar.word(pl.split * per) : 0u;   // the next tile's word
+  // group of item 32 t + j, clamped for the load (an item at or beyond V is no candidate)
+  auto tile_group = [&](int64_t t) -> int {
+    return gr.ids[max<int64_t>(0, min<int64_t>(t * kTile + j, V - 1))] & kNoGroup;
+  };
+  int gw = 0;   // the next tile's groups
+  if constexpr (kGroup) gw = tile_group(pl.split * per);
   stream_tiles<D, false>(W, V, per, pl.split, nullptr, nullptr,
                          [&](int64_t t, const float* tile, const float*, const int64_t*) {
     const int64_t v0 = t * kTile;
@@ -816,6 +870,11 @@ __device__ __forceinline__ void item_topk(const float* __restrict__ E,
     if constexpr (kAllow) {
       am = lane_bits(aw, h);
       aw = ar.word(t + 1);
+    }
+    int gt = 0;
+    if constexpr (kGroup) {
+      gt = gw;
+      gw = tile_group(t + 1);
     }
     const f32x16 x = lds_dot<D, KH, true>(tile, j, h, eb);
     const int lo = rel32(first, v0), hi = rel32(V, v0);
@@ -838,9 +897,14 @@ __device__ __forceinline__ void item_topk(const float* __restrict__ E,
       const float s1 = __shfl_xor(cs, 32);
       const int id1 = __shfl_xor(cid, 32);
       const int p1 = __shfl_xor((int)p, 32);
+      int cg = 0, g1 = 0;
+      if constexpr (kGroup) {
+        cg = __shfl(gt, crow(r, h));
+        g1 = __shfl_xor(cg, 32);
+      }
       if (h == 0) {
-        if (p) try_insert(cs, cid);
-        if (p1) try_insert(s1, id1);
+        if (p) try_insert(cs, cid, cg);
+        if (p1) try_insert(s1, id1, g1);
       }
       thr = __shfl(thr, j);
     }
@@ -850,6 +914,10 @@ __device__ __forceinline__ void item_topk(const float* __restrict__ E,
     for (int i = 0; i < k; ++i) {
       c_sc[o + i] = l_sc[i * NR + row];
       c_id[o + i] = l_id[i * NR + row];
+      if constexpr (kGroup) {
+        const int g = l_g[i * NR + row];
+        c_g[o + i] = g == kNoGroup ? -1 : g;
+      }
     }
   }
 }
@@ -884,6 +952,21 @@ __global__ __launch_bounds__(256) void k_item_topk_allowed(
   TOPK_LDS;
   item_topk<D, KP, true>(E, W, B, V, first, k, ex, NE, per, RB, NS, c_sc, c_id, l_sc, l_id, l_ex,
                          al);
+}
+
+// The capped lists: one more LDS array (a 16-bit group per entry: 16 KB at
+// KP = 64, where int32 would not fit beside D = 256's stream buffers) and one
+// more workspace array (the entries' groups as int32, -1 for none).
+template <int D, int KP, bool kAllow>
+__global__ __launch_bounds__(256) void k_item_topk_grouped(
+    const float* __restrict__ E, const float* __restrict__ W, int64_t B, int64_t V, int64_t first,
+    int k, const int64_t* __restrict__ ex, int64_t NE, int64_t per, int64_t RB, int64_t NS,
+    float* __restrict__ c_sc, int* __restrict__ c_id, int* __restrict__ c_g, AllowArgs al,
+    GroupArgs gr) {
+  TOPK_LDS;
+  __shared__ unsigned short l_g[KP * kWaves * kTile];
+  item_topk<D, KP, kAllow, true>(E, W, B, V, first, k, ex, NE, per, RB, NS, c_sc, c_id, l_sc, l_id,
+                                 l_ex, al, c_g, l_g, gr);
 }
 
 // One wave per row: the row's S lists of k candidates (all ids distinct: the
@@ -930,6 +1013,73 @@ __global__ __launch_bounds__(256) void k_topk_rows(const float* __restrict__ c_s
     if (lane == t) {
       my_s = bs;
       my_id = bid;
+    }
+  }
+  if (lane < k) {
+    ids[b * k + lane] = my_id == kNoItem ? -1 : (int64_t)my_id;
+    scores[b * k + lane] = my_s;
+  }
+}
+
+// k_topk_rows under the cap: the walk over the row's S k candidates in order
+// that takes a candidate unless m of its group were taken.  Still k turns: pick
+// t's group sits on lane t, its count among the picks is a ballot, and when a
+// pick fills its group the next turn's scan retires that group's remaining
+// candidates in the row's own workspace slice (they become empty slots; a lane
+// re-reads only what it wrote itself), so a full group never costs a turn.  At
+// most one group fills per turn.  Group -1 is never counted.
+__global__ __launch_bounds__(256) void k_topk_rows_grouped(float* __restrict__ c_sc,
+                                                           int* __restrict__ c_id,
+                                                           const int* __restrict__ c_g, int64_t S,
+                                                           int64_t B, int k, int m,
+                                                           int64_t* __restrict__ ids,
+                                                           float* __restrict__ scores) {
+  const int lane = threadIdx.x & 63;
+  const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  const int64_t n = S * k;
+  float ps = INFINITY, my_s = -INFINITY;
+  int pid = -1, my_id = kNoItem, my_g = -1;
+  int full = -2;   // the group that the previous pick filled (-2: none)
+  for (int t = 0; t < k; ++t) {
+    float bs = -INFINITY;
+    int bid = kNoItem, bg = -1;
+    if (pid != kNoItem) {
+      for (int64_t c = lane; c < n; c += 64) {
+        const int64_t sp = c / k, i = c - sp * k, at = (sp * B + b) * k + i;
+        const float s = c_sc[at];
+        const int id = c_id[at];
+        const int g = c_g[at];
+        if (g == full) {
+          c_sc[at] = -INFINITY;
+          c_id[at] = kNoItem;
+        } else if (beats(ps, pid, s, id) && beats(s, id, bs, bid)) {
+          bs = s;
+          bid = id;
+          bg = g;
+        }
+      }
+#pragma unroll
+      for (int sh = 32; sh >= 1; sh >>= 1) {
+        const float os = __shfl_xor(bs, sh);
+        const int oid = __shfl_xor(bid, sh);
+        const int og = __shfl_xor(bg, sh);
+        if (beats(os, oid, bs, bid)) {
+          bs = os;
+          bid = oid;
+          bg = og;
+        }
+      }
+    }
+    ps = bs;
+    pid = bid;
+    const bool taken = bid != kNoItem && bg >= 0;
+    const int same = __builtin_popcountll(__builtin_amdgcn_ballot_w64(lane < t && my_g == bg));
+    full = taken && same + 1 >= m ? bg : -2;
+    if (lane == t) {
+      my_s = bs;
+      my_id = bid;
+      my_g = taken ? bg : -1;
     }
   }
   if (lane < k) {
@@ -1389,15 +1539,17 @@ RankWs rank_layout(int64_t B, int64_t V) {
 }
 
 struct TopkWs {
-  size_t sc, id, total;
+  size_t sc, id, g, total;
 };
 
-TopkWs topk_layout(int64_t B, int64_t V, int64_t k) {
+// grouped: the third array (each entry's group) of rb_item_topk_grouped
+TopkWs topk_layout(int64_t B, int64_t V, int64_t k, bool grouped = false) {
   const Grid2 f = plan(B, ntiles(V));
   TopkWs o{};
   WsCursor c;
   o.sc = c.take(f.splits * B * k * 4);
   o.id = c.take(f.splits * B * k * 4);
+  if (grouped) o.g = c.take(f.splits * B * k * 4);
   o.total = c.off;
   return o;
 }
@@ -1568,18 +1720,39 @@ int64_t item_topk_workspace_bytes(int64_t B, int64_t V, int64_t k) {
   return (int64_t)topk_layout(B, V, k).total;
 }
 
+int64_t item_topk_grouped_workspace_bytes(int64_t B, int64_t V, int64_t k) {
+  return (int64_t)topk_layout(B, V, k, true).total;
+}
+
 namespace {
-// rb_item_topk (al null) and rb_item_topk_allowed: one workspace, one plan
+// rb_item_topk (al null), rb_item_topk_allowed and rb_item_topk_grouped (gr
+// given, al or not): one plan, and one workspace but for the grouped third array
 int item_topk_launch(const char* fn, const float* E, const float* W, int64_t B, int64_t V,
                      int64_t D, int64_t k, int64_t first, const int64_t* ex, int64_t NE,
                      int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
-                     const AllowArgs* al, hipStream_t st) {
-  const TopkWs L = topk_layout(B, V, k);
+                     const AllowArgs* al, hipStream_t st, const GroupArgs* gr = nullptr) {
+  const TopkWs L = topk_layout(B, V, k, gr != nullptr);
   if (ws_bytes < (int64_t)L.total) return fail((std::string(fn) + ": workspace too small").c_str());
   char* w = static_cast<char*>(ws);
   float* sc = reinterpret_cast<float*>(w + L.sc);
   int* id = reinterpret_cast<int*>(w + L.id);
   const Grid2 g = plan(B, ntiles(V));
+  if (gr) {
+    int* cg = reinterpret_cast<int*>(w + L.g);
+    if (int rc = for_item_dim(D, [&](auto dc) {
+          const auto kernel =
+              al ? (k <= 32 ? k_item_topk_grouped<dc, 32, true> : k_item_topk_grouped<dc, 64, true>)
+                 : (k <= 32 ? k_item_topk_grouped<dc, 32, false>
+                            : k_item_topk_grouped<dc, 64, false>);
+          hipLaunchKernelGGL(kernel, dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, (int)k,
+                             ex, NE, g.per, g.blocks, g.splits, sc, id, cg,
+                             al ? *al : AllowArgs{}, *gr);
+        }))
+      return rc;
+    hipLaunchKernelGGL(k_topk_rows_grouped, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, sc,
+                       id, cg, g.splits, B, (int)k, gr->m, ids, scores);
+    return launch_status(fn);
+  }
   if (int rc = for_item_dim(D, [&](auto dc) {
         // the candidate list's LDS capacity per (row, split)
         if (al) {
@@ -1614,6 +1787,19 @@ int launch_item_topk_allowed(const float* E, const float* W, int64_t B, int64_t 
   const AllowArgs al{allow, F, words, allow_rows};
   return item_topk_launch("rb_item_topk_allowed", E, W, B, V, D, k, first, ex, NE, ids, scores,
                           ws, ws_bytes, &al, st);
+}
+
+int launch_item_topk_grouped(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
+                             int64_t k, int64_t first, const int64_t* ex, int64_t NE,
+                             int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
+                             const int* allow, int64_t F, int64_t words,
+                             const int64_t* allow_rows, const int* groups, int64_t m,
+                             hipStream_t st) {
+  const AllowArgs al{allow, F, words, allow_rows};
+  // a cap of k or more never binds: clamp it into the kernel's int
+  const GroupArgs gr{groups, (int)std::min<int64_t>(m, k)};
+  return item_topk_launch("rb_item_topk_grouped", E, W, B, V, D, k, first, ex, NE, ids, scores,
+                          ws, ws_bytes, allow ? &al : nullptr, st, &gr);
 }
 
 int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, const float* lse,

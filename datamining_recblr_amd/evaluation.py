@@ -113,7 +113,8 @@ def full_sort_metrics(model, batches, topk=(10, 20), allow=None, allow_rows_key=
 
 @torch.no_grad()
 def recommend(model, item_id_lists, k: int = 10, batch_size: int = 1024,
-              exclude_seen: bool = True, device=None, allow=None, allow_rows=None):
+              exclude_seen: bool = True, device=None, allow=None, allow_rows=None,
+              groups=None, max_per_group=None):
     """Each user's k best items from their input id sequence.
 
     item_id_lists: per-user id sequences (ints in [0, n_items)), batched by
@@ -128,8 +129,14 @@ def recommend(model, item_id_lists, k: int = 10, batch_size: int = 1024,
     allow (scoring.item_filters) restricts every list to a catalogue filter;
     allow_rows [n] names each user's filter in the callers' order (None:
     filter 0 for everyone, -1: no filter for that user) and follows the users
-    through the length sort."""
+    through the length sort.  groups (scoring.item_groups) and max_per_group
+    cap every list at that many items of one group; the groups are per item,
+    so the length sort does not touch them."""
     device = device or next(model.parameters()).device
+    if (groups is None) != (max_per_group is None):
+        raise ValueError("groups and max_per_group are given together or not at all")
+    if groups is not None:
+        groups = groups.to(device)
     if allow_rows is not None:
         if allow is None:
             raise ValueError("allow_rows without allow")
@@ -159,7 +166,8 @@ def recommend(model, item_id_lists, k: int = 10, batch_size: int = 1024,
             out = model.forward(seq, lens[idx].to(device), exact_lengths=True)
             i, sc = top_items(out, table, k, first_item=1, exclude=seq if exclude_seen else None,
                               allow=allow,
-                              allow_rows=allow_rows[idx] if allow_rows is not None else None)
+                              allow_rows=allow_rows[idx] if allow_rows is not None else None,
+                              groups=groups, max_per_group=max_per_group)
             ids[idx] = i.cpu()
             scores[idx] = sc.cpu()
     finally:

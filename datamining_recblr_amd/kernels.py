@@ -696,7 +696,7 @@ def embedding_plan(idx, num_rows, d, stream=None):
 # MFMA roofline).
 FLOP_KERNELS = frozenset({"rb_item_ce_fwd", "rb_item_ce_bwd", "rb_item_ce_probs", "rb_item_rank",
                           "rb_item_scores", "rb_item_topk", "rb_item_ce_fwd_h", "rb_item_ce_probs_h",
-                          "rb_item_rank_allowed", "rb_item_topk_allowed",
+                          "rb_item_rank_allowed", "rb_item_topk_allowed", "rb_item_topk_grouped",
                           "rb_item_ce_probs_h_t", "rb_item_ce_probs_h_both",
                           "rb_item_ce_fwd_h_rows", "rb_item_ce_probs_h_rows",
                           "rb_item_ce_probs_h_both_rows"})
@@ -1048,16 +1048,23 @@ def item_rank(seq, items, target, first_item=1, want_equal=True, allow=None, all
 
 
 ITEM_TOPK_MAX = 64
+# the largest group id of item_topk's groups (RB_GROUP_ID_MAX of
+# include/recblr_groups.h): a list entry's group is 16 bits of LDS
+ITEM_GROUP_ID_MAX = 65534
 
 
-def item_topk(seq, items, k, first_item=1, exclude=None, allow=None, allow_rows=None):
+def item_topk(seq, items, k, first_item=1, exclude=None, allow=None, allow_rows=None,
+              groups=None, max_per_group=None):
     """(ids int64 [B, k], scores fp32 [B, k]): each row's k best items in
     [first_item, V) not listed in exclude [B, E] (int64; entries outside
     [0, V) ignored), by (score descending, id ascending), scores bit-identical
     to item_scores'; id -1 / score -inf where fewer than k are selectable.
     No [B, V] buffer (rb_item_topk).  allow / allow_rows: per-row
     allow-bitmaps (_allow_args, rb_item_topk_allowed) — the selection runs
-    over the items that the row's filter allows."""
+    over the items that the row's filter allows.  groups int32 [V] (values in
+    [-1, ITEM_GROUP_ID_MAX], not read here) with max_per_group >= 1: the walk
+    in that order takes an item unless max_per_group of its group were taken
+    (-1: never capped), with or without a filter (rb_item_topk_grouped)."""
     seq, items, _ = _item_operands(seq, items)
     B, d = seq.shape
     V = items.shape[0]
@@ -1073,15 +1080,32 @@ def item_topk(seq, items, k, first_item=1, exclude=None, allow=None, allow_rows=
         E = exclude.shape[1]
     if allow is None and allow_rows is not None:
         raise ValueError("allow_rows without allow")
+    if (groups is None) != (max_per_group is None):
+        raise ValueError("groups and max_per_group go together")
+    if groups is not None:
+        _check(groups, "groups", dtype=torch.int32)
+        if groups.shape != (V,) or groups.device != seq.device:
+            raise ValueError(f"groups must be int32 [{V}] on the same device, got "
+                             f"{tuple(groups.shape)}")
+        groups = groups.contiguous()
+        if int(max_per_group) < 1:
+            raise ValueError(f"max_per_group = {max_per_group} must be >= 1")
     lib = _lib.load()
-    ws_bytes = int(lib.rb_item_topk_workspace(B, V, d, k))
+    ws_fn = lib.rb_item_topk_workspace if groups is None else lib.rb_item_topk_grouped_workspace
+    ws_bytes = int(ws_fn(B, V, d, k))
     ws = torch.empty((ws_bytes,), device=seq.device, dtype=torch.uint8)
     ids = torch.empty((B, k), device=seq.device, dtype=torch.int64)
     scores = torch.empty((B, k), device=seq.device, dtype=torch.float32)
     args = (seq.data_ptr(), items.data_ptr(), B, V, d, k, int(first_item),
             exclude.data_ptr() if E > 0 else None, E, ids.data_ptr(), scores.data_ptr(),
             ws.data_ptr(), ws_bytes, _stream(seq))
-    if allow is None:
+    if groups is not None:
+        extra = (None, 0, 0, None)
+        if allow is not None:
+            _keep, extra = _allow_args(allow, allow_rows, B, V, seq.device)
+        _launch("rb_item_topk_grouped", 2 * B * V * d, *args, *extra, groups.data_ptr(),
+                int(max_per_group), _flops=True)
+    elif allow is None:
         _launch("rb_item_topk", 2 * B * V * d, *args, _flops=True)
     else:
         _keep, extra = _allow_args(allow, allow_rows, B, V, seq.device)

@@ -703,18 +703,20 @@ class RecBLR(SequentialRecommender):
 
     @torch.no_grad()
     def full_sort_topk(self, interaction, k: int = 10, exclude_seen: bool = True,
-                       first_item: int = 1, allow=None, allow_rows=None):
+                       first_item: int = 1, allow=None, allow_rows=None, groups=None,
+                       max_per_group=None):
         """(ids, scores) [B, k]: each row's k best items under
         full_sort_predict's scores (RecBLR.py:114-122) without materialising
         them, by (score descending, id ascending) over items [first_item,
         n_items); exclude_seen drops the row's own ITEM_SEQ entries.  allow /
         allow_rows: a catalogue filter per row (scoring.item_filters,
-        scoring.top_items)."""
+        scoring.top_items).  groups / max_per_group: at most that many items
+        of one group in a list (scoring.item_groups, scoring.top_items)."""
         item_seq = interaction[self.ITEM_SEQ]
         seq_output = self.forward(item_seq, interaction[self.ITEM_SEQ_LEN])
         return top_items(seq_output, self.item_embedding.weight, k, first_item=first_item,
                          exclude=item_seq if exclude_seen else None, allow=allow,
-                         allow_rows=allow_rows)
+                         allow_rows=allow_rows, groups=groups, max_per_group=max_per_group)
 
     # ---- candidate lists (scoring.candidate_scores / top_candidates) ----------
     def predict_candidates(self, interaction, candidates):
@@ -786,15 +788,16 @@ class RecBLR(SequentialRecommender):
 
     def session_recommend(self, state, items=None, slots=None, k: int = 10,
                           exclude_seen: bool = True, first_item: int = 1, allow=None,
-                          allow_rows=None):
+                          allow_rows=None, groups=None, max_per_group=None):
         """(ids, scores) [B, k]: the rows' k best items after one step (items
         [B]) or append (items [B, W]), or from the slots' stored outputs (items
         None), the slots' own last S item ids excluded (session.recommend).
-        allow / allow_rows: a catalogue filter per row (scoring.item_filters)."""
+        allow / allow_rows: a catalogue filter per row (scoring.item_filters);
+        groups / max_per_group: a cap per group (scoring.item_groups)."""
         from .session import recommend
 
         return recommend(self, state, items, slots, k, exclude_seen, first_item, allow=allow,
-                         allow_rows=allow_rows)
+                         allow_rows=allow_rows, groups=groups, max_per_group=max_per_group)
 
     def session_rerank(self, state, candidates, items=None, slots=None, k: int = 10,
                        exclude_seen: bool = False, first_item: int = 1):

@@ -53,7 +53,8 @@ from .linear import _timed
 __all__ = ["item_cross_entropy", "item_cross_entropy_rows", "full_sort_scores", "target_ranks", "rank_metrics",
            "top_items", "supported", "pair_loss", "pair_loss_reference", "shared_softmax_loss",
            "shared_softmax_reference", "candidate_scores",
-           "order_candidates", "top_candidates", "candidate_ranks", "ItemFilters", "item_filters"]
+           "order_candidates", "top_candidates", "candidate_ranks", "ItemFilters", "item_filters",
+           "ItemGroups", "item_groups"]
 
 
 def supported(seq: torch.Tensor, table: torch.Tensor) -> bool:
@@ -702,6 +703,60 @@ def _allowed_mask(allow: ItemFilters, allow_rows, B: int) -> torch.Tensor:
     return ok | (allow_rows == -1)[:, None]
 
 
+# ---- diversity caps: one group id per item (include/recblr_groups.h) ----------------
+class ItemGroups:
+    """One group id per catalogue item (brand, seller, category, series) for
+    top_items' cap "at most max_per_group items of a group in a list": ids int32
+    [n_items] contiguous, -1 for an item that is never capped.  n_groups is the
+    largest id + 1.  Built by item_groups."""
+
+    __slots__ = ("ids", "n_items", "n_groups")
+
+    def __init__(self, ids: torch.Tensor, n_groups: int):
+        if ids.dtype != torch.int32 or ids.dim() != 1 or ids.shape[0] < 1:
+            raise ValueError(f"ids must be int32 [V >= 1], got {ids.dtype} {tuple(ids.shape)}")
+        self.ids = ids.contiguous()
+        self.n_items = ids.shape[0]
+        self.n_groups = int(n_groups)
+
+    def to(self, device) -> "ItemGroups":
+        """The same groups on `device` (itself when already there)."""
+        ids = self.ids.to(device)
+        return self if ids is self.ids else ItemGroups(ids, self.n_groups)
+
+
+def item_groups(group_of_item, device=None) -> ItemGroups:
+    """ItemGroups from an integer tensor or sequence [V]: item v's group id, -1
+    for an item that no cap applies to.  A value below -1 (or one that does not
+    fit int32) raises ValueError.  The ids then move to `device`."""
+    ids = torch.as_tensor(group_of_item)
+    if ids.dim() != 1 or ids.numel() < 1 or ids.dtype.is_floating_point or ids.dtype in (
+            torch.bool, torch.complex64, torch.complex128):
+        raise ValueError(f"group_of_item must be an integer [V >= 1], got {ids.dtype} "
+                         f"{tuple(ids.shape)}")
+    lo, hi = int(ids.min()), int(ids.max())
+    if lo < -1 or hi >= 2 ** 31 - 1:
+        raise ValueError(f"group ids must lie in [-1, 2^31 - 1), got [{lo}, {hi}]")
+    ids = ids.to(torch.int32)
+    return ItemGroups(ids if device is None else ids.to(device), hi + 1)
+
+
+def _check_groups(groups, max_per_group, V: int, device):
+    """top_items' cap arguments -> (groups on `device` or None, m)."""
+    if (groups is None) != (max_per_group is None):
+        raise ValueError("groups and max_per_group are given together or not at all")
+    if groups is None:
+        return None, None
+    if not isinstance(groups, ItemGroups):
+        raise TypeError("groups must be an ItemGroups (scoring.item_groups)")
+    if groups.n_items != V:
+        raise ValueError(f"groups covers {groups.n_items} items, the table has {V}")
+    m = int(max_per_group)
+    if m < 1:
+        raise ValueError(f"max_per_group = {max_per_group} must be >= 1")
+    return groups.to(device), m
+
+
 def target_ranks(seq: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
                  first_item: int = 1, allow: ItemFilters | None = None,
                  allow_rows: torch.Tensor | None = None):
@@ -722,8 +777,9 @@ def target_ranks(seq: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
                              allow=allow.words, allow_rows=allow_rows)
 
 
-def _top_items_torch(seq, table, k, first_item, exclude, allow=None, allow_rows=None):
-    """top_items' contract in plain torch (any device, any d, any k)."""
+def _top_items_torch(seq, table, k, first_item, exclude, allow=None, allow_rows=None,
+                     groups=None, max_per_group=None):
+    """top_items' contract in plain torch (any device, any d, any k, any group id)."""
     scores = seq.float() @ table.float().t()
     B, V = scores.shape
     dev = scores.device
@@ -745,6 +801,22 @@ def _top_items_torch(seq, table, k, first_item, exclude, allow=None, allow_rows=
     back = torch.sort(drop.gather(1, order).to(torch.int8), dim=1, stable=True).indices
     order = order.gather(1, back)
     n_ok = (~drop).sum(1, keepdim=True)
+    groups, m = _check_groups(groups, max_per_group, V, dev)
+    if groups is not None:
+        # the cap as a segmented count: a stable sort of the ordered items by
+        # group keeps each group's run in walk order, so an item's place in its
+        # run is the number of its group walked before it (the dropped columns
+        # stand behind every selectable one and disturb no count)
+        g = groups.ids.to(torch.int64)[order]
+        by = torch.sort(g, dim=1, stable=True)
+        pos = torch.arange(V, device=dev)[None, :].expand(B, -1)
+        head = torch.ones_like(drop)
+        head[:, 1:] = by.values[:, 1:] != by.values[:, :-1]
+        seen = pos - torch.where(head, pos, torch.zeros_like(pos)).cummax(1).values
+        seen = torch.empty_like(seen).scatter_(1, by.indices, seen)
+        keep = (pos < n_ok) & ((g < 0) | (seen < m))
+        order = order.gather(1, torch.sort((~keep).to(torch.int8), dim=1, stable=True).indices)
+        n_ok = keep.sum(1, keepdim=True)
     kk = min(k, V)
     ids = torch.full((B, k), -1, dtype=torch.int64, device=dev)
     out = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
@@ -757,7 +829,8 @@ def _top_items_torch(seq, table, k, first_item, exclude, allow=None, allow_rows=
 @torch.no_grad()
 def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 1,
               exclude: torch.Tensor | None = None, allow: ItemFilters | None = None,
-              allow_rows: torch.Tensor | None = None):
+              allow_rows: torch.Tensor | None = None, groups: ItemGroups | None = None,
+              max_per_group: int | None = None):
     """Each row's k best items: (ids int64 [B, k], scores fp32 [B, k]).
 
     Selects over items in [first_item, V) not listed in exclude [B, E] (int64;
@@ -779,7 +852,18 @@ def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 
     bit for bit), and a value outside [-1, F) selects nothing (k times -1 /
     -inf).  exclude, first_item and the NaN rule apply on top.  In the kernel
     a filter costs one word load per (row, 32-item tile) and a sparse one
-    saves selection work (rb_item_topk_allowed)."""
+    saves selection work (rb_item_topk_allowed).
+
+    groups (an ItemGroups over the table's V items, from item_groups) with
+    max_per_group = m >= 1, given together, cap a list's diversity: at most m
+    items of one brand, seller, category or series.  The result is that of a
+    walk over the row's selectable items (all the rules above) in the order
+    above that takes an item unless m of its group were taken, and stops after
+    k; an item of group -1 is never capped; where fewer than k are taken the
+    tail is id -1 / score -inf.  The selection kernel applies the cap in its
+    own sweep (rb_item_topk_grouped, exact: no depth to guess); m >= k, or
+    groups that are all distinct or all -1, give the uncapped result bit for
+    bit.  A group id above kernels.ITEM_GROUP_ID_MAX takes the torch path."""
     k = int(k)
     if k < 1:
         raise ValueError(f"k = {k} must be positive")
@@ -788,16 +872,23 @@ def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 
     if exclude is not None and (exclude.dim() != 2 or exclude.shape[0] != seq.shape[0]):
         raise ValueError(f"exclude must be [B, E], got {tuple(exclude.shape)}")
     allow, allow_rows = _check_allow(allow, allow_rows, seq.shape[0], table.shape[0], seq.device)
-    if supported(seq, table) and k <= kernels.ITEM_TOPK_MAX:
+    groups, m = _check_groups(groups, max_per_group, table.shape[0], seq.device)
+    if supported(seq, table) and k <= kernels.ITEM_TOPK_MAX and (
+            groups is None or groups.n_groups <= kernels.ITEM_GROUP_ID_MAX + 1):
         if exclude is not None:
             exclude = exclude.to(device=seq.device, dtype=torch.int64)
+        if groups is not None:
+            return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
+                                     exclude=exclude,
+                                     allow=allow.words if allow is not None else None,
+                                     allow_rows=allow_rows, groups=groups.ids, max_per_group=m)
         if allow is None:
             return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
                                      exclude=exclude)
         return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
                                  exclude=exclude, allow=allow.words, allow_rows=allow_rows)
     return _top_items_torch(seq.detach(), table.detach(), k, first_item, exclude, allow,
-                            allow_rows)
+                            allow_rows, groups, m)
 
 
 # ---- candidate lists: scoring chosen items (csrc/candidates.hip) --------------------

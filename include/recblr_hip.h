@@ -75,7 +75,7 @@ typedef uint16_t rb_bf16;
 #define RB_TILE 16
 
 /* ABI version; bumped on any signature change.  rb_version() returns it. */
-#define RB_ABI_VERSION 52
+#define RB_ABI_VERSION 53
 int rb_version(void);
 
 /* Human-readable description of the last error on the calling thread. */
