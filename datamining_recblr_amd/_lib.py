@@ -106,6 +106,9 @@ FILTER_SIGNATURES = parse_header(_read(os.path.join(os.path.dirname(HEADER_PATH)
 # diversity caps (include/recblr_groups.h): likewise
 GROUP_SIGNATURES = parse_header(_read(os.path.join(os.path.dirname(HEADER_PATH),
                                                    "recblr_groups.h")))
+# score priors (include/recblr_priors.h): likewise
+PRIOR_SIGNATURES = parse_header(_read(os.path.join(os.path.dirname(HEADER_PATH),
+                                                   "recblr_priors.h")))
 # the experimental library (experimental/recblr_exp.h: opt-in kernels that
 # measured slower than the default path; never loaded unless requested)
 EXP_SIGNATURES = parse_header(_read(os.path.join(_HERE, "experimental", "recblr_exp.h")))
@@ -148,7 +151,7 @@ def load(path: str | None = None) -> ctypes.CDLL:
     explicit path is loaded afresh and not cached."""
     return _load(path or LIB_PATH,
                  {**SIGNATURES, **DENSE_SIGNATURES, **PAIR_SIGNATURES, **CANDIDATE_SIGNATURES,
-                  **FILTER_SIGNATURES, **GROUP_SIGNATURES},
+                  **FILTER_SIGNATURES, **GROUP_SIGNATURES, **PRIOR_SIGNATURES},
                  "HIP extension not built",
                  "rb_version",
                  "ABI mismatch: library {} vs binding {}; rebuild", cache=path is None,

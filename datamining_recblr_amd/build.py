@@ -21,7 +21,8 @@ HEADERS = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.h"))) + [
     os.path.join(ROOT, "include", "recblr_pairs.h"),
     os.path.join(ROOT, "include", "recblr_candidates.h"),
     os.path.join(ROOT, "include", "recblr_filters.h"),
-    os.path.join(ROOT, "include", "recblr_groups.h")]
+    os.path.join(ROOT, "include", "recblr_groups.h"),
+    os.path.join(ROOT, "include", "recblr_priors.h")]
 OUT = os.path.join(_HERE, "lib", "libdmrecblr.so")
 # measurement aids for bench.py (probes/recblr_probe.h): their own library,
 # hidden visibility, never loaded by the model's path

@@ -583,6 +583,53 @@ int rb_item_topk_grouped(const float* seq, const float* items, int64_t B, int64_
                                   groups, max_per_group, reinterpret_cast<hipStream_t>(stream));
 }
 
+int64_t rb_item_topk_prior_workspace(int64_t B, int64_t V, int64_t d, int64_t k) {
+  if (B <= 0 || V <= 0 || d <= 0 || k < 1 || k > 64) return 0;
+  return item_topk_grouped_workspace_bytes(B, V, k);
+}
+
+int rb_item_topk_prior(const float* seq, const float* items, int64_t B, int64_t V, int64_t d,
+                       int64_t k, int64_t first_item, const int64_t* exclude, int64_t E,
+                       int64_t* ids, float* scores, void* workspace, int64_t workspace_bytes,
+                       void* stream, const int32_t* allow, int64_t F, int64_t words,
+                       const int64_t* allow_rows, const int32_t* groups, int64_t max_per_group,
+                       const float* prior, int64_t P, const int64_t* prior_rows,
+                       const float* prior_weight) {
+  const char* fn = "rb_item_topk_prior";
+  if (int rc = check_item_topk(fn, seq, items, B, V, d, k, first_item, exclude, E, ids, scores,
+                               workspace))
+    return rc;
+  if (allow)
+    if (int rc = check_allow(fn, allow, F, words, V)) return rc;
+  if (groups && max_per_group < 1) return fail(fn, "max_per_group must be >= 1");
+  if (!prior) return fail(fn, "null pointer (prior)");
+  if (P < 1) return fail(fn, "P must be >= 1");
+  return launch_item_topk_prior(seq, items, B, V, d, k, first_item, E > 0 ? exclude : nullptr, E,
+                                ids, scores, workspace, workspace_bytes, allow, F, words,
+                                allow ? allow_rows : nullptr, groups, groups ? max_per_group : 1,
+                                prior, P, prior_rows, prior_weight,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
+int rb_item_rank_prior(const float* seq, const float* items, const int64_t* target, int64_t B,
+                       int64_t V, int64_t d, int64_t first_item, int64_t* n_greater,
+                       int64_t* n_equal, void* workspace, int64_t workspace_bytes, void* stream,
+                       const int32_t* allow, int64_t F, int64_t words, const int64_t* allow_rows,
+                       const float* prior, int64_t P, const int64_t* prior_rows,
+                       const float* prior_weight) {
+  const char* fn = "rb_item_rank_prior";
+  if (int rc = check_item_rank(fn, seq, items, target, B, V, d, first_item, n_greater, workspace))
+    return rc;
+  if (allow)
+    if (int rc = check_allow(fn, allow, F, words, V)) return rc;
+  if (!prior) return fail(fn, "null pointer (prior)");
+  if (P < 1) return fail(fn, "P must be >= 1");
+  return launch_item_rank_prior(seq, items, target, B, V, d, first_item, n_greater, n_equal,
+                                workspace, workspace_bytes, allow, F, words,
+                                allow ? allow_rows : nullptr, prior, P, prior_rows, prior_weight,
+                                reinterpret_cast<hipStream_t>(stream));
+}
+
 int rb_item_ce_probs(const float* seq, const float* items, const int64_t* target,
                      const float* lse, const float* dloss, int64_t B, int64_t V, int64_t d,
                      int64_t item_offset, float* probs, int64_t ld, void* stream) {

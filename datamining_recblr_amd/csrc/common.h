@@ -14,6 +14,7 @@
 #include "../../include/recblr_candidates.h"
 #include "../../include/recblr_filters.h"
 #include "../../include/recblr_groups.h"
+#include "../../include/recblr_priors.h"
 
 namespace rb {
 
@@ -582,6 +583,21 @@ int launch_item_topk_grouped(const float* E, const float* W, int64_t B, int64_t 
                              const int* allow, int64_t F, int64_t words,
                              const int64_t* allow_rows, const int* groups, int64_t m,
                              hipStream_t st);
+// launch_item_topk / launch_item_rank over scores adjusted by a per-item prior
+// (include/recblr_priors.h); allow null: no filter, groups null: no cap; the
+// top-k workspace is the grouped one's with groups, the plain one's without
+int launch_item_topk_prior(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
+                           int64_t k, int64_t first, const int64_t* ex, int64_t NE, int64_t* ids,
+                           float* scores, void* ws, int64_t ws_bytes, const int* allow, int64_t F,
+                           int64_t words, const int64_t* allow_rows, const int* groups, int64_t m,
+                           const float* prior, int64_t P, const int64_t* prior_rows,
+                           const float* prior_weight, hipStream_t st);
+int launch_item_rank_prior(const float* E, const float* W, const int64_t* tgt, int64_t B,
+                           int64_t V, int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq,
+                           void* ws, int64_t ws_bytes, const int* allow, int64_t F, int64_t words,
+                           const int64_t* allow_rows, const float* prior, int64_t P,
+                           const int64_t* prior_rows, const float* prior_weight,
+                           hipStream_t st);
 int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, const float* lse,
                          const float* dloss, int64_t B, int64_t V, int64_t D, int64_t v_off,
                          float* out, int64_t ld, hipStream_t st);

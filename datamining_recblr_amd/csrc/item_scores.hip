@@ -244,6 +244,19 @@ struct AllowRow {
   __device__ __forceinline__ unsigned word(int64_t t) const {
     return ((unsigned)w[max<int64_t>(0, min<int64_t>(t, last))] & keep) | force;
   }
+  // every item allowed, for a kAllow kernel called without a filter; `any`
+  // is readable memory of at least one word (its value is masked away)
+  __device__ __forceinline__ static AllowRow all(const void* any) {
+    AllowRow r;
+    r.w = static_cast<const int*>(any);
+    r.last = 0;
+    r.keep = 0u;
+    r.force = ~0u;
+    return r;
+  }
+
+ private:
+  AllowRow() = default;
 };
 
 // bit r of the result = bit crow(r, h) of a tile's word: a lane's 16 items
@@ -252,13 +265,102 @@ __device__ __forceinline__ unsigned lane_bits(unsigned a, int h) {
   return (a & 0xfu) | ((a >> 4) & 0xf0u) | ((a >> 8) & 0xf00u) | ((a >> 12) & 0xf000u);
 }
 
+// ---- score priors: a per-item term, weighted per row (include/recblr_priors.h) -----
+// values [P, V] fp32, rows [B] int64 or null (the prior each row takes), weight
+// [B] fp32 or null (1 for every row).
+struct PriorArgs {
+  const float* values;
+  int64_t P, V;
+  const int64_t* rows;
+  const float* weight;
+};
+
+// One row's view of its prior.  rows null: prior 0.  f == -1: the row takes no
+// prior (its scores stay as they are, bit for bit); f outside [-1, P): the row
+// selects nothing.  The prior and item indices are clamped for the load and the
+// loaded value is used only where `on`, so nothing is ever read out of range.
+struct PriorRow {
+  const float* p = nullptr;
+  int64_t idx = 0, last = 0;   // the clamped prior index; V - 1
+  float w = 0.0f;
+  bool on = false, none = false;
+  PriorRow() = default;
+  __device__ __forceinline__ PriorRow(const PriorArgs& a, int64_t b) {
+    const int64_t f = a.rows ? a.rows[b] : 0;
+    idx = max<int64_t>(0, min<int64_t>(f, a.P - 1));
+    p = a.values + idx * a.V;
+    last = a.V - 1;
+    w = a.weight ? a.weight[b] : 1.0f;
+    on = f >= 0 && f < a.P;
+    none = f < -1 || f >= a.P;
+  }
+  __device__ __forceinline__ float at(int64_t v) const {
+    return p[max<int64_t>(0, min<int64_t>(v, last))];
+  }
+  // score + (w * prior): the product rounded, then the sum (no fma); a select,
+  // not an addition of zero, where the row takes no prior
+  __device__ __forceinline__ float adj(float s, float pv) const {
+    return on ? __fadd_rn(s, __fmul_rn(w, pv)) : s;
+  }
+};
+
+// The prior over a lane's walk of the item tiles: the lane owns one sequence and
+// the 16 items crow(r, h) of a tile, so it needs 16 values of its row's prior
+// per tile.  Where the wave's 32 sequences take one prior row (the common case;
+// a sequence without a prior counts as taking row 0) the tile's 32 values are
+// read one per lane, one tile ahead, and fetched by shuffle; otherwise each
+// lane gathers its own 16 ahead of the tile's MFMA chain.  The choice is a
+// ballot taken once, so it is wave-uniform.  kPrior false: nothing.
+template <bool kPrior>
+struct PriorSweep {
+  PriorRow pr;
+  bool shared = false;
+  float pw = 0.0f;    // the next tile's value of item 32 t + j (shared)
+  float pv[16] = {};  // this tile's values of the lane's items
+  __device__ __forceinline__ PriorSweep(const PriorArgs& pa, int64_t b, int64_t t0, int j) {
+    if constexpr (kPrior) {
+      pr = PriorRow(pa, b);
+      shared = __builtin_amdgcn_ballot_w64(pr.idx != __shfl(pr.idx, 0)) == 0;
+      if (shared) pw = pr.at(t0 * kTile + j);
+    }
+  }
+  // before tile t's MFMA chain: the loads
+  __device__ __forceinline__ void load(int64_t t, int j, int h) {
+    if constexpr (kPrior) {
+      if (shared) {
+        pv[0] = pw;
+        pw = pr.at((t + 1) * kTile + j);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) pv[r] = pr.at(t * kTile + crow(r, h));
+      }
+    }
+  }
+  // after it: the tile's scores become the adjusted scores
+  __device__ __forceinline__ void apply(f32x16& x, int h) {
+    if constexpr (kPrior) {
+      if (shared) {
+        const float pt = pv[0];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) pv[r] = __shfl(pt, crow(r, h));
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) x[r] = pr.adj(x[r], pv[r]);
+    }
+  }
+};
+
 // ---- target scores: the MFMA chain order, one thread per row ------------------
-// kAllow: a target its row's filter does not allow counts as out of range
-template <int D, bool kAllow>
+// kAllow: a target its row's filter does not allow counts as out of range (al
+// without words, in a kPrior kernel: no filter).  kPrior: the target's score
+// is adjusted by its row's prior; a row whose prior index selects nothing, like
+// a NaN adjusted score, counts as out of range.
+template <int D, bool kAllow, bool kPrior = false>
 __device__ __forceinline__ void target_dot(const float* __restrict__ E,
                                            const float* __restrict__ W,
                                            const int64_t* __restrict__ tgt, int64_t B, int64_t V,
-                                           float* __restrict__ ts, const AllowArgs& al) {
+                                           float* __restrict__ ts, const AllowArgs& al,
+                                           const PriorArgs& pa = PriorArgs{}) {
   constexpr int KH = D / 2;
   const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
@@ -268,7 +370,17 @@ __device__ __forceinline__ void target_dot(const float* __restrict__ E,
     return;
   }
   if constexpr (kAllow) {
-    if (!((AllowRow(al, b).word(t >> 5) >> (t & 31)) & 1u)) {
+    if (!kPrior || al.words) {
+      if (!((AllowRow(al, b).word(t >> 5) >> (t & 31)) & 1u)) {
+        ts[b] = NAN;
+        return;
+      }
+    }
+  }
+  PriorRow pr;
+  if constexpr (kPrior) {
+    pr = PriorRow(pa, b);
+    if (pr.none) {
       ts[b] = NAN;
       return;
     }
@@ -284,6 +396,7 @@ __device__ __forceinline__ void target_dot(const float* __restrict__ E,
     acc = fmaf(w0[s], e0[s], acc);
     acc = fmaf(w1[s], e1[s], acc);
   }
+  if constexpr (kPrior) acc = pr.adj(acc, pr.at(t));
   ts[b] = acc;
 }
 
@@ -302,6 +415,16 @@ __global__ __launch_bounds__(256) void k_target_dot_allowed(const float* __restr
                                                             int64_t B, int64_t V,
                                                             float* __restrict__ ts, AllowArgs al) {
   target_dot<D, true>(E, W, tgt, B, V, ts, al);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_target_dot_prior(const float* __restrict__ E,
+                                                          const float* __restrict__ W,
+                                                          const int64_t* __restrict__ tgt,
+                                                          int64_t B, int64_t V,
+                                                          float* __restrict__ ts, AllowArgs al,
+                                                          PriorArgs pa) {
+  target_dot<D, true, true>(E, W, tgt, B, V, ts, al, pa);
 }
 
 // Workgroup placement.  The grid is 1-D over RB fixed-row blocks x S splits
@@ -621,14 +744,16 @@ __global__ __launch_bounds__(256) void k_sum_parts(const float* __restrict__ par
 // ---- ranks: #items scoring above / equal to the target -----------------------------
 // kAllow: only items that the row's filter allows are counted; tile t of the
 // items is word t of the filter, read one tile ahead of its use.
-template <int D, bool kAllow>
+// kPrior: the counts run over the adjusted scores (ts holds the target's).
+template <int D, bool kAllow, bool kPrior = false>
 __device__ __forceinline__ void item_rank(const float* __restrict__ E,
                                           const float* __restrict__ W,
                                           const float* __restrict__ ts,
                                           const int64_t* __restrict__ tgt, int64_t B, int64_t V,
                                           int64_t first, int64_t per, int64_t RB, int64_t NS,
                                           int* __restrict__ gt_part, int* __restrict__ eq_part,
-                                          const AllowArgs& al) {
+                                          const AllowArgs& al,
+                                          const PriorArgs& pa = PriorArgs{}) {
   constexpr int KH = D / 2;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
   Place pl;
@@ -642,6 +767,7 @@ __device__ __forceinline__ void item_rank(const float* __restrict__ E,
   int gt = 0, eq = 0;
   const AllowRow ar(al, kAllow ? bc : 0);
   unsigned aw = kAllow ? ar.word(pl.split * per) : 0u;   // the next tile's word
+  PriorSweep<kPrior> ps(pa, bc, pl.split * per, j);
   stream_tiles<D, false>(W, V, per, pl.split, nullptr, nullptr,
                          [&](int64_t t, const float* tile, const float*, const int64_t*) {
     const int64_t v0 = t * kTile;
@@ -650,7 +776,9 @@ __device__ __forceinline__ void item_rank(const float* __restrict__ E,
       am = lane_bits(aw, h);
       aw = ar.word(t + 1);
     }
-    const f32x16 x = lds_dot<D, KH, true>(tile, j, h, eb);
+    ps.load(t, j, h);
+    f32x16 x = lds_dot<D, KH, true>(tile, j, h, eb);
+    ps.apply(x, h);
     const int lo = rel32(first, v0), hi = rel32(V, v0), tt = rel32(tb, v0);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -686,6 +814,14 @@ __global__ __launch_bounds__(256) void k_item_rank_allowed(
     const int64_t* __restrict__ tgt, int64_t B, int64_t V, int64_t first, int64_t per, int64_t RB,
     int64_t NS, int* __restrict__ gt_part, int* __restrict__ eq_part, AllowArgs al) {
   item_rank<D, true>(E, W, ts, tgt, B, V, first, per, RB, NS, gt_part, eq_part, al);
+}
+
+template <int D, bool kAllow>
+__global__ __launch_bounds__(256) void k_item_rank_prior(
+    const float* __restrict__ E, const float* __restrict__ W, const float* __restrict__ ts,
+    const int64_t* __restrict__ tgt, int64_t B, int64_t V, int64_t first, int64_t per, int64_t RB,
+    int64_t NS, int* __restrict__ gt_part, int* __restrict__ eq_part, AllowArgs al, PriorArgs pa) {
+  item_rank<D, kAllow, true>(E, W, ts, tgt, B, V, first, per, RB, NS, gt_part, eq_part, al, pa);
 }
 
 __global__ __launch_bounds__(256) void k_rank_rows(const int* __restrict__ gt_part,
@@ -756,7 +892,14 @@ struct GroupArgs {
   int m;
 };
 
-template <int D, int KP, bool kAllow, bool kGroup = false>
+//
+// kPrior (include/recblr_priors.h): a tile's scores become the adjusted scores
+// right after the MFMA chain (PriorSweep), ahead of the threshold compare, so
+// the filter, the exclusion, the cap, the lists and the merge over the splits
+// see adjusted scores and nothing else changes; a row whose prior index selects
+// nothing passes no score.  al without words (a kAllow kernel called without a
+// filter): every item allowed.  No LDS of its own.
+template <int D, int KP, bool kAllow, bool kGroup = false, bool kPrior = false>
 __device__ __forceinline__ void item_topk(const float* __restrict__ E,
                                           const float* __restrict__ W, int64_t B, int64_t V,
                                           int64_t first, int k, const int64_t* __restrict__ ex,
@@ -765,7 +908,8 @@ __device__ __forceinline__ void item_topk(const float* __restrict__ E,
                                           float* l_sc, int* l_id, unsigned* l_ex,
                                           const AllowArgs& al, int* __restrict__ c_g = nullptr,
                                           unsigned short* l_g = nullptr,
-                                          const GroupArgs& gr = GroupArgs{}) {
+                                          const GroupArgs& gr = GroupArgs{},
+                                          const PriorArgs& pa = PriorArgs{}) {
   constexpr int KH = D / 2, NR = kWaves * kTile, XW = kExBits / 32;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
   Place pl;
@@ -855,8 +999,10 @@ __device__ __forceinline__ void item_topk(const float* __restrict__ E,
     thr_id = wi;
     thr_pos = wp;
   };
-  const AllowRow ar(al, kAllow ? bc : 0);
+  const AllowRow ar = kPrior && kAllow && !al.words ? AllowRow::all(E)
+                                                    : AllowRow(al, kAllow ? bc : 0);
   unsigned aw = kAllow ? ar.word(pl.split * per) : 0u;   // the next tile's word
+  PriorSweep<kPrior> ps(pa, bc, pl.split * per, j);
   // group of item 32 t + j, clamped for the load (an item at or beyond V is no candidate)
   auto tile_group = [&](int64_t t) -> int {
     return gr.ids[max<int64_t>(0, min<int64_t>(t * kTile + j, V - 1))] & kNoGroup;
@@ -876,7 +1022,9 @@ __device__ __forceinline__ void item_topk(const float* __restrict__ E,
       gt = gw;
       gw = tile_group(t + 1);
     }
-    const f32x16 x = lds_dot<D, KH, true>(tile, j, h, eb);
+    ps.load(t, j, h);
+    f32x16 x = lds_dot<D, KH, true>(tile, j, h, eb);
+    ps.apply(x, h);
     const int lo = rel32(first, v0), hi = rel32(V, v0);
     unsigned m = 0;   // bit r: score r passes the cheap filter
 #pragma unroll
@@ -885,6 +1033,7 @@ __device__ __forceinline__ void item_topk(const float* __restrict__ E,
       m |= ((c >= lo) & (c < hi) & (x[r] >= thr)) ? 1u << r : 0u;
     }
     if constexpr (kAllow) m &= am;
+    if constexpr (kPrior) m = ps.pr.none ? 0u : m;
     // wave-uniform loop: every lane takes its lowest passing score per turn
     while (__builtin_amdgcn_ballot_w64(m != 0) != 0) {
       const bool p = m != 0;
@@ -967,6 +1116,28 @@ __global__ __launch_bounds__(256) void k_item_topk_grouped(
   __shared__ unsigned short l_g[KP * kWaves * kTile];
   item_topk<D, KP, kAllow, true>(E, W, B, V, first, k, ex, NE, per, RB, NS, c_sc, c_id, l_sc, l_id,
                                  l_ex, al, c_g, l_g, gr);
+}
+
+// The lists under a prior: the LDS of the kernel without one, to the byte (the
+// prior lives in registers), so the grouped d = 256, KP = 64 instantiation
+// stands where k_item_topk_grouped's does.  Instantiated for <kAllow, kGroup> =
+// (0, 0), (1, 0) and (1, 1): a cap without a filter runs (1, 1) with al.words
+// null.
+template <int D, int KP, bool kAllow, bool kGroup>
+__global__ __launch_bounds__(256) void k_item_topk_prior(
+    const float* __restrict__ E, const float* __restrict__ W, int64_t B, int64_t V, int64_t first,
+    int k, const int64_t* __restrict__ ex, int64_t NE, int64_t per, int64_t RB, int64_t NS,
+    float* __restrict__ c_sc, int* __restrict__ c_id, int* __restrict__ c_g, AllowArgs al,
+    GroupArgs gr, PriorArgs pa) {
+  TOPK_LDS;
+  if constexpr (kGroup) {
+    __shared__ unsigned short l_g[KP * kWaves * kTile];
+    item_topk<D, KP, kAllow, true, true>(E, W, B, V, first, k, ex, NE, per, RB, NS, c_sc, c_id,
+                                         l_sc, l_id, l_ex, al, c_g, l_g, gr, pa);
+  } else {
+    item_topk<D, KP, kAllow, false, true>(E, W, B, V, first, k, ex, NE, per, RB, NS, c_sc, c_id,
+                                          l_sc, l_id, l_ex, al, nullptr, nullptr, gr, pa);
+  }
 }
 
 // One wave per row: the row's S lists of k candidates (all ids distinct: the
@@ -1670,10 +1841,11 @@ int launch_item_ce_bwd(const float* E, const float* W, const int64_t* tgt, const
 
 namespace {
 // rb_item_rank (al null) and rb_item_rank_allowed: one workspace, one plan
+// ... and rb_item_rank_prior (pa given, al or not): kernels of its own
 int item_rank_launch(const char* fn, const float* E, const float* W, const int64_t* tgt,
                      int64_t B, int64_t V, int64_t D, int64_t first, int64_t* n_gt,
                      int64_t* n_eq, void* ws, int64_t ws_bytes, const AllowArgs* al,
-                     hipStream_t st) {
+                     hipStream_t st, const PriorArgs* pa = nullptr) {
   const RankWs L = rank_layout(B, V);
   if (ws_bytes < (int64_t)L.total) return fail((std::string(fn) + ": workspace too small").c_str());
   char* w = static_cast<char*>(ws);
@@ -1683,7 +1855,14 @@ int item_rank_launch(const char* fn, const float* E, const float* W, const int64
   const Grid2 g = plan(B, ntiles(V));
   const dim3 rows((unsigned)((B + 255) / 256));
   if (int rc = for_item_dim(D, [&](auto dc) {
-        if (al) {
+        if (pa) {
+          const AllowArgs a = al ? *al : AllowArgs{};
+          hipLaunchKernelGGL(k_target_dot_prior<dc>, rows, dim3(256), 0, st, E, W, tgt, B, V, ts,
+                             a, *pa);
+          const auto kernel = al ? k_item_rank_prior<dc, true> : k_item_rank_prior<dc, false>;
+          hipLaunchKernelGGL(kernel, dim3(g.wgs()), dim3(256), 0, st, E, W, ts, tgt, B, V, first,
+                             g.per, g.blocks, g.splits, gt, eq, a, *pa);
+        } else if (al) {
           hipLaunchKernelGGL(k_target_dot_allowed<dc>, rows, dim3(256), 0, st, E, W, tgt, B, V, ts,
                              *al);
           hipLaunchKernelGGL(k_item_rank_allowed<dc>, dim3(g.wgs()), dim3(256), 0, st, E, W, ts,
@@ -1716,6 +1895,18 @@ int launch_item_rank_allowed(const float* E, const float* W, const int64_t* tgt,
                           ws_bytes, &al, st);
 }
 
+int launch_item_rank_prior(const float* E, const float* W, const int64_t* tgt, int64_t B,
+                           int64_t V, int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq,
+                           void* ws, int64_t ws_bytes, const int* allow, int64_t F, int64_t words,
+                           const int64_t* allow_rows, const float* prior, int64_t P,
+                           const int64_t* prior_rows, const float* prior_weight,
+                           hipStream_t st) {
+  const AllowArgs al{allow, F, words, allow_rows};
+  const PriorArgs pa{prior, P, V, prior_rows, prior_weight};
+  return item_rank_launch("rb_item_rank_prior", E, W, tgt, B, V, D, first, n_gt, n_eq, ws,
+                          ws_bytes, allow ? &al : nullptr, st, &pa);
+}
+
 int64_t item_topk_workspace_bytes(int64_t B, int64_t V, int64_t k) {
   return (int64_t)topk_layout(B, V, k).total;
 }
@@ -1730,13 +1921,38 @@ namespace {
 int item_topk_launch(const char* fn, const float* E, const float* W, int64_t B, int64_t V,
                      int64_t D, int64_t k, int64_t first, const int64_t* ex, int64_t NE,
                      int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
-                     const AllowArgs* al, hipStream_t st, const GroupArgs* gr = nullptr) {
+                     const AllowArgs* al, hipStream_t st, const GroupArgs* gr = nullptr,
+                     const PriorArgs* pa = nullptr) {
   const TopkWs L = topk_layout(B, V, k, gr != nullptr);
   if (ws_bytes < (int64_t)L.total) return fail((std::string(fn) + ": workspace too small").c_str());
   char* w = static_cast<char*>(ws);
   float* sc = reinterpret_cast<float*>(w + L.sc);
   int* id = reinterpret_cast<int*>(w + L.id);
   const Grid2 g = plan(B, ntiles(V));
+  if (pa) {
+    // rb_item_topk_prior: the same plan, workspace and merge kernels
+    int* cg = gr ? reinterpret_cast<int*>(w + L.g) : nullptr;
+    if (int rc = for_item_dim(D, [&](auto dc) {
+          const auto kernel =
+              gr ? (k <= 32 ? k_item_topk_prior<dc, 32, true, true>
+                            : k_item_topk_prior<dc, 64, true, true>)
+              : al ? (k <= 32 ? k_item_topk_prior<dc, 32, true, false>
+                              : k_item_topk_prior<dc, 64, true, false>)
+                   : (k <= 32 ? k_item_topk_prior<dc, 32, false, false>
+                              : k_item_topk_prior<dc, 64, false, false>);
+          hipLaunchKernelGGL(kernel, dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, (int)k,
+                             ex, NE, g.per, g.blocks, g.splits, sc, id, cg,
+                             al ? *al : AllowArgs{}, gr ? *gr : GroupArgs{}, *pa);
+        }))
+      return rc;
+    if (gr)
+      hipLaunchKernelGGL(k_topk_rows_grouped, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, sc,
+                         id, cg, g.splits, B, (int)k, gr->m, ids, scores);
+    else
+      hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, sc, id,
+                         g.splits, B, (int)k, ids, scores);
+    return launch_status(fn);
+  }
   if (gr) {
     int* cg = reinterpret_cast<int*>(w + L.g);
     if (int rc = for_item_dim(D, [&](auto dc) {
@@ -1800,6 +2016,19 @@ int launch_item_topk_grouped(const float* E, const float* W, int64_t B, int64_t 
   const GroupArgs gr{groups, (int)std::min<int64_t>(m, k)};
   return item_topk_launch("rb_item_topk_grouped", E, W, B, V, D, k, first, ex, NE, ids, scores,
                           ws, ws_bytes, allow ? &al : nullptr, st, &gr);
+}
+
+int launch_item_topk_prior(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
+                           int64_t k, int64_t first, const int64_t* ex, int64_t NE, int64_t* ids,
+                           float* scores, void* ws, int64_t ws_bytes, const int* allow, int64_t F,
+                           int64_t words, const int64_t* allow_rows, const int* groups, int64_t m,
+                           const float* prior, int64_t P, const int64_t* prior_rows,
+                           const float* prior_weight, hipStream_t st) {
+  const AllowArgs al{allow, F, words, allow_rows};
+  const GroupArgs gr{groups, (int)std::min<int64_t>(m, k)};
+  const PriorArgs pa{prior, P, V, prior_rows, prior_weight};
+  return item_topk_launch("rb_item_topk_prior", E, W, B, V, D, k, first, ex, NE, ids, scores, ws,
+                          ws_bytes, allow ? &al : nullptr, st, groups ? &gr : nullptr, &pa);
 }
 
 int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, const float* lse,

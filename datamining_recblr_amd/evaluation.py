@@ -89,18 +89,33 @@ def evaluate_unseen(model, item_id_lists, targets, topk=(10,), batch_size: int =
 
 
 @torch.no_grad()
-def full_sort_metrics(model, batches, topk=(10, 20), allow=None, allow_rows_key=None):
+def full_sort_metrics(model, batches, topk=(10, 20), allow=None, allow_rows_key=None,
+                      prior=None, prior_rows_key=None, prior_weight=None):
     """RecBole full-sort Hit/NDCG/MRR@k over leave-one-out batches
     (interaction dicts with ITEM_SEQ, ITEM_SEQ_LEN and POS_ITEM_ID).  allow
     (scoring.item_filters) ranks each target among the items of a catalogue
     filter only; allow_rows_key names the batches' entry that holds each row's
     filter index (None: filter 0 for every row).  A target that its row's
-    filter does not allow is dropped, as an invalid target is."""
+    filter does not allow is dropped, as an invalid target is.  prior
+    (scoring.item_priors) ranks by score + weight * prior[item];
+    prior_rows_key names the batches' entry that holds each row's prior index
+    (None: prior 0 for every row), and prior_weight is a float (or None: 1.0)
+    for all rows.  A target whose adjusted score is NaN is dropped."""
+    if prior is None and (prior_rows_key is not None or prior_weight is not None):
+        raise ValueError("prior_rows_key / prior_weight without prior")
     was_training = model.training
     model.eval()
     gts, eqs = [], []
     for inter in batches:
-        if allow is None:
+        if prior is not None:
+            kw = {}
+            if allow is not None:
+                kw = dict(allow=allow, allow_rows=inter[allow_rows_key]
+                          if allow_rows_key is not None else None)
+            g, e = model.full_sort_rank(
+                inter, prior=prior, prior_weight=prior_weight,
+                prior_rows=inter[prior_rows_key] if prior_rows_key is not None else None, **kw)
+        elif allow is None:
             g, e = model.full_sort_rank(inter)
         else:
             rows = inter[allow_rows_key] if allow_rows_key is not None else None
@@ -114,7 +129,7 @@ def full_sort_metrics(model, batches, topk=(10, 20), allow=None, allow_rows_key=
 @torch.no_grad()
 def recommend(model, item_id_lists, k: int = 10, batch_size: int = 1024,
               exclude_seen: bool = True, device=None, allow=None, allow_rows=None,
-              groups=None, max_per_group=None):
+              groups=None, max_per_group=None, prior=None, prior_rows=None, prior_weight=None):
     """Each user's k best items from their input id sequence.
 
     item_id_lists: per-user id sequences (ints in [0, n_items)), batched by
@@ -131,8 +146,27 @@ def recommend(model, item_id_lists, k: int = 10, batch_size: int = 1024,
     filter 0 for everyone, -1: no filter for that user) and follows the users
     through the length sort.  groups (scoring.item_groups) and max_per_group
     cap every list at that many items of one group; the groups are per item,
-    so the length sort does not touch them."""
+    so the length sort does not touch them.  prior (scoring.item_priors)
+    ranks by score + weight * prior[item]: prior_rows [n] names each user's
+    prior (None: prior 0 for everyone, -1: none for that user) and prior_weight
+    is a float for everyone or a float [n] tensor with each user's strength;
+    both are per user, in the callers' order, and follow the users through the
+    length sort."""
     device = device or next(model.parameters()).device
+    n_users = len(item_id_lists)
+    if prior is None and (prior_rows is not None or prior_weight is not None):
+        raise ValueError("prior_rows / prior_weight without prior")
+    if prior is not None:
+        prior = prior.to(device)
+    if prior_rows is not None:
+        prior_rows = torch.as_tensor(prior_rows, dtype=torch.int64).cpu()
+        if prior_rows.shape != (n_users,):
+            raise ValueError(f"prior_rows must be [{n_users}], got {tuple(prior_rows.shape)}")
+    if isinstance(prior_weight, torch.Tensor):
+        prior_weight = prior_weight.detach().to(dtype=torch.float32).cpu()
+        if prior_weight.shape != (n_users,):
+            raise ValueError(f"a tensor prior_weight must be [{n_users}], got "
+                             f"{tuple(prior_weight.shape)}")
     if (groups is None) != (max_per_group is None):
         raise ValueError("groups and max_per_group are given together or not at all")
     if groups is not None:
@@ -164,10 +198,16 @@ def recommend(model, item_id_lists, k: int = 10, batch_size: int = 1024,
                 seq[r, :len(row)] = torch.as_tensor(row, dtype=torch.int64)
             seq = seq.to(device)
             out = model.forward(seq, lens[idx].to(device), exact_lengths=True)
+            pkw = {}
+            if prior is not None:
+                pkw = dict(prior=prior,
+                           prior_rows=prior_rows[idx] if prior_rows is not None else None,
+                           prior_weight=prior_weight[idx]
+                           if isinstance(prior_weight, torch.Tensor) else prior_weight)
             i, sc = top_items(out, table, k, first_item=1, exclude=seq if exclude_seen else None,
                               allow=allow,
                               allow_rows=allow_rows[idx] if allow_rows is not None else None,
-                              groups=groups, max_per_group=max_per_group)
+                              groups=groups, max_per_group=max_per_group, **pkw)
             ids[idx] = i.cpu()
             scores[idx] = sc.cpu()
     finally:

@@ -697,6 +697,7 @@ def embedding_plan(idx, num_rows, d, stream=None):
 FLOP_KERNELS = frozenset({"rb_item_ce_fwd", "rb_item_ce_bwd", "rb_item_ce_probs", "rb_item_rank",
                           "rb_item_scores", "rb_item_topk", "rb_item_ce_fwd_h", "rb_item_ce_probs_h",
                           "rb_item_rank_allowed", "rb_item_topk_allowed", "rb_item_topk_grouped",
+                          "rb_item_topk_prior", "rb_item_rank_prior",
                           "rb_item_ce_probs_h_t", "rb_item_ce_probs_h_both",
                           "rb_item_ce_fwd_h_rows", "rb_item_ce_probs_h_rows",
                           "rb_item_ce_probs_h_both_rows"})
@@ -1020,17 +1021,54 @@ def _allow_args(allow, allow_rows, B, V, device):
                                  allow_rows.data_ptr() if allow_rows is not None else None)
 
 
-def item_rank(seq, items, target, first_item=1, want_equal=True, allow=None, allow_rows=None):
+def _prior_args(prior, prior_rows, prior_weight, B, V, device):
+    """The four trailing arguments of rb_item_*_prior, and the tensors that
+    back them: prior fp32 [P, V] (scoring.ItemPriors.values), prior_rows int64
+    [B] or None (prior 0 for every row), prior_weight fp32 [B] or None (1).
+    Values of prior_rows are the kernel's business (-1: no prior; out of
+    range: the row selects nothing) and are not read here."""
+    _check(prior, "prior")
+    if prior.dim() != 2 or prior.shape[0] < 1 or prior.shape[1] != V:
+        raise ValueError(f"prior must be fp32 [P >= 1, {V}], got {tuple(prior.shape)}")
+    if prior.device != device:
+        raise ValueError("prior must be on the same device")
+    prior = prior.contiguous()
+    if prior_rows is not None:
+        _check(prior_rows, "prior_rows", dtype=torch.int64)
+        if prior_rows.shape != (B,) or prior_rows.device != device:
+            raise ValueError(f"prior_rows must be int64 [B] on the same device, got "
+                             f"{tuple(prior_rows.shape)}")
+        prior_rows = prior_rows.contiguous()
+    if prior_weight is not None:
+        _check(prior_weight, "prior_weight")
+        if prior_weight.shape != (B,) or prior_weight.device != device:
+            raise ValueError(f"prior_weight must be fp32 [B] on the same device, got "
+                             f"{tuple(prior_weight.shape)}")
+        prior_weight = prior_weight.contiguous()
+    return (prior, prior_rows, prior_weight), (
+        prior.data_ptr(), prior.shape[0],
+        prior_rows.data_ptr() if prior_rows is not None else None,
+        prior_weight.data_ptr() if prior_weight is not None else None)
+
+
+def item_rank(seq, items, target, first_item=1, want_equal=True, allow=None, allow_rows=None,
+              prior=None, prior_rows=None, prior_weight=None):
     """(n_greater, n_equal) int64 [B]: items in [first_item, V) other than the
     target scoring above / equal to it (-1 for an out-of-range target).
     allow / allow_rows: per-row allow-bitmaps (_allow_args,
     rb_item_rank_allowed) — only allowed items count, and a target its row's
-    filter does not allow gives -1."""
+    filter does not allow gives -1.  prior / prior_rows / prior_weight
+    (_prior_args, rb_item_rank_prior, with or without a filter): the counts
+    compare adjusted scores, score + (weight * prior[row's prior, item]); a
+    target whose adjusted score is NaN, or whose row's prior index is out of
+    range, gives -1."""
     seq, items, target = _item_operands(seq, items, target)
     B, d = seq.shape
     V = items.shape[0]
     if allow is None and allow_rows is not None:
         raise ValueError("allow_rows without allow")
+    if prior is None and (prior_rows is not None or prior_weight is not None):
+        raise ValueError("prior_rows / prior_weight without prior")
     lib = _lib.load()
     ws_bytes = int(lib.rb_item_rank_workspace(B, V, d))
     ws = torch.empty((ws_bytes,), device=seq.device, dtype=torch.uint8)
@@ -1039,7 +1077,13 @@ def item_rank(seq, items, target, first_item=1, want_equal=True, allow=None, all
     args = (seq.data_ptr(), items.data_ptr(), target.data_ptr(), B, V, d, int(first_item),
             gt.data_ptr(), eq.data_ptr() if eq is not None else None, ws.data_ptr(), ws_bytes,
             _stream(seq))
-    if allow is None:
+    if prior is not None:
+        extra = (None, 0, 0, None)
+        if allow is not None:
+            _keep, extra = _allow_args(allow, allow_rows, B, V, seq.device)
+        _keep_p, pextra = _prior_args(prior, prior_rows, prior_weight, B, V, seq.device)
+        _launch("rb_item_rank_prior", 2 * B * V * d, *args, *extra, *pextra, _flops=True)
+    elif allow is None:
         _launch("rb_item_rank", 2 * B * V * d, *args, _flops=True)
     else:
         _keep, extra = _allow_args(allow, allow_rows, B, V, seq.device)
@@ -1054,7 +1098,7 @@ ITEM_GROUP_ID_MAX = 65534
 
 
 def item_topk(seq, items, k, first_item=1, exclude=None, allow=None, allow_rows=None,
-              groups=None, max_per_group=None):
+              groups=None, max_per_group=None, prior=None, prior_rows=None, prior_weight=None):
     """(ids int64 [B, k], scores fp32 [B, k]): each row's k best items in
     [first_item, V) not listed in exclude [B, E] (int64; entries outside
     [0, V) ignored), by (score descending, id ascending), scores bit-identical
@@ -1064,7 +1108,11 @@ def item_topk(seq, items, k, first_item=1, exclude=None, allow=None, allow_rows=
     over the items that the row's filter allows.  groups int32 [V] (values in
     [-1, ITEM_GROUP_ID_MAX], not read here) with max_per_group >= 1: the walk
     in that order takes an item unless max_per_group of its group were taken
-    (-1: never capped), with or without a filter (rb_item_topk_grouped)."""
+    (-1: never capped), with or without a filter (rb_item_topk_grouped).
+    prior / prior_rows / prior_weight (_prior_args, rb_item_topk_prior, with or
+    without a filter and a cap): all of the above runs over adjusted scores,
+    score + (weight * prior[row's prior, item]), product and sum each rounded
+    to fp32, which are the scores returned."""
     seq, items, _ = _item_operands(seq, items)
     B, d = seq.shape
     V = items.shape[0]
@@ -1090,8 +1138,12 @@ def item_topk(seq, items, k, first_item=1, exclude=None, allow=None, allow_rows=
         groups = groups.contiguous()
         if int(max_per_group) < 1:
             raise ValueError(f"max_per_group = {max_per_group} must be >= 1")
+    if prior is None and (prior_rows is not None or prior_weight is not None):
+        raise ValueError("prior_rows / prior_weight without prior")
     lib = _lib.load()
     ws_fn = lib.rb_item_topk_workspace if groups is None else lib.rb_item_topk_grouped_workspace
+    if prior is not None:
+        ws_fn = lib.rb_item_topk_prior_workspace
     ws_bytes = int(ws_fn(B, V, d, k))
     ws = torch.empty((ws_bytes,), device=seq.device, dtype=torch.uint8)
     ids = torch.empty((B, k), device=seq.device, dtype=torch.int64)
@@ -1099,7 +1151,15 @@ def item_topk(seq, items, k, first_item=1, exclude=None, allow=None, allow_rows=
     args = (seq.data_ptr(), items.data_ptr(), B, V, d, k, int(first_item),
             exclude.data_ptr() if E > 0 else None, E, ids.data_ptr(), scores.data_ptr(),
             ws.data_ptr(), ws_bytes, _stream(seq))
-    if groups is not None:
+    if prior is not None:
+        extra = (None, 0, 0, None)
+        if allow is not None:
+            _keep, extra = _allow_args(allow, allow_rows, B, V, seq.device)
+        _keep_p, pextra = _prior_args(prior, prior_rows, prior_weight, B, V, seq.device)
+        _launch("rb_item_topk_prior", 2 * B * V * d, *args, *extra,
+                groups.data_ptr() if groups is not None else None,
+                int(max_per_group) if groups is not None else 0, *pextra, _flops=True)
+    elif groups is not None:
         extra = (None, 0, 0, None)
         if allow is not None:
             _keep, extra = _allow_args(allow, allow_rows, B, V, seq.device)

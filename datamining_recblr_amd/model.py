@@ -690,33 +690,40 @@ class RecBLR(SequentialRecommender):
         seq_output = self.forward(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN])
         return self._scores_all(seq_output)
 
-    def full_sort_rank(self, interaction, first_item: int = 1, allow=None, allow_rows=None):
+    def full_sort_rank(self, interaction, first_item: int = 1, allow=None, allow_rows=None,
+                       prior=None, prior_rows=None, prior_weight=None):
         """Rank of each row's target (POS_ITEM_ID) under full_sort_predict's
         scores without materialising them: (n_greater, n_equal) over items
         [first_item, n_items) (item 0 is RecBole's padding id, masked to -inf
         by its full-sort evaluator).  allow / allow_rows: a catalogue filter
-        per row (scoring.item_filters, scoring.target_ranks)."""
+        per row (scoring.item_filters, scoring.target_ranks).  prior /
+        prior_rows / prior_weight: the ranks under score + weight * prior[item]
+        (scoring.item_priors, scoring.target_ranks)."""
         seq_output = self.forward(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN])
         return target_ranks(seq_output, self.item_embedding.weight,
                             interaction[self.POS_ITEM_ID], first_item, allow=allow,
-                            allow_rows=allow_rows)
+                            allow_rows=allow_rows, prior=prior, prior_rows=prior_rows,
+                            prior_weight=prior_weight)
 
     @torch.no_grad()
     def full_sort_topk(self, interaction, k: int = 10, exclude_seen: bool = True,
                        first_item: int = 1, allow=None, allow_rows=None, groups=None,
-                       max_per_group=None):
+                       max_per_group=None, prior=None, prior_rows=None, prior_weight=None):
         """(ids, scores) [B, k]: each row's k best items under
         full_sort_predict's scores (RecBLR.py:114-122) without materialising
         them, by (score descending, id ascending) over items [first_item,
         n_items); exclude_seen drops the row's own ITEM_SEQ entries.  allow /
         allow_rows: a catalogue filter per row (scoring.item_filters,
         scoring.top_items).  groups / max_per_group: at most that many items
-        of one group in a list (scoring.item_groups, scoring.top_items)."""
+        of one group in a list (scoring.item_groups, scoring.top_items).  prior
+        / prior_rows / prior_weight: rank by score + weight * prior[item]
+        (scoring.item_priors, scoring.top_items)."""
         item_seq = interaction[self.ITEM_SEQ]
         seq_output = self.forward(item_seq, interaction[self.ITEM_SEQ_LEN])
         return top_items(seq_output, self.item_embedding.weight, k, first_item=first_item,
                          exclude=item_seq if exclude_seen else None, allow=allow,
-                         allow_rows=allow_rows, groups=groups, max_per_group=max_per_group)
+                         allow_rows=allow_rows, groups=groups, max_per_group=max_per_group,
+                         prior=prior, prior_rows=prior_rows, prior_weight=prior_weight)
 
     # ---- candidate lists (scoring.candidate_scores / top_candidates) ----------
     def predict_candidates(self, interaction, candidates):
@@ -788,16 +795,19 @@ class RecBLR(SequentialRecommender):
 
     def session_recommend(self, state, items=None, slots=None, k: int = 10,
                           exclude_seen: bool = True, first_item: int = 1, allow=None,
-                          allow_rows=None, groups=None, max_per_group=None):
+                          allow_rows=None, groups=None, max_per_group=None, prior=None,
+                          prior_rows=None, prior_weight=None):
         """(ids, scores) [B, k]: the rows' k best items after one step (items
         [B]) or append (items [B, W]), or from the slots' stored outputs (items
         None), the slots' own last S item ids excluded (session.recommend).
         allow / allow_rows: a catalogue filter per row (scoring.item_filters);
-        groups / max_per_group: a cap per group (scoring.item_groups)."""
+        groups / max_per_group: a cap per group (scoring.item_groups); prior /
+        prior_rows / prior_weight: a score prior per row (scoring.item_priors)."""
         from .session import recommend
 
         return recommend(self, state, items, slots, k, exclude_seen, first_item, allow=allow,
-                         allow_rows=allow_rows, groups=groups, max_per_group=max_per_group)
+                         allow_rows=allow_rows, groups=groups, max_per_group=max_per_group,
+                         prior=prior, prior_rows=prior_rows, prior_weight=prior_weight)
 
     def session_rerank(self, state, candidates, items=None, slots=None, k: int = 10,
                        exclude_seen: bool = False, first_item: int = 1):

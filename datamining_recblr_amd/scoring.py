@@ -54,7 +54,7 @@ __all__ = ["item_cross_entropy", "item_cross_entropy_rows", "full_sort_scores", 
            "top_items", "supported", "pair_loss", "pair_loss_reference", "shared_softmax_loss",
            "shared_softmax_reference", "candidate_scores",
            "order_candidates", "top_candidates", "candidate_ranks", "ItemFilters", "item_filters",
-           "ItemGroups", "item_groups"]
+           "ItemGroups", "item_groups", "ItemPriors", "item_priors", "log_popularity"]
 
 
 def supported(seq: torch.Tensor, table: torch.Tensor) -> bool:
@@ -757,20 +757,164 @@ def _check_groups(groups, max_per_group, V: int, device):
     return groups.to(device), m
 
 
+# ---- score priors: a per-item term, weighted per row (include/recblr_priors.h) ------
+class ItemPriors:
+    """P per-item score priors over a catalogue of n_items items: values fp32
+    [P, n_items] contiguous.  top_items and target_ranks rank by score +
+    (prior_weight * values[prior_rows[b], item]): a promotion, a recency or
+    margin boost, a popularity damping (log_popularity), a per-market prior.
+    Built by item_priors."""
+
+    __slots__ = ("values", "n_items")
+
+    def __init__(self, values: torch.Tensor):
+        if (values.dtype != torch.float32 or values.dim() != 2 or values.shape[0] < 1
+                or values.shape[1] < 1):
+            raise ValueError(f"values must be fp32 [P >= 1, V >= 1], got {values.dtype} "
+                             f"{tuple(values.shape)}")
+        self.values = values.contiguous()
+        self.n_items = values.shape[1]
+
+    @property
+    def n_priors(self) -> int:
+        return self.values.shape[0]
+
+    def to(self, device) -> "ItemPriors":
+        """The same priors on `device` (itself when already there)."""
+        values = self.values.to(device)
+        return self if values is self.values else ItemPriors(values)
+
+
+def item_priors(values, n_items: int | None = None, device=None) -> ItemPriors:
+    """ItemPriors from a float tensor [V] (P = 1) or [P, V], or a sequence of P
+    sequences of V numbers; stored as fp32, contiguous.  n_items, when given,
+    must be V.  inf and NaN are values like any other: +inf lifts an item to
+    the top, -inf sinks it without hiding it, NaN drops it for the rows that
+    take that prior.  The values then move to `device`."""
+    v = values if isinstance(values, torch.Tensor) else torch.as_tensor(values)
+    if not v.dtype.is_floating_point:
+        if isinstance(values, torch.Tensor):
+            raise ValueError(f"values must be a float tensor, got {v.dtype}")
+        v = v.to(torch.float32)
+    if v.dim() == 1:
+        v = v[None]
+    if v.dim() != 2 or v.shape[0] < 1 or v.shape[1] < 1:
+        raise ValueError(f"values must be [V] or [P, V], got {tuple(v.shape)}")
+    if n_items is not None and int(n_items) != v.shape[1]:
+        raise ValueError(f"n_items = {n_items} but the values cover {v.shape[1]} items")
+    v = v.detach().to(torch.float32).contiguous()
+    return ItemPriors(v if device is None else v.to(device))
+
+
+def log_popularity(counts, smoothing: float = 1.0, alpha: float = 1.0) -> torch.Tensor:
+    """fp32 [V]: alpha * log(counts + smoothing), normalised by its logsumexp —
+    the log of the smoothed, alpha-tempered popularity distribution.  With
+    data.train_item_counts it is a prior (item_priors), and prior_weight =
+    -beta damps popular items at serving time."""
+    c = torch.as_tensor(counts).to(torch.float64)
+    if c.dim() != 1 or c.numel() < 1:
+        raise ValueError(f"counts must be [V >= 1], got {tuple(c.shape)}")
+    logq = float(alpha) * torch.log(c + float(smoothing))
+    return (logq - torch.logsumexp(logq, 0)).to(torch.float32)
+
+
+def _check_prior(prior, prior_rows, prior_weight, B: int, V: int, device):
+    """top_items' and target_ranks' prior arguments -> (prior on `device`,
+    prior_rows int64 [B] on `device` or None, prior_weight fp32 [B] on `device`
+    or None), all None without a prior.  prior_rows is moved, not read (-1: no
+    prior; a value outside [-1, P): the row selects nothing)."""
+    if prior is None:
+        if prior_rows is not None or prior_weight is not None:
+            raise ValueError("prior_rows / prior_weight without prior")
+        return None, None, None
+    if not isinstance(prior, ItemPriors):
+        raise TypeError("prior must be an ItemPriors (scoring.item_priors)")
+    if prior.n_items != V:
+        raise ValueError(f"prior covers {prior.n_items} items, the table has {V}")
+    if prior_rows is not None:
+        if not isinstance(prior_rows, torch.Tensor) or prior_rows.shape != (B,):
+            raise ValueError(f"prior_rows must be [B] = [{B}], got "
+                             f"{tuple(getattr(prior_rows, 'shape', ()))}")
+        prior_rows = prior_rows.to(device=device, dtype=torch.int64)
+    if isinstance(prior_weight, torch.Tensor):
+        if prior_weight.shape != (B,) or not prior_weight.dtype.is_floating_point:
+            raise ValueError(f"a tensor prior_weight must be float [B] = [{B}], got "
+                             f"{prior_weight.dtype} {tuple(prior_weight.shape)}")
+        prior_weight = prior_weight.detach().to(device=device, dtype=torch.float32)
+    elif prior_weight is not None:
+        prior_weight = torch.full((B,), float(prior_weight), dtype=torch.float32, device=device)
+    return prior.to(device), prior_rows, prior_weight
+
+
+def _adjusted(scores, prior: ItemPriors, prior_rows, prior_weight):
+    """(adj fp32 [B, V], none bool [B]) by the kernels' rule: adj = scores +
+    (w[:, None] * values[p]), product and sum each rounded to fp32, for rows
+    with p in [0, P); the scores themselves (a select) for p = -1; none marks
+    the rows whose p is outside [-1, P), which select nothing."""
+    B = scores.shape[0]
+    dev = scores.device
+    n = prior.n_priors
+    p = torch.zeros(B, dtype=torch.int64, device=dev) if prior_rows is None else prior_rows
+    w = torch.ones(B, dtype=torch.float32, device=dev) if prior_weight is None else prior_weight
+    term = w[:, None] * prior.values[p.clamp(0, n - 1)]
+    adj = torch.where(((p >= 0) & (p < n))[:, None], scores + term, scores)
+    return adj, (p < -1) | (p >= n)
+
+
+def _target_ranks_torch(seq, table, target, first_item=1, allow=None, allow_rows=None,
+                        prior=None, prior_rows=None, prior_weight=None, scores=None):
+    """target_ranks' contract in plain torch on the [B, V] matrix (scores:
+    the model scores to use instead of seq @ table.T)."""
+    scores = seq.float() @ table.float().t() if scores is None else scores
+    B, V = scores.shape
+    dev = scores.device
+    target = target.to(device=dev, dtype=torch.int64)
+    bad = (target < 0) | (target >= V)
+    tc = target.clamp(0, V - 1)
+    cols = torch.arange(V, device=dev)[None, :]
+    sel = (cols >= int(first_item)) & (cols != tc[:, None])
+    allow, allow_rows = _check_allow(allow, allow_rows, B, V, dev)
+    if allow is not None:
+        ok = _allowed_mask(allow, allow_rows, B)
+        sel &= ok
+        bad |= ~ok.gather(1, tc[:, None])[:, 0]
+    prior, prior_rows, prior_weight = _check_prior(prior, prior_rows, prior_weight, B, V, dev)
+    if prior is not None:
+        scores, none = _adjusted(scores, prior, prior_rows, prior_weight)
+        bad |= none
+    ts = scores.gather(1, tc[:, None])
+    bad |= torch.isnan(ts[:, 0])
+    minus = torch.full((B,), -1, dtype=torch.int64, device=dev)
+    n_gt = torch.where(bad, minus, (sel & (scores > ts)).sum(1))
+    n_eq = torch.where(bad, minus, (sel & (scores == ts)).sum(1))
+    return n_gt, n_eq
+
+
 def target_ranks(seq: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
                  first_item: int = 1, allow: ItemFilters | None = None,
-                 allow_rows: torch.Tensor | None = None):
+                 allow_rows: torch.Tensor | None = None, prior: ItemPriors | None = None,
+                 prior_rows: torch.Tensor | None = None, prior_weight=None):
     """(n_greater, n_equal) over items [first_item, V) other than the target.
 
     first_item = 1 excludes the padding item 0, as RecBole's full-sort
     evaluation does (scores[:, 0] = -inf) and as run_with_unseen.py:237 does
     (scores[1:]).  allow / allow_rows (top_items' arguments): only the items
     that the row's filter allows are counted, and a target that it does not
-    allow gives -1, -1, which rank_metrics drops."""
+    allow gives -1, -1, which rank_metrics drops.  prior / prior_rows /
+    prior_weight (top_items' arguments): the counts compare adjusted scores,
+    the target's included (rb_item_rank_prior); a target whose adjusted score
+    is NaN, or whose row's prior index is outside [-1, P), gives -1, -1."""
     if not supported(seq, table):
         raise kernels.RecBLRNativeError("target_ranks needs fp32 CUDA tensors with d in "
                                         f"{kernels.ITEM_DIMS}")
     allow, allow_rows = _check_allow(allow, allow_rows, seq.shape[0], table.shape[0], seq.device)
+    prior, prior_rows, prior_weight = _check_prior(prior, prior_rows, prior_weight, seq.shape[0],
+                                                   table.shape[0], seq.device)
+    if prior is not None:
+        return kernels.item_rank(seq.detach(), table.detach(), target, first_item=first_item,
+                                 allow=allow.words if allow is not None else None,
+                                 allow_rows=allow_rows, prior=prior.values,
+                                 prior_rows=prior_rows, prior_weight=prior_weight)
     if allow is None:
         return kernels.item_rank(seq.detach(), table.detach(), target, first_item=first_item)
     return kernels.item_rank(seq.detach(), table.detach(), target, first_item=first_item,
@@ -778,12 +922,21 @@ def target_ranks(seq: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
 
 
 def _top_items_torch(seq, table, k, first_item, exclude, allow=None, allow_rows=None,
-                     groups=None, max_per_group=None):
-    """top_items' contract in plain torch (any device, any d, any k, any group id)."""
-    scores = seq.float() @ table.float().t()
+                     groups=None, max_per_group=None, prior=None, prior_rows=None,
+                     prior_weight=None, scores=None):
+    """top_items' contract in plain torch (any device, any d, any k, any group
+    id).  scores: the [B, V] model scores to select on instead of seq @ table.T
+    (full_sort_scores' matrix makes this the kernels' reference, bit for bit)."""
+    scores = seq.float() @ table.float().t() if scores is None else scores
     B, V = scores.shape
     dev = scores.device
+    prior, prior_rows, prior_weight = _check_prior(prior, prior_rows, prior_weight, B, V, dev)
+    none = None
+    if prior is not None:
+        scores, none = _adjusted(scores, prior, prior_rows, prior_weight)
     drop = torch.isnan(scores)
+    if none is not None:
+        drop |= none[:, None]
     drop[:, :min(max(int(first_item), 0), V)] = True
     allow, allow_rows = _check_allow(allow, allow_rows, B, V, dev)
     if allow is not None:
@@ -830,7 +983,8 @@ def _top_items_torch(seq, table, k, first_item, exclude, allow=None, allow_rows=
 def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 1,
               exclude: torch.Tensor | None = None, allow: ItemFilters | None = None,
               allow_rows: torch.Tensor | None = None, groups: ItemGroups | None = None,
-              max_per_group: int | None = None):
+              max_per_group: int | None = None, prior: ItemPriors | None = None,
+              prior_rows: torch.Tensor | None = None, prior_weight=None):
     """Each row's k best items: (ids int64 [B, k], scores fp32 [B, k]).
 
     Selects over items in [first_item, V) not listed in exclude [B, E] (int64;
@@ -863,7 +1017,26 @@ def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 
     tail is id -1 / score -inf.  The selection kernel applies the cap in its
     own sweep (rb_item_topk_grouped, exact: no depth to guess); m >= k, or
     groups that are all distinct or all -1, give the uncapped result bit for
-    bit.  A group id above kernels.ITEM_GROUP_ID_MAX takes the torch path."""
+    bit.  A group id above kernels.ITEM_GROUP_ID_MAX takes the torch path.
+
+    prior (an ItemPriors over the table's V items, from item_priors) ranks by
+    the adjusted score adj = score + (w_b * prior.values[p_b, item]) instead of
+    the model score: the product is rounded to fp32, then the sum (no fused
+    multiply-add), so full_sort_scores(seq, table) + w[:, None] * values[p]
+    gives the same bits on any device.  prior_rows [B] (int64, any device;
+    moved to the GPU but never read on the host) is p: None means prior 0 for
+    every row, -1 no prior for that row (a select, not an addition of zero: the
+    un-priored result bit for bit, a -0.0 score included), and a value outside
+    [-1, P) selects nothing.  prior_weight is w: None (1.0), a Python float,
+    or a float [B] tensor.  Every rule above then applies to adj: the order is
+    (adj descending, id ascending), a NaN adj is never selected (a NaN prior,
+    inf - inf), a -inf prior sinks an item without hiding it, exclude,
+    first_item, the filter and the cap apply unchanged, and the scores returned
+    are adjusted scores.  The kernel adds the term to a tile's scores before
+    its threshold compare (rb_item_topk_prior); without prior the calls are the
+    ones above.  Candidate reranking (top_candidates, candidate_ranks) takes no
+    prior: candidate_scores, plus a gather of the prior at the candidates, plus
+    order_candidates already does that without a [B, V] matrix."""
     k = int(k)
     if k < 1:
         raise ValueError(f"k = {k} must be positive")
@@ -873,10 +1046,20 @@ def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 
         raise ValueError(f"exclude must be [B, E], got {tuple(exclude.shape)}")
     allow, allow_rows = _check_allow(allow, allow_rows, seq.shape[0], table.shape[0], seq.device)
     groups, m = _check_groups(groups, max_per_group, table.shape[0], seq.device)
+    prior, prior_rows, prior_weight = _check_prior(prior, prior_rows, prior_weight, seq.shape[0],
+                                                   table.shape[0], seq.device)
     if supported(seq, table) and k <= kernels.ITEM_TOPK_MAX and (
             groups is None or groups.n_groups <= kernels.ITEM_GROUP_ID_MAX + 1):
         if exclude is not None:
             exclude = exclude.to(device=seq.device, dtype=torch.int64)
+        if prior is not None:
+            return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
+                                     exclude=exclude,
+                                     allow=allow.words if allow is not None else None,
+                                     allow_rows=allow_rows,
+                                     groups=groups.ids if groups is not None else None,
+                                     max_per_group=m, prior=prior.values, prior_rows=prior_rows,
+                                     prior_weight=prior_weight)
         if groups is not None:
             return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
                                      exclude=exclude,
@@ -888,7 +1071,7 @@ def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 
         return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
                                  exclude=exclude, allow=allow.words, allow_rows=allow_rows)
     return _top_items_torch(seq.detach(), table.detach(), k, first_item, exclude, allow,
-                            allow_rows, groups, m)
+                            allow_rows, groups, m, prior, prior_rows, prior_weight)
 
 
 # ---- candidate lists: scoring chosen items (csrc/candidates.hip) --------------------

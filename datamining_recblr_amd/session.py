@@ -954,7 +954,7 @@ def prefill(model, state: SessionState, item_seq, item_seq_len, slots=None,
 @torch.no_grad()
 def recommend(model, state: SessionState, items=None, slots=None, k: int = 10,
               exclude_seen: bool = True, first_item: int = 1, allow=None, allow_rows=None,
-              groups=None, max_per_group=None):
+              groups=None, max_per_group=None, prior=None, prior_rows=None, prior_weight=None):
     """Click in, recommendation list out: ``(ids int64 [B, k], scores fp32
     [B, k])``, each row's k best items by ``scoring.top_items`` for its slot's
     seq_output after the call's events.
@@ -978,13 +978,16 @@ def recommend(model, state: SessionState, items=None, slots=None, k: int = 10,
     catalogue filter, as ``scoring.top_items`` takes them: the row's filter
     index, None for filter 0 everywhere, -1 for no filter.  groups
     (``scoring.item_groups``) and max_per_group cap every list at that many
-    items of one group, again as ``scoring.top_items`` takes them."""
+    items of one group, again as ``scoring.top_items`` takes them.  prior
+    (``scoring.item_priors``), prior_rows [B] and prior_weight (a float or a
+    float [B] tensor) rank each row by score + weight * prior[item], likewise."""
     from .scoring import top_items
 
     p, y, seen, dead = _serve_rows(model, state, items, slots, exclude_seen, "recommend")
     ids, scores = top_items(y, p.t["item_embedding.weight"], k, first_item,
                             exclude=seen if exclude_seen else None, allow=allow,
-                            allow_rows=allow_rows, groups=groups, max_per_group=max_per_group)
+                            allow_rows=allow_rows, groups=groups, max_per_group=max_per_group,
+                            prior=prior, prior_rows=prior_rows, prior_weight=prior_weight)
     ids.masked_fill_(dead[:, None], -1)
     scores.masked_fill_(dead[:, None], float("-inf"))
     return ids, scores

@@ -51,7 +51,9 @@
  * declared here and defined in csrc/capi.hip, and RB_ABI_VERSION is bumped.
  * The all-position training loss's entry points (the same library, the same
  * version) are declared in recblr_dense.h, its sampled pairwise loss's in
- * recblr_pairs.h, candidate-list scoring's in recblr_candidates.h.
+ * recblr_pairs.h, candidate-list scoring's in recblr_candidates.h, the
+ * catalogue filters' in recblr_filters.h, the diversity caps' in
+ * recblr_groups.h, the score priors' in recblr_priors.h.
  */
 #ifndef RECBLR_HIP_H
 #define RECBLR_HIP_H
@@ -75,7 +77,7 @@ typedef uint16_t rb_bf16;
 #define RB_TILE 16
 
 /* ABI version; bumped on any signature change.  rb_version() returns it. */
-#define RB_ABI_VERSION 53
+#define RB_ABI_VERSION 54
 int rb_version(void);
 
 /* Human-readable description of the last error on the calling thread. */
