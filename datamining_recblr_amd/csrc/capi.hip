@@ -121,39 +121,47 @@ int conv_silu_bwd(const char* fn, const T* x, int64_t x_rs, const float* w, cons
                             seq_offsets, as_stream(stream));
 }
 
-// y_last / batch_row: rb_gate_scan_fwd_last (y NULL, y_rs = H); NULL otherwise
+// y_last / batch_row: rb_gate_scan_fwd_last (y NULL, y_rs = H); NULL otherwise.
+// z_last: its sparse-z mode (z NULL, z_rs = H)
 template <typename T>
 int gate_scan_fwd(const char* fn, const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs,
                   const T* z, int64_t z_rs, const float* lam, const float* gate_b,
                   const float* h0, int64_t h0_bs, T* y, int64_t y_rs, float* carries, int64_t B,
                   int64_t L, int64_t H, const int64_t* seq_offsets, void* stream,
-                  T* y_last = nullptr, const int64_t* batch_row = nullptr) {
-  if (!rg || !xc || !z || !lam || !(y || y_last)) return fail(fn, "null pointer");
+                  T* y_last = nullptr, const int64_t* batch_row = nullptr,
+                  const T* z_last = nullptr) {
+  if (!rg || !xc || !(z || z_last) || !lam || !(y || y_last)) return fail(fn, "null pointer");
+  if (z && z_last) return fail(fn, "give z or z_last, not both");
   if (h0_bs != 0 && h0_bs < H) return fail(fn, "h0 batch stride must be 0 or >= H");
   if (rg_rs < 2 * H || xc_rs < H || z_rs < H || y_rs < H) return fail(fn, "row stride too small");
   if (int r = check_dims(B, L, H, max4(rg_rs, xc_rs, z_rs, y_rs))) return r;
   return launch_gate_fwd<T>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, h0, h0_bs, y, y_rs,
-                            carries, B, L, H, seq_offsets, as_stream(stream), y_last, batch_row);
+                            carries, B, L, H, seq_offsets, as_stream(stream), y_last, batch_row,
+                            z_last);
 }
 
-// dy_last / batch_row: rb_gate_scan_bwd_last (dy NULL); NULL otherwise
+// dy_last / batch_row: rb_gate_scan_bwd_last (dy NULL); NULL otherwise.
+// z_last / dz_last: its sparse-z mode (z, dz NULL, z_rs = dz_rs = H)
 template <typename T>
 int gate_scan_bwd(const char* fn, const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs,
                   const T* z, int64_t z_rs, const float* lam, const float* gate_b,
                   const float* carries, const T* dy, T* drg, int64_t drg_rs, T* dxc,
                   int64_t dxc_rs, T* dz, int64_t dz_rs, float* part, float* dh0_part, int64_t B,
                   int64_t L, int64_t H, const int64_t* seq_offsets, void* stream,
-                  const T* dy_last = nullptr, const int64_t* batch_row = nullptr) {
-  if (!rg || !xc || !z || !lam || !carries || !(dy || dy_last) || !drg || !dxc || !dz || !part ||
-      !dh0_part)
+                  const T* dy_last = nullptr, const int64_t* batch_row = nullptr,
+                  const T* z_last = nullptr, T* dz_last = nullptr) {
+  if (!rg || !xc || !(z || z_last) || !lam || !carries || !(dy || dy_last) || !drg || !dxc ||
+      !(dz || dz_last) || !part || !dh0_part)
     return fail(fn, "null pointer");
+  if ((z_last != nullptr) != (dz_last != nullptr) || (z && z_last) || (dz && dz_last))
+    return fail(fn, "give z and dz, or z_last and dz_last");
   if (rg_rs < 2 * H || xc_rs < H || z_rs < H || drg_rs < 2 * H || dxc_rs < H || dz_rs < H)
     return fail(fn, "row stride too small");
   if (int r = check_dims(B, L, H, max4(max4(rg_rs, xc_rs, z_rs, drg_rs), dz_rs, dxc_rs, H)))
     return r;
   return launch_gate_bwd<T>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, carries, dy, drg, drg_rs,
                             dxc, dxc_rs, dz, dz_rs, part, dh0_part, B, L, H, seq_offsets,
-                            as_stream(stream), dy_last, batch_row);
+                            as_stream(stream), dy_last, batch_row, z_last, dz_last);
 }
 
 // rb_bf16 (raw bits in the C header) is the kernels' bf16_t
@@ -235,24 +243,28 @@ int rb_gate_scan_bwd(const float* rg, int64_t rg_rs, const float* xc, int64_t xc
 }
 
 int rb_gate_scan_fwd_last(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
-                          const float* z, int64_t z_rs, const float* lam, const float* gate_b,
-                          const float* h0, int64_t h0_bs, float* y_last, float* carries,
-                          int64_t B, int64_t L, int64_t H, const int64_t* seq_offsets,
-                          const int64_t* batch_row, void* stream) {
-  return gate_scan_fwd<float>(__func__, rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, h0, h0_bs,
-                              nullptr, H, carries, B, L, H, seq_offsets, stream, y_last,
-                              batch_row);
+                          const float* z, int64_t z_rs, const float* z_last, const float* lam,
+                          const float* gate_b, const float* h0, int64_t h0_bs, float* y_last,
+                          float* carries, int64_t B, int64_t L, int64_t H,
+                          const int64_t* seq_offsets, const int64_t* batch_row, void* stream) {
+  if (!y_last) return fail(__func__, "null pointer");
+  return gate_scan_fwd<float>(__func__, rg, rg_rs, xc, xc_rs, z, z_last ? H : z_rs, lam, gate_b,
+                              h0, h0_bs, nullptr, H, carries, B, L, H, seq_offsets, stream,
+                              y_last, batch_row, z_last);
 }
 
 int rb_gate_scan_bwd_last(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
-                          const float* z, int64_t z_rs, const float* lam, const float* gate_b,
-                          const float* carries, const float* dy_last, float* drg,
-                          int64_t drg_rs, float* dxc, int64_t dxc_rs, float* dz, int64_t dz_rs,
-                          float* part, float* dh0_part, int64_t B, int64_t L, int64_t H,
-                          const int64_t* seq_offsets, const int64_t* batch_row, void* stream) {
-  return gate_scan_bwd<float>(__func__, rg, rg_rs, xc, xc_rs, z, z_rs, lam, gate_b, carries,
-                              nullptr, drg, drg_rs, dxc, dxc_rs, dz, dz_rs, part, dh0_part, B, L,
-                              H, seq_offsets, stream, dy_last, batch_row);
+                          const float* z, int64_t z_rs, const float* z_last, const float* lam,
+                          const float* gate_b, const float* carries, const float* dy_last,
+                          float* drg, int64_t drg_rs, float* dxc, int64_t dxc_rs, float* dz,
+                          int64_t dz_rs, float* dz_last, float* part, float* dh0_part, int64_t B,
+                          int64_t L, int64_t H, const int64_t* seq_offsets,
+                          const int64_t* batch_row, void* stream) {
+  if (!dy_last) return fail(__func__, "null pointer");
+  return gate_scan_bwd<float>(__func__, rg, rg_rs, xc, xc_rs, z, z_last ? H : z_rs, lam, gate_b,
+                              carries, nullptr, drg, drg_rs, dxc, dxc_rs, dz,
+                              dz_last ? H : dz_rs, part, dh0_part, B, L, H, seq_offsets, stream,
+                              dy_last, batch_row, z_last, dz_last);
 }
 
 // ---- bf16 storage variants (fp32 arithmetic; the same bodies as the fp32 forms) ----

@@ -370,20 +370,22 @@ template <typename T>
 int launch_conv_bwd(const T* x, int64_t x_rs, const float* w, const float* bias, const T* g1,
                     const T* g2, T* dx, int64_t dx_rs, float* dw_part, float* db_part, int64_t B,
                     int64_t L, int64_t H, int64_t K, const int64_t* offs, hipStream_t st);
-// y_last / dy_last [B, H] (rows permuted by order): rb_gate_scan_*_last
+// y_last / dy_last [B, H] (rows permuted by order): rb_gate_scan_*_last;
+// z_last / dz_last [B, H] (rows likewise, fp32): their sparse-z mode, z and dz unused
 template <typename T>
 int launch_gate_fwd(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* z,
                     int64_t z_rs, const float* lam, const float* gb, const float* h0,
                     int64_t h0_bs, T* y, int64_t y_rs, float* carries, int64_t B, int64_t L,
                     int64_t H, const int64_t* offs, hipStream_t st, T* y_last = nullptr,
-                    const int64_t* order = nullptr);
+                    const int64_t* order = nullptr, const T* z_last = nullptr);
 template <typename T>
 int launch_gate_bwd(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* z,
                     int64_t z_rs, const float* lam, const float* gb, const float* carries,
                     const T* dy, T* drg, int64_t drg_rs, T* dxc, int64_t dxc_rs, T* dz,
                     int64_t dz_rs, float* part, float* dh0_part, int64_t B, int64_t L, int64_t H,
                     const int64_t* offs, hipStream_t st, const T* dy_last = nullptr,
-                    const int64_t* order = nullptr);
+                    const int64_t* order = nullptr, const T* z_last = nullptr,
+                    T* dz_last = nullptr);
 int launch_add_ln_fwd(const float* a, const int64_t* idx, int64_t nidx, const DropSpec& drop,
                       const float* r, const float* gamma, const float* beta, float eps, float* y,
                       float* s_out, float* mean, float* rstd, int64_t rows, int64_t d,

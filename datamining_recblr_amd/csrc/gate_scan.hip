@@ -20,22 +20,26 @@
 namespace rb {
 namespace {
 
-template <typename T, int VEC, int TC>
+// ZL (sparse z, the last-position kernels): z is given only at each
+// sequence's last row (z_last [B, H], indexed like y_last / dy_last), so the
+// tile buffers carry no z slot and no row of z is loaded
+template <typename T, int VEC, int TC, bool ZL = false>
 struct FwdIn {
-  RawVec<T, VEC> r[TC], i[TC], x[TC], z[TC];
+  RawVec<T, VEC> r[TC], i[TC], x[TC], z[ZL ? 1 : TC];
 };
 
 // backward operands as loaded: raw storage words (bf16 stays packed until the
 // tile is processed, so a prefetched tile costs half the registers)
-template <typename T, int VEC, int TC>
+template <typename T, int VEC, int TC, bool ZL = false>
 struct BwdIn {
-  RawVec<T, VEC> r[TC], i[TC], x[TC], z[TC], g[TC];
+  RawVec<T, VEC> r[TC], i[TC], x[TC], z[ZL ? 1 : TC], g[TC];
 };
 
 // PF: software-prefetch the next tile's operands before computing this one
 // (two register buffers), so a wave keeps its loads in flight across the
 // shuffle/compute/store phase of the previous tile.
-template <typename T, int VEC, int Q, int TC, bool PF>
+// ZL: z points at z_last [B, H] (z_rs unused) and y_last is set.
+template <typename T, int VEC, int Q, int TC, bool PF, bool ZL = false>
 __global__ void __launch_bounds__(256)
 k_gate_scan_fwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, int xc_rs,
                 const T* __restrict__ z, int z_rs, const float* __restrict__ lam,
@@ -69,10 +73,12 @@ k_gate_scan_fwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
   }
   const T* rgb = rg + row0 * rg_rs + cc;
   const T* xcb = xc + row0 * xc_rs + cc;
-  const T* zb = z + row0 * z_rs + cc;
+  const T* zb = ZL ? nullptr : z + row0 * z_rs + cc;
   T* yb = y + row0 * y_rs + cc;
 
   float nsp[VEC], carry[VEC], br[VEC], bi[VEC];
+  [[maybe_unused]] float zl[VEC];   // ZL: z at this sequence's last row
+  if constexpr (ZL) ldc(zl, z + (order ? order[b] : b) * H + cc);
   ldc(nsp, lam + cc);
 #pragma unroll
   for (int v = 0; v < VEC; ++v) nsp[v] = -softplus_f(nsp[v]);
@@ -92,7 +98,7 @@ k_gate_scan_fwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
   const int nT = (L + TILE - 1) / TILE;          // tiles of this row
   const int nTc = (Lmax + TILE - 1) / TILE;      // carries row stride
 
-  auto load = [&](FwdIn<T, VEC, TC>& in, int tile) {
+  auto load = [&](FwdIn<T, VEC, TC, ZL>& in, int tile) {
     const int t0 = tile * TILE + q * TC;
 #pragma unroll
     for (int j = 0; j < TC; ++j) {
@@ -100,19 +106,19 @@ k_gate_scan_fwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
       ld_raw(in.r[j], rgb + t * rg_rs);
       ld_raw(in.i[j], rgb + t * rg_rs + H);
       ld_raw(in.x[j], xcb + t * xc_rs);
-      ld_raw(in.z[j], zb + t * z_rs);
+      if constexpr (!ZL) ld_raw(in.z[j], zb + t * z_rs);
     }
   };
-  auto process = [&](const FwdIn<T, VEC, TC>& raw, int tile) {
+  auto process = [&](const FwdIn<T, VEC, TC, ZL>& raw, int tile) {
     struct {
-      float r[TC][VEC], i[TC][VEC], x[TC][VEC], z[TC][VEC];
+      float r[TC][VEC], i[TC][VEC], x[TC][VEC], z[ZL ? 1 : TC][VEC];
     } in;
 #pragma unroll
     for (int j = 0; j < TC; ++j) {
       unpack_raw(in.r[j], raw.r[j]);
       unpack_raw(in.i[j], raw.i[j]);
       unpack_raw(in.x[j], raw.x[j]);
-      unpack_raw(in.z[j], raw.z[j]);
+      if constexpr (!ZL) unpack_raw(in.z[j], raw.z[j]);
     }
     if (carries != nullptr && q == 0 && cv) stv(carries + (b * nTc + tile) * H + c0, carry);
     const int t0 = tile * TILE + q * TC;
@@ -163,9 +169,10 @@ k_gate_scan_fwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         cin[v] = cin[v] * in.r[j][v] + in.x[j][v];
-        out[v] = fsilu(in.z[j][v]) * cin[v];
+        if constexpr (ZL) out[v] = fsilu(zl[v]) * cin[v];   // stored at the last row only
+        else out[v] = fsilu(in.z[j][v]) * cin[v];
       }
-      if (y_last != nullptr) {   // only each sequence's last position is kept: [B, H]
+      if (ZL || y_last != nullptr) {   // only each sequence's last position is kept: [B, H]
         if (cv && t0 + j == L - 1) stv(y_last + (order ? order[b] : b) * H + c0, out);
       } else if (cv && t0 + j < L) {
         stv(yb + (t0 + j) * y_rs, out);
@@ -173,7 +180,7 @@ k_gate_scan_fwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
     }
   };
 
-  FwdIn<T, VEC, TC> bufA, bufB;
+  FwdIn<T, VEC, TC, ZL> bufA, bufB;
   if constexpr (PF) {
     load(bufA, 0);
     for (int tile = 0; tile < nT; tile += 2) {
@@ -241,7 +248,11 @@ __device__ __forceinline__ void scan_from_upper(float& A, float& E, int q) {
   }
 }
 
-template <typename T, int VEC, int Q, int TC, bool PF, int VH = VEC>
+// ZL: z / dz point at z_last / dz_last [B, H] (rows as dy_last's; z_rs and
+// dz_rs unused) and dy_last is set.  Away from a sequence's last row dy = 0, so
+// z enters nothing there (gs = 0, dz = 0): those rows run the same operations
+// on z = 0 and store no dz.
+template <typename T, int VEC, int Q, int TC, bool PF, int VH = VEC, bool ZL = false>
 __global__ void __launch_bounds__(256, VH < VEC ? 2 : 1)   // channel passes: 2 waves per SIMD
 k_gate_scan_bwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, int xc_rs,
                 const T* __restrict__ z, int z_rs, const float* __restrict__ lam,
@@ -273,6 +284,7 @@ k_gate_scan_bwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
   int L = 0;
   const T *rgb = nullptr, *xcb = nullptr, *zb = nullptr, *dyb = nullptr;
   T *drgb = nullptr, *dxcb = nullptr, *dzb = nullptr;
+  [[maybe_unused]] float zl[VEC];   // ZL: z at the bound sequence's last row
   auto bind = [&](int64_t bs) {
     b = bs;
     bl = order != nullptr ? order[bs] : bs;
@@ -285,11 +297,16 @@ k_gate_scan_bwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
     }
     rgb = rg + row0 * rg_rs + cc;
     xcb = xc + row0 * xc_rs + cc;
-    zb = z + row0 * z_rs + cc;
     dyb = dy + row0 * H + cc;
     drgb = drg + row0 * drg_rs + cc;
     dxcb = dxc + row0 * dxc_rs + cc;
-    dzb = dz + row0 * dz_rs + cc;
+    if constexpr (ZL) {
+      ldc(zl, z + bl * H + cc);
+      dzb = dz + bl * H + cc;
+    } else {
+      zb = z + row0 * z_rs + cc;
+      dzb = dz + row0 * dz_rs + cc;
+    }
   };
 
   float lamv[VEC], nsp[VEC], br[VEC], bi[VEC];
@@ -308,7 +325,7 @@ k_gate_scan_bwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
   for (int v = 0; v < VEC; ++v) acc_v[v] = acc_r[v] = acc_i[v] = 0.0f;
   const int nTc = (Lmax + TILE - 1) / TILE;      // carries row stride
 
-  auto load = [&](BwdIn<T, VEC, TC>& in, int tile) {
+  auto load = [&](BwdIn<T, VEC, TC, ZL>& in, int tile) {
     const int t0 = tile * TILE + q * TC;
 #pragma unroll
     for (int j = 0; j < TC; ++j) {
@@ -316,7 +333,7 @@ k_gate_scan_bwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
       ld_raw(in.r[j], rgb + t * rg_rs);
       ld_raw(in.i[j], rgb + t * rg_rs + H);
       ld_raw(in.x[j], xcb + t * xc_rs);
-      ld_raw(in.z[j], zb + t * z_rs);
+      if constexpr (!ZL) ld_raw(in.z[j], zb + t * z_rs);
       if (dy_last == nullptr) {
         ld_raw(in.g[j], dyb + t * H);
       } else if (t == L - 1) {   // dy is zero except at each sequence's last position
@@ -332,7 +349,8 @@ k_gate_scan_bwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
   // VEC-wide vectors after the last pass — a third of the live registers.
   constexpr bool SPLIT = VH < VEC;
   static_assert(VEC % VH == 0 && (!SPLIT || VH % 2 == 0), "channel passes");
-  auto process = [&](const BwdIn<T, VEC, TC>& raw, int tile) {
+  static_assert(!(ZL && SPLIT), "sparse z: fp32 activations, one channel pass");
+  auto process = [&](const BwdIn<T, VEC, TC, ZL>& raw, int tile) {
     float hcar[VEC];
     ldc(hcar, carries + (b * nTc + tile) * H + cc);
     const int t0 = tile * TILE + q * TC;
@@ -341,14 +359,15 @@ k_gate_scan_bwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
 #pragma unroll
     for (int h0 = 0; h0 < VEC; h0 += VH) {
       struct {
-        float r[TC][VH], i[TC][VH], x[TC][VH], z[TC][VH], g[TC][VH];
+        float r[TC][VH], i[TC][VH], x[TC][VH], z[ZL ? 1 : TC][VH], g[TC][VH];
       } in;
 #pragma unroll
       for (int j = 0; j < TC; ++j) {
         // (channel passes: this pass's words through an empty volatile asm,
         // ordered after the previous pass's results below, so the compiler
         // cannot interleave the passes and the register saving is real)
-        RawVec<T, VEC> wr = raw.r[j], wi = raw.i[j], wx = raw.x[j], wz = raw.z[j], wg = raw.g[j];
+        RawVec<T, VEC> wr = raw.r[j], wi = raw.i[j], wx = raw.x[j], wz = raw.z[ZL ? 0 : j],
+                       wg = raw.g[j];
         if constexpr (SPLIT) {
           opaque_part<VH>(wr, h0);
           opaque_part<VH>(wi, h0);
@@ -359,7 +378,7 @@ k_gate_scan_bwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
         unpack_part(in.r[j], wr, h0);
         unpack_part(in.i[j], wi, h0);
         unpack_part(in.x[j], wx, h0);
-        unpack_part(in.z[j], wz, h0);
+        if constexpr (!ZL) unpack_part(in.z[j], wz, h0);
         unpack_part(in.g[j], wg, h0);
       }
 #pragma unroll
@@ -383,7 +402,9 @@ k_gate_scan_bwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
           si[j][v] = fsigm(in.i[j][v]);
           sq[j][v] = fsqrt(1.0f - a * a + 1e-8f);
           bp[j][v] = ok ? sq[j][v] * si[j][v] * in.x[j][v] : 0.0f;
-          const float zz = in.z[j][v];
+          float zz;
+          if constexpr (ZL) zz = t0 + j == L - 1 ? zl[h0 + v] : 0.0f;
+          else zz = in.z[j][v];
           const float sz = fsigm(zz);
           const float g = ok ? in.g[j][v] : 0.0f;   // dy past the end contributes nothing
           in.g[j][v] = g;
@@ -439,7 +460,9 @@ k_gate_scan_bwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
           dzo[v] = (in.g[j][v] * cin[v]) * dsz[j][v];
         }
         if constexpr (SPLIT) pack_part(odz[j], dzo, h0);
-        else if (cv && ok) stv(dzb + (t0 + j) * dz_rs, dzo);
+        else if constexpr (ZL) {
+          if (cv && t0 + j == L - 1) stv(dzb, dzo);
+        } else if (cv && ok) stv(dzb + (t0 + j) * dz_rs, dzo);
       }
 #pragma unroll
       for (int j = TC - 1; j >= 0; --j) {
@@ -503,7 +526,7 @@ k_gate_scan_bwd(const T* __restrict__ rg, int rg_rs, const T* __restrict__ xc, i
     }
   };
 
-  BwdIn<T, VEC, TC> bufA, bufB;
+  BwdIn<T, VEC, TC, ZL> bufA, bufB;
   const int nseq = (pair && B - 1 - bw != bw) ? 2 : 1;
   for (int sq_i = 0; sq_i < nseq; ++sq_i) {
     bind(sq_i == 0 ? bw : B - 1 - bw);
@@ -581,7 +604,7 @@ bool vec_ok(int64_t H, std::initializer_list<int64_t> strides,
   return true;
 }
 
-template <typename T, int V, bool PF = true>
+template <typename T, int V, bool PF = true, bool ZL = false>
 int gate_fwd_v(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* z,
                int64_t z_rs, const float* lam, const float* gb, const float* h0, int64_t h0_bs,
                T* y, int64_t y_rs, float* carries, int64_t B, int64_t L, int64_t H,
@@ -589,13 +612,14 @@ int gate_fwd_v(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* 
   const int span = (kWave / kFwdQ) * V;
   const int ncw = (int)((H + span - 1) / span);
   const int64_t blocks = (B * ncw + 3) / 4;
-  hipLaunchKernelGGL((k_gate_scan_fwd<T, V, kFwdQ, kFwdTC, PF>), dim3((unsigned)blocks),
+  hipLaunchKernelGGL((k_gate_scan_fwd<T, V, kFwdQ, kFwdTC, PF, ZL>), dim3((unsigned)blocks),
                      dim3(256), 0, st, rg, (int)rg_rs, xc, (int)xc_rs, z, (int)z_rs, lam, gb,
                      h0, (int)h0_bs, y, (int)y_rs, carries, B, (int)L, (int)H, ncw, offs, y_last, order);
   return launch_status("rb_gate_scan_fwd");
 }
 
-template <typename T, int V, int Q = kBwdQ, int TC = kBwdTC, bool PF = false, int VH = V>
+template <typename T, int V, int Q = kBwdQ, int TC = kBwdTC, bool PF = false, int VH = V,
+          bool ZL = false>
 int gate_bwd_v(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* z,
                int64_t z_rs, const float* lam, const float* gb, const float* carries,
                const T* dy, T* drg, int64_t drg_rs, T* dxc, int64_t dxc_rs, T* dz, int64_t dz_rs,
@@ -607,7 +631,7 @@ int gate_bwd_v(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, const T* 
   const int pair = offs != nullptr && kBwdPair;
   const int64_t Bw = pair ? (B + 1) / 2 : B;
   const int64_t blocks = (Bw * ncw + 3) / 4;
-  hipLaunchKernelGGL((k_gate_scan_bwd<T, V, Q, TC, PF, VH>), dim3((unsigned)blocks),
+  hipLaunchKernelGGL((k_gate_scan_bwd<T, V, Q, TC, PF, VH, ZL>), dim3((unsigned)blocks),
                      dim3(256), 0, st, rg, (int)rg_rs, xc, (int)xc_rs, z, (int)z_rs, lam, gb,
                      carries, dy, drg, (int)drg_rs, dxc, (int)dxc_rs, dz, (int)dz_rs, part,
                      dh0_part, B, (int)L, (int)H, ncw, offs, pair, dy_last, order);
@@ -623,12 +647,25 @@ int launch_gate_fwd(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, cons
                     int64_t z_rs, const float* lam, const float* gb, const float* h0,
                     int64_t h0_bs, T* y, int64_t y_rs, float* carries, int64_t B, int64_t L,
                     int64_t H, const int64_t* offs, hipStream_t st, T* y_last,
-                    const int64_t* order) {
+                    const int64_t* order, const T* z_last) {
   constexpr int VW = sizeof(T) == 2 ? 4 : 2;
+  if (z_last != nullptr) {   // sparse z (fp32, with y_last): the kernels' z is z_last [B, H]
+    z = z_last;
+    z_rs = H;
+  }
   const auto strides = {rg_rs, xc_rs, z_rs, y_rs, h0_bs};
   const auto act = {(const void*)rg, (const void*)xc, (const void*)z, (const void*)y,
                     (const void*)y_last};
   const auto f32 = {(const void*)lam, (const void*)gb, (const void*)h0, (const void*)carries};
+  if constexpr (sizeof(T) == 4) {
+    if (z_last != nullptr) {
+      if (vec_ok<T, 2>(H, strides, act, f32))
+        return gate_fwd_v<T, 2, true, true>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gb, h0, h0_bs, y,
+                                            y_rs, carries, B, L, H, offs, st, y_last, order);
+      return gate_fwd_v<T, 1, true, true>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gb, h0, h0_bs, y,
+                                          y_rs, carries, B, L, H, offs, st, y_last, order);
+    }
+  }
   // bf16: no register prefetch (measured 3% faster at config 5, tools/kbench.hip)
   if (vec_ok<T, VW>(H, strides, act, f32))
     return gate_fwd_v<T, VW, sizeof(T) == 4>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gb, h0, h0_bs,
@@ -646,8 +683,13 @@ int launch_gate_bwd(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, cons
                     const T* dy, T* drg, int64_t drg_rs, T* dxc, int64_t dxc_rs, T* dz,
                     int64_t dz_rs, float* part, float* dh0_part, int64_t B, int64_t L, int64_t H,
                     const int64_t* offs, hipStream_t st, const T* dy_last,
-                    const int64_t* order) {
+                    const int64_t* order, const T* z_last, T* dz_last) {
   constexpr int VW = 4;
+  if (z_last != nullptr) {   // sparse z (fp32, with dy_last): z / dz are z_last / dz_last [B, H]
+    z = z_last;
+    dz = dz_last;
+    z_rs = dz_rs = H;
+  }
   const auto strides = {rg_rs, xc_rs, z_rs, drg_rs, dxc_rs, dz_rs};
   const auto act = {(const void*)rg, (const void*)xc, (const void*)z, (const void*)dy,
                     (const void*)drg, (const void*)dxc, (const void*)dz, (const void*)dy_last};
@@ -664,6 +706,21 @@ int launch_gate_bwd(const T* rg, int64_t rg_rs, const T* xc, int64_t xc_rs, cons
       return gate_bwd_v<T, VW, 4, 4, false, 2>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gb, carries,
                                                dy, drg, drg_rs, dxc, dxc_rs, dz, dz_rs, part,
                                                dh0_part, B, L, H, offs, st, dy_last, order);
+  }
+  if constexpr (sizeof(T) == 4) {
+    if (z_last != nullptr) {
+      if (vec_ok<T, VW>(H, strides, act, f32))
+        return gate_bwd_v<T, VW, kBwdQ, kBwdTC, false, VW, true>(
+            rg, rg_rs, xc, xc_rs, z, z_rs, lam, gb, carries, dy, drg, drg_rs, dxc, dxc_rs, dz,
+            dz_rs, part, dh0_part, B, L, H, offs, st, dy_last, order);
+      if (vec_ok<T, 2>(H, strides, act, f32))
+        return gate_bwd_v<T, 2, kBwdQ, kBwdTC, false, 2, true>(
+            rg, rg_rs, xc, xc_rs, z, z_rs, lam, gb, carries, dy, drg, drg_rs, dxc, dxc_rs, dz,
+            dz_rs, part, dh0_part, B, L, H, offs, st, dy_last, order);
+      return gate_bwd_v<T, 1, kBwdQ, kBwdTC, false, 1, true>(
+          rg, rg_rs, xc, xc_rs, z, z_rs, lam, gb, carries, dy, drg, drg_rs, dxc, dxc_rs, dz,
+          dz_rs, part, dh0_part, B, L, H, offs, st, dy_last, order);
+    }
   }
   if (vec_ok<T, VW>(H, strides, act, f32)) {
     return gate_bwd_v<T, VW>(rg, rg_rs, xc, xc_rs, z, z_rs, lam, gb, carries, dy, drg, drg_rs,

@@ -361,7 +361,8 @@ def conv_silu_bwd(x, weight, bias, g1, g2, dx, seq: Packed | None = None):
 
 
 def gate_scan_fwd(rg, xc, z, lam, h0=None, y=None, want_carries=True, gate_b=None,
-                  seq: Packed | None = None, last_only: bool = False, batch_row=None):
+                  seq: Packed | None = None, last_only: bool = False, batch_row=None,
+                  z_last=None):
     """Fused alpha/beta gates + BD-LRU scan + silu(z) merge.
 
     rg: [B, L, 2H]; xc, z: [B, L, H] views (or packed [ntok, 2H] / [ntok, H]
@@ -370,16 +371,25 @@ def gate_scan_fwd(rg, xc, z, lam, h0=None, y=None, want_carries=True, gate_b=Non
     (or None).  Returns (y in xc's layout, carries [B, nT, H] or None when not
     wanted).  last_only (fp32): y is only needed at each sequence's last
     position — returns y_last [B, H] instead (rb_gate_scan_fwd_last); with
-    batch_row (int64 [B] permutation) sequence b's row is batch_row[b]."""
+    batch_row (int64 [B] permutation) sequence b's row is batch_row[b].
+    z_last (with last_only, z None): z at each sequence's last position only,
+    [B, H] with y_last's rows — the kernel then reads no row of z."""
     dt = _act_dtype(xc, "xc")
-    for t, n in ((rg, "rg"), (xc, "xc"), (z, "z")):
+    sparse_z = z_last is not None
+    if sparse_z and (z is not None or not last_only):
+        raise ValueError("z_last goes with last_only and replaces z")
+    for t, n in ((rg, "rg"), (xc, "xc"), (z_last if sparse_z else z, "z")):
         _check(t, n, dt)
     _check(lam, "Lambda")
     H = xc.shape[-1]
     B, L, xc_rs, offs = _layout(xc, "xc", H, seq)
     rg_rs = _layout(rg, "rg", 2 * H, seq)[2]
-    z_rs = _layout(z, "z", H, seq)[2]
-    if seq is None and (z.shape[:2] != (B, L) or rg.shape[:2] != (B, L)):
+    if sparse_z:
+        _check_rows_bh(z_last, "z_last", B, H)
+        z_rs = H
+    else:
+        z_rs = _layout(z, "z", H, seq)[2]
+    if seq is None and ((not sparse_z and z.shape[:2] != (B, L)) or rg.shape[:2] != (B, L)):
         raise ValueError("rg, xc, z batch/length mismatch")
     if lam.shape != (H,):
         raise ValueError(f"Lambda must be [{H}]")
@@ -397,8 +407,12 @@ def gate_scan_fwd(rg, xc, z, lam, h0=None, y=None, want_carries=True, gate_b=Non
         if dt != torch.float32:
             raise ValueError("last_only is fp32")
         y_last = torch.empty((B, H), device=xc.device, dtype=dt)
-        _launch("rb_gate_scan_fwd", 4 * n * 4 + B * H * 4, rg.data_ptr(), rg_rs, xc.data_ptr(),
-                xc_rs, z.data_ptr(), z_rs, lam.contiguous().data_ptr(), _gb_ptr(gate_b, H),
+        # r, i, xc (and z) read at every row; y_last (and z_last) on B rows
+        nbytes = (3 * n + 2 * B * H if sparse_z else 4 * n + B * H) * 4
+        _launch("rb_gate_scan_fwd", nbytes, rg.data_ptr(), rg_rs, xc.data_ptr(),
+                xc_rs, None if sparse_z else z.data_ptr(), z_rs,
+                z_last.data_ptr() if sparse_z else None,
+                lam.contiguous().data_ptr(), _gb_ptr(gate_b, H),
                 0 if h0 is None else h0.data_ptr(), h0_bs, y_last.data_ptr(),
                 0 if carries is None else carries.data_ptr(), B, L, H, offs,
                 _batch_row_ptr(batch_row, B, xc.device), _stream(xc), _fn="rb_gate_scan_fwd_last")
@@ -413,6 +427,11 @@ def gate_scan_fwd(rg, xc, z, lam, h0=None, y=None, want_carries=True, gate_b=Non
             h0_bs, y.data_ptr(), y_rs, 0 if carries is None else carries.data_ptr(), B, L, H,
             offs, _stream(xc))
     return y, carries
+
+
+def _check_rows_bh(t, name, B, H):
+    if t.shape != (B, H) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous [{B}, {H}] tensor")
 
 
 def _batch_row_ptr(batch_row, B, dev):
@@ -435,16 +454,23 @@ def _gb_ptr(gate_b, H):
 
 def gate_scan_bwd(rg, xc, z, lam, carries, dy, dz, drg=None, dxc=None, dh0_rows=False,
                   gate_b=None, seq: Packed | None = None, last_only: bool = False,
-                  batch_row=None):
+                  batch_row=None, z_last=None):
     """Backward of gate_scan_fwd.  Writes dz (a row-strided view) and returns
     (drg, dxc, dlam [H], dgate_bias [2H], dh0), dh0 [H] (summed over rows) or
     [B, H] when dh0_rows (a per-row h0).  Layouts as in gate_scan_fwd.
     last_only: dy is [B, H], the gradient at each sequence's last position
     (zero elsewhere; rb_gate_scan_bwd_last), row batch_row[b] for sequence b
-    when batch_row is given."""
+    when batch_row is given.
+    z_last (with last_only, z None): as in gate_scan_fwd; dz is then dz_last
+    [B, H] (dy's rows) — dz is zero at every other position, which the
+    kernel neither reads z for nor writes."""
     H = xc.shape[-1]
     dt = _act_dtype(xc, "xc")
-    for t, n in ((rg, "rg"), (xc, "xc"), (z, "z"), (dy, "dy"), (dz, "dz")):
+    sparse_z = z_last is not None
+    if sparse_z and (z is not None or not last_only):
+        raise ValueError("z_last goes with last_only and replaces z")
+    for t, n in ((rg, "rg"), (xc, "xc"), (z_last if sparse_z else z, "z"), (dy, "dy"),
+                 (dz, "dz")):
         _check(t, n, dt)
     _check(carries, "carries")
     B, L, xc_rs, offs = _layout(xc, "xc", H, seq)
@@ -456,8 +482,13 @@ def gate_scan_bwd(rg, xc, z, lam, carries, dy, dz, drg=None, dxc=None, dh0_rows=
     if carries.shape != (B, num_tiles(L), H) or not carries.is_contiguous():
         raise ValueError("carries shape mismatch")
     rg_rs = _layout(rg, "rg", 2 * H, seq)[2]
-    z_rs = _layout(z, "z", H, seq)[2]
-    dz_rs = _layout(dz, "dz", H, seq)[2]
+    if sparse_z:
+        _check_rows_bh(z_last, "z_last", B, H)
+        _check_rows_bh(dz, "dz_last", B, H)
+        z_rs = dz_rs = H
+    else:
+        z_rs = _layout(z, "z", H, seq)[2]
+        dz_rs = _layout(dz, "dz", H, seq)[2]
     if drg is None:
         drg = torch.empty(xc.shape[:-1] + (2 * H,), device=xc.device, dtype=dt)
     drg_rs = _layout(drg, "drg", 2 * H, seq)[2]
@@ -470,14 +501,22 @@ def gate_scan_bwd(rg, xc, z, lam, carries, dy, dz, drg=None, dxc=None, dh0_rows=
     part = torch.empty((4, B, H), device=xc.device, dtype=torch.float32)
     dh0_part = part[3]
     n = xc.numel()
-    nbytes = (8 * n + B * H if last_only else 9 * n) * xc.element_size()
+    # reads r, i, xc (z), writes dr, di, dxc (dz) at every row; dy_last
+    # (z_last, dz_last) on B rows
+    nbytes = ((6 * n + 3 * B * H if sparse_z else 8 * n + B * H) if last_only
+              else 9 * n) * xc.element_size()
     tail = ((offs, _batch_row_ptr(batch_row, B, xc.device), _stream(xc)) if last_only
             else (offs, _stream(xc)))
+    # rb_gate_scan_bwd_last's z_last / dz_last follow z_rs / dz_rs
+    zl = ((z_last.data_ptr() if sparse_z else None,),
+          (dz.data_ptr() if sparse_z else None,)) if last_only else ((), ())
     _launch("rb_gate_scan_bwd" + _sfx(dt), nbytes, rg.data_ptr(), rg_rs,
             xc.data_ptr(), xc_rs,
-            z.data_ptr(), z_rs, lam.contiguous().data_ptr(), _gb_ptr(gate_b, H), carries.data_ptr(),
+            None if sparse_z else z.data_ptr(), z_rs, *zl[0],
+            lam.contiguous().data_ptr(), _gb_ptr(gate_b, H), carries.data_ptr(),
             dy.data_ptr(),
-            drg.data_ptr(), drg_rs, dxc.data_ptr(), dxc_rs, dz.data_ptr(), dz_rs,
+            drg.data_ptr(), drg_rs, dxc.data_ptr(), dxc_rs,
+            None if sparse_z else dz.data_ptr(), dz_rs, *zl[1],
             part.data_ptr(), dh0_part.data_ptr(), B, L, H, *tail,
             _fn="rb_gate_scan_bwd_last" if last_only else None)
     if dh0_rows:

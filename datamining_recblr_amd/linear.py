@@ -36,7 +36,8 @@ import torch
 from . import _lib, gemm_tuning, kernels
 
 __all__ = ["linear", "wgrad", "LinearFn", "mm_nt", "mm_nn", "split_gemm_enabled",
-           "HipLinearForward", "has_hooks", "fire_hooks"]
+           "HipLinearForward", "has_hooks", "fire_hooks", "SplitInProjFn",
+           "split_in_projection"]
 
 _GEMM = os.environ.get("RECBLR_GEMM", "f16x3")
 if _GEMM not in ("f16x3", "torch"):
@@ -52,9 +53,11 @@ _cache_on = os.environ.get("RECBLR_SPLIT_CACHE", "1") != "0"
 # (profiles/r03_v1_bench.log: 32-64 workgroups of column-strided loads)
 _small_tn = os.environ.get("RECBLR_SMALL_TN", "0") == "1"
 
-# Split images of the weights, kept across calls: (id(w), transpose) ->
-# [weakref(w), data_ptr, (version, optimizer steps), wf].  An entry is current
-# while the weight's storage, its version counter (every in-place update:
+# Split images of the weights, kept across calls: (id(w), transpose, rows) ->
+# [weakref(w), data_ptr, (version, optimizer steps), wf]; rows None, or
+# (r0, r1): the image of the row slice w[r0:r1] (the two halves of a split
+# in-projection: a strided view of the weight, split in the same launch).
+# An entry is current while the weight's storage, its version counter (every in-place update:
 # optimizer steps, load_state_dict, nn.init) and the count of optimizer steps
 # taken anywhere (torch.optim step hook: also covers optimizers that write
 # through .data) are unchanged; the first stale lookup of a training step
@@ -95,28 +98,32 @@ def _stamp(w: torch.Tensor):
     return (w._version, _opt_steps[0])
 
 
-def _make_image(w, transpose):
-    return kernels.gemm_h_weight(w, transpose=transpose)
+def _rows_of(w, rows):
+    return w if rows is None else w[rows[0]:rows[1]]
 
 
-def _weight_split(w: torch.Tensor, transpose: bool) -> torch.Tensor:
-    """The f16 weight image of w (transpose: of w^T), cached.  Every f16 GEMM
-    launch takes its weight from here, so RECBLR_NT_WS reaches the library
-    here, before the first of them."""
+def _make_image(w, transpose, rows=None):
+    return kernels.gemm_h_weight(_rows_of(w, rows), transpose=transpose)
+
+
+def _weight_split(w: torch.Tensor, transpose: bool, rows=None) -> torch.Tensor:
+    """The f16 weight image of w (transpose: of w^T), cached; rows = (r0, r1):
+    of w[r0:r1].  Every f16 GEMM launch takes its weight from here, so
+    RECBLR_NT_WS reaches the library here, before the first of them."""
     _apply_nt_ws()
     if not _cache_on:
-        return _make_image(w, transpose)
-    key = (id(w), transpose)
+        return _make_image(w, transpose, rows)
+    key = (id(w), transpose, rows)
     e = _split_cache.get(key)
     if e is not None and e[0]() is w and e[1] == w.data_ptr() and e[2] == _stamp(w):
-        if _cache_check and not torch.equal(e[3], _make_image(w, transpose)):
+        if _cache_check and not torch.equal(e[3], _make_image(w, transpose, rows)):
             raise StaleSplitCacheError(
                 "cached split image of a weight is stale: the weight was rewritten without "
                 "a torch.optim step or a version bump; call linear.invalidate_split_cache()")
         return e[3]
     if e is None or e[0]() is not w or e[1] != w.data_ptr():
         # new (or re-allocated) weight: its own split, then cached
-        wf = _make_image(w, transpose)
+        wf = _make_image(w, transpose, rows)
         _split_cache[key] = [weakref.ref(w), w.data_ptr(), _stamp(w), wf]
         return wf
     # stale after an in-place update: refresh all stale entries at once
@@ -127,7 +134,7 @@ def _weight_split(w: torch.Tensor, transpose: bool) -> torch.Tensor:
             del _split_cache[k]
             continue
         if _stamp(ww) != ent[2] and ww.device == w.device:
-            jobs.append((ww, k[1], ent[3]))
+            jobs.append((_rows_of(ww, k[2]), k[1], ent[3]))
             fresh.append(ent)
     kernels.gemm_h_split_weights(jobs)
     for ent in fresh:
@@ -258,10 +265,18 @@ def _bf16_ok(a: torch.Tensor, w: torch.Tensor, C: int, R: int) -> bool:
 
 
 def mm_nt(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None,
-          rmax: torch.Tensor | None = None) -> torch.Tensor:
+          rmax: torch.Tensor | None = None, rows=None) -> torch.Tensor:
     """a [M, K] @ w[N, K]^T (+ bias): F.linear's forward GEMM.  bf16
     activations (config 5) use the weight rounded to bf16 (bf16 MFMA, fp32
-    accumulation, bf16 output).  rmax: from rmax_buffer(a, N, K)."""
+    accumulation, bf16 output).  rmax: from rmax_buffer(a, N, K).
+    rows = (r0, r1): with w[r0:r1] for w (fp32; its cached image is kept under
+    the parameter w)."""
+    if rows is not None:
+        ws = w[rows[0]:rows[1]]
+        N, K = ws.shape
+        if a.dtype == w.dtype and _split_ok(a, N, K):
+            return kernels.gemm_nt_h(a, _weight_split(w, False, rows), N, bias=bias, rmax=rmax)
+        return mm_nt(a, ws, bias)
     if a.dtype != w.dtype and _bf16_ok(a, w, w.shape[0], w.shape[1]):
         b = None if bias is None else bias.contiguous()
         return kernels.gemm_nt_bf16(a, _bf16_image(w, False), w.shape[0], bias=b)
@@ -362,9 +377,16 @@ def mm_nn_dact(dy: torch.Tensor, w: torch.Tensor, pre: torch.Tensor, seed: int, 
 
 
 def mm_nn(dy: torch.Tensor, w: torch.Tensor, out: torch.Tensor | None = None,
-          rmax: torch.Tensor | None = None) -> torch.Tensor:
+          rmax: torch.Tensor | None = None, rows=None) -> torch.Tensor:
     """dy [M, N] @ w [N, K] (the input gradient of F.linear); with `out`,
-    accumulated into it in place (out += dy @ w)."""
+    accumulated into it in place (out += dy @ w).  rows: as in mm_nt."""
+    if rows is not None:
+        ws = w[rows[0]:rows[1]]
+        N, K = ws.shape
+        if dy.dtype == w.dtype and _split_ok(dy, K, N):
+            r = kernels.gemm_nt_h(dy, _weight_split(w, True, rows), K, rmax=rmax)
+            return r if out is None else out.add_(r)
+        return mm_nn(dy, ws, out)
     if dy.dtype != w.dtype and out is None and _bf16_ok(dy, w, w.shape[1], w.shape[0]):
         return kernels.gemm_nt_bf16(dy, _bf16_image(w, True), w.shape[1])
     if dy.dtype != w.dtype:
@@ -450,12 +472,13 @@ def wgrad(dy2: torch.Tensor, x2: torch.Tensor, splits: int = SPLIT_K,
     return kernels.colsum(parts.view(parts.shape[0], -1)).view(N, K)
 
 
-def _label(fn, args) -> str:
+def _label(fn, args, rows=None) -> str:
     """GEMM label for the bench's per-shape breakdown: op[M x K -> N]."""
     name = getattr(fn, "__name__", "gemm")
     if name in ("mm_nt", "mm_nn", "mm_nt_act", "mm_nn_dact") and len(args) >= 2:
         a, w = args[0], args[1]
-        n_out = w.shape[1] if name.startswith("mm_nn") else w.shape[0]
+        n_out = (w.shape[1] if name.startswith("mm_nn") else
+                 w.shape[0] if rows is None else rows[1] - rows[0])
         return f"{name}[{a.shape[0]}x{a.shape[1]}->{n_out}]"
     if name == "wgrad" and len(args) >= 2:
         return f"wgrad[{args[0].shape[0]}:{args[0].shape[1]}x{args[1].shape[1]}]"
@@ -473,7 +496,7 @@ def _timed(kind, flops, fn, *args, **kw):
     out = fn(*args, **kw)
     e1.record()
     t.records.append((kind, flops, e0, e1))
-    t.detail.append((_label(fn, args), flops, e0, e1))
+    t.detail.append((_label(fn, args, kw.get("rows")), flops, e0, e1))
     return out
 
 
@@ -501,14 +524,7 @@ class LinearFn(torch.autograd.Function):
             slot = ctx.slot
             ry = rmax_buffer(dy2, weight.shape[1], weight.shape[0]) if ctx.rx is not None else None
             dx = _timed("gemm", flops, mm_nn, dy2, weight, rmax=ry)
-            if slot is not None and slot.ds is not None:
-                if slot.rows is not None:        # residual of gathered rows
-                    dx.index_add_(0, slot.rows, slot.ds.view(-1, weight.shape[1]))
-                    slot.ds = None
-                elif not slot.taken:             # nobody downstream adds it
-                    dx.add_(slot.ds.view(-1, weight.shape[1]))
-                    slot.ds = None
-                # else: x's producer adds slot.ds while loading (rb_add_ln_bwd2)
+            _add_slot(dx, slot, weight.shape[1])
             dx = dx.view(*dy.shape[:-1], weight.shape[1])
         if ctx.needs_input_grad[1]:
             dw = _timed("gemm", flops, wgrad, dy2, x2, ymax=ry, xmax=ctx.rx)
@@ -516,6 +532,71 @@ class LinearFn(torch.autograd.Function):
             db = (kernels.colsum(dy2.contiguous()) if dy2.dtype == torch.float32
                   else dy2.sum(0, dtype=torch.float32))
         return dx, dw, db, None
+
+
+def _add_slot(dx: torch.Tensor, slot, K: int) -> None:
+    """The residual gradient a slot hands to the GEMM that made dx [M, K]."""
+    if slot is None or slot.ds is None:
+        return
+    if slot.rows is not None:        # residual of gathered rows
+        dx.index_add_(0, slot.rows, slot.ds.view(-1, K))
+        slot.ds = None
+    elif not slot.taken:             # nobody downstream adds it
+        dx.add_(slot.ds.view(-1, K))
+        slot.ds = None
+    # else: x's producer adds slot.ds while loading (rb_add_ln_bwd2)
+
+
+class SplitInProjFn(torch.autograd.Function):
+    """The last layer's in-projection when only each sequence's last row of z
+    is read (sparse z, model.GatedRecurrentLayer): x [ntok, d], weight [2H, d],
+    last int64 [B] (distinct rows) -> (xh = x @ weight[:H]^T [ntok, H],
+    z_last = x[last] @ weight[H:]^T [B, H]).  The H columns of z at the other
+    rows, and their zero gradients, are never computed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, last, slot=None):
+        H, d = weight.shape[0] // 2, weight.shape[1]
+        want_w = ctx.needs_input_grad[1]
+        x_last = x.index_select(0, last)
+        rx = rmax_buffer(x, H, d) if want_w else None
+        rl = rmax_buffer(x_last, H, d) if want_w else None
+        xh = _timed("gemm", 2 * x.shape[0] * d * H, mm_nt, x, weight, rmax=rx, rows=(0, H))
+        z_last = _timed("gemm", 2 * x_last.shape[0] * d * H, mm_nt, x_last, weight, rmax=rl,
+                        rows=(H, 2 * H))
+        ctx.rx, ctx.rl, ctx.slot = rx, rl, slot
+        ctx.save_for_backward(x, x_last, weight, last)
+        return xh, z_last
+
+    @staticmethod
+    def backward(ctx, dxh, dz_last):
+        x, x_last, weight, last = ctx.saved_tensors
+        H, d = weight.shape[0] // 2, weight.shape[1]
+        dxh, dz_last = dxh.contiguous(), dz_last.contiguous()
+        big, few = 2 * x.shape[0] * d * H, 2 * x_last.shape[0] * d * H
+        dx = dw = None
+        ry = rmax_buffer(dxh, d, H) if ctx.rx is not None else None
+        rz = rmax_buffer(dz_last, d, H) if ctx.rl is not None else None
+        if ctx.needs_input_grad[0]:
+            dx = _timed("gemm", big, mm_nn, dxh, weight, rmax=ry, rows=(0, H))
+            dx.index_add_(0, last, _timed("gemm", few, mm_nn, dz_last, weight, rmax=rz,
+                                          rows=(H, 2 * H)))
+            _add_slot(dx, ctx.slot, d)
+        if ctx.needs_input_grad[1]:
+            if dx is None:   # the weight gradients' row maxima come from the dX GEMMs
+                ry = rz = None
+            dw = torch.cat((_timed("gemm", big, wgrad, dxh, x, ymax=ry, xmax=ctx.rx),
+                            _timed("gemm", few, wgrad, dz_last, x_last, ymax=rz, xmax=ctx.rl)))
+        return dx, dw, None, None
+
+
+def split_in_projection(x: torch.Tensor, weight: torch.Tensor, last: torch.Tensor, slot=None):
+    """(xh [ntok, H], z_last [B, H]) of a bias-free in-projection weight
+    [2H, d] on packed fp32 rows x [ntok, d] (SplitInProjFn); `slot` as in
+    linear()."""
+    if _tuned is None and x.is_cuda:
+        _load_tuned()
+    return SplitInProjFn.apply(x, weight, last, slot)
 
 
 def has_hooks(module: torch.nn.Module) -> bool:

@@ -34,7 +34,8 @@ from .blocks import (ResidualGrad, add_dropout_layer_norm, draw_seed, embed_drop
 from .kernels import (MAX_NEGATIVES, MAX_SHARED_NEGATIVES, Packed, grl_max_tiles, grl_pieces,
                       next_item_targets, next_item_targets_reference, sample_negatives_reference,
                       negative_sampler, pack_plan, sample_negatives)
-from .linear import HipLinearForward, fire_hooks, has_hooks, linear
+from .linear import (MIN_ROWS_FOR_SPLIT, HipLinearForward, fire_hooks, has_hooks, linear,
+                     split_in_projection)
 from .recbole_compat import BPRLoss, SequentialRecommender, install_interaction_hook
 from .recurrence import bd_lru, fused_ok, pow2_pad_len, row_pad_lens
 
@@ -103,6 +104,26 @@ def _num_cus(dev) -> int:
 
 # RECBLR_LAST_ONLY=0: the last layer's scan writes y at every position
 _LAST_ONLY = os.environ.get("RECBLR_LAST_ONLY", "1") != "0"
+# RECBLR_SPARSE_Z=0: that layer still computes z, and dz's zeros, at every row.
+# Default: y_last reads z only at each sequence's last row, so the
+# in-projection makes x [ntok, H] and z_last [B, H] (linear.SplitInProjFn) and
+# the scan kernels take z_last / write dz_last — from SPARSE_Z_MIN_ROWS packed
+# rows (the row count from which linear switches kernels: below it the saved
+# bytes are microseconds and the extra few-rows launches cost more)
+_SPARSE_Z = os.environ.get("RECBLR_SPARSE_Z", "1") != "0"
+SPARSE_Z_MIN_ROWS = MIN_ROWS_FOR_SPLIT
+
+
+def set_sparse_z(on: bool, min_rows: int | None = None):
+    """Switch the last layer's sparse z and, optionally, its minimum packed
+    row count (A/B runs, tests); returns the previous (on, min_rows)."""
+    global _SPARSE_Z, SPARSE_Z_MIN_ROWS
+    prev = (_SPARSE_Z, SPARSE_Z_MIN_ROWS)
+    _SPARSE_Z = bool(on)
+    if min_rows is not None:
+        SPARSE_Z_MIN_ROWS = int(min_rows)
+    return prev
+
 
 __all__ = ["RecBLR", "RecurrentLayer", "GatedRecurrentLayer", "FeedForward",
            "softplus_inverse", "lambda_init_range"]
@@ -161,21 +182,28 @@ class GatedRecurrentLayer(nn.Module):
             raise RecBLRNativeError(
                 "GatedRecurrentLayer runs only on the MI355X HIP path (ROCm GPU tensors); "
                 "move the model to a GPU. The CPU restatement under oracle/ is test-only.")
-        self.input._recblr_slot = slot
-        xz = self.input(x)
-        # the last layer under gather_indexes on packed sequences needs y only
-        # at each sequence's last row: the scan kernels keep just those
-        last_only = (_LAST_ONLY and rows is not None and seq is not None
-                     and rows is seq.last and xz.dtype == torch.float32)
         observe = None
         if has_hooks(self.gates) or has_hooks(self.conv1d):
             def observe(x_, xc, rg):   # hooks of the Linear / Conv1d fused into bd_lru
                 if not self.disable_conv1d:
                     fire_hooks(self.conv1d, (x_.transpose(-1, -2),), xc.transpose(-1, -2))
                 fire_hooks(self.gates, (xc,), rg + self.gates.bias)
+        z_last = None
+        if self._sparse_z(x, rows, seq, observe, capture):
+            # ... and z only there: no [ntok, 2H] xz exists (the hooks of
+            # self.input, which would see it, select the dense path)
+            xz, z_last = split_in_projection(x, self.input.weight, seq.last, slot)
+        else:
+            self.input._recblr_slot = slot
+            xz = self.input(x)
+        # the last layer under gather_indexes on packed sequences needs y only
+        # at each sequence's last row: the scan kernels keep just those
+        last_only = (_LAST_ONLY and rows is not None and seq is not None
+                     and rows is seq.last and xz.dtype == torch.float32)
         y = bd_lru(xz, self.conv1d.weight, self.conv1d.bias, self.gates.weight,
                    self.gates.bias, self.Lambda, use_conv=not self.disable_conv1d, pad=pad,
-                   seq=seq, last_only=last_only, observe=observe, capture=capture)
+                   seq=seq, last_only=last_only, observe=observe, capture=capture,
+                   z_last=z_last)
         if last_only:
             if seq.order is None:   # packed-sequence order -> batch order
                 y = y.index_select(0, seq.inv)
@@ -184,6 +212,21 @@ class GatedRecurrentLayer(nn.Module):
         # project=False: y before the out-projection (the caller fuses the
         # projection with its residual LayerNorm, blocks.linear_add_dropout_layer_norm)
         return self.output(y) if project else y
+
+    def _sparse_z(self, x, rows, seq, observe, capture) -> bool:
+        """Whether this call takes the sparse-z path: the last_only conditions
+        of forward() on fp32, from SPARSE_Z_MIN_ROWS packed rows, with nothing
+        that reads xz or the scan's inputs (hooks, observe, capture) and the
+        three-launch recurrence."""
+        w = self.input.weight
+        return (_SPARSE_Z and _LAST_ONLY and rows is not None and seq is not None
+                and rows is seq.last and seq.order is not None
+                and seq.ntok >= SPARSE_Z_MIN_ROWS and x.dim() == 2
+                and x.dtype == torch.float32 and w.dtype == torch.float32
+                and self.input.bias is None and observe is None and capture is None
+                and not has_hooks(self.input)
+                and not fused_ok(seq.pieces is not None, self.hidden,
+                                 not self.disable_conv1d, self.conv1d.weight.shape[-1], x.dtype))
 
     @staticmethod
     def pad_len(seq_len: int) -> int:

@@ -113,11 +113,13 @@ class PadPrefix(torch.autograd.Function):
 
 class BDLRUCore(torch.autograd.Function):
     """xz [B, L, 2H] (or packed [ntok, 2H] with `seq`) -> y = silu(z) *
-    BD-LRU(conv_silu(x)), in xz's layout."""
+    BD-LRU(conv_silu(x)), in xz's layout.  Sparse z (z_last given; packed,
+    last_only, fp32): xz is x [ntok, H] alone and z_last [B, H] holds z at each
+    sequence's last row (y_last's rows) — the only rows of z that y_last reads."""
 
     @staticmethod
     def forward(ctx, xz, conv_w, conv_b, gate_w, gate_b, lam, h0, use_conv, seq=None,
-                last_only=False, pad_len=None, observe=None, capture=None):
+                last_only=False, pad_len=None, observe=None, capture=None, z_last=None):
         """h0: an initial state given as an input (its gradient returned), or
         pad_len (int P > 0 or int64 [B] per-row lengths) with h0 None: the
         pad-prefix state computed here, its gradient added in place into the
@@ -128,14 +130,23 @@ class BDLRUCore(torch.autograd.Function):
         if pad_len is not None:
             h0 = kernels.pad_prefix_fwd(conv_b, gate_w, gate_b, lam, pad_len)
         ctx.pad_len = pad_len
-        H2 = xz.shape[-1]
-        H = H2 // 2
-        x, z = xz[..., :H], xz[..., H:]
+        sparse_z = ctx.sparse_z = z_last is not None
+        if sparse_z:
+            if not (last_only and seq is not None and observe is None and capture is None):
+                raise ValueError("z_last: packed last_only sequences without observe / capture")
+            H = xz.shape[-1]
+            H2 = 2 * H
+            x, z = xz, None
+        else:
+            H2 = xz.shape[-1]
+            H = H2 // 2
+            x, z = xz[..., :H], xz[..., H:]
         train = any(ctx.needs_input_grad)
         # last_only on packed sequences: y_last in batch order (seq.order)
         batch_row = seq.order if (last_only and seq is not None) else None
         ctx.batch_row = batch_row
-        if (observe is None and capture is None and (h0 is None or h0.dim() == 1)
+        if (not sparse_z and observe is None and capture is None
+                and (h0 is None or h0.dim() == 1)
                 and fused_ok(seq is not None and seq.pieces is not None, H, use_conv, conv_w.shape[-1], xz.dtype)):
             # conv + gates GEMM + gate scan in one launch (rb_grl_fwd).  Its
             # backward is one launch too (rb_grl_bwd), from the 64-row tile
@@ -156,19 +167,19 @@ class BDLRUCore(torch.autograd.Function):
                 xc = kernels.conv_silu_fwd(x, conv_w, conv_b, seq=seq)
             else:
                 xc = x
-            rows = xz.numel() // H2
+            rows = x.numel() // H
             gflops = 2 * rows * H * H2
             # gates GEMM without its bias: the gate kernels add gate_b on the fly
             xc2 = xc.reshape(rows, H)
             r_xc = rmax_buffer(xc2, H2, H) if ctx.needs_input_grad[3] else None
-            rg = _timed("gemm", gflops, mm_nt, xc2, gate_w, rmax=r_xc).view(*xz.shape[:-1], H2)
+            rg = _timed("gemm", gflops, mm_nt, xc2, gate_w, rmax=r_xc).view(*x.shape[:-1], H2)
             ctx.r_xc = r_xc
             if observe is not None:   # module hooks of the fused conv / gates (model.py)
                 observe(x, xc, rg)
             y, carries = kernels.gate_scan_fwd(rg, xc, z, lam, h0,
                                                want_carries=train or capture is not None,
                                                gate_b=gate_b, seq=seq, last_only=last_only,
-                                               batch_row=batch_row)
+                                               batch_row=batch_row, z_last=z_last)
             if capture is not None:   # the session state of a stored history (session.py)
                 capture(x, xc, rg, carries)
         ctx.use_conv = use_conv
@@ -177,26 +188,33 @@ class BDLRUCore(torch.autograd.Function):
         ctx.h0_rows = h0 is not None and h0.dim() == 2
         ctx.seq = seq
         ctx.save_for_backward(xz, xc if use_conv else None, rg, carries, conv_w, conv_b,
-                              gate_w, gate_b, lam)
+                              gate_w, gate_b, lam, z_last)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         if ctx.fused_bwd:
             return BDLRUCore._backward_fused(ctx, dy)
-        xz, xc, rg, carries, conv_w, conv_b, gate_w, gate_b, lam = ctx.saved_tensors
+        xz, xc, rg, carries, conv_w, conv_b, gate_w, gate_b, lam, z_last = ctx.saved_tensors
         seq = ctx.seq
-        H2 = xz.shape[-1]
-        H = H2 // 2
-        rows = xz.numel() // H2
-        x, z = xz[..., :H], xz[..., H:]
+        dxz = torch.empty_like(xz)
+        if ctx.sparse_z:   # no dxz buffer: dx and dz_last [B, H] are the gradients
+            H = xz.shape[-1]
+            H2 = 2 * H
+            x, z, dx = xz, None, dxz
+            dz = torch.empty_like(z_last)
+        else:
+            H2 = xz.shape[-1]
+            H = H2 // 2
+            x, z = xz[..., :H], xz[..., H:]
+            dx, dz = dxz[..., :H], dxz[..., H:]
+        rows = x.numel() // H
         if xc is None:
             xc = x
         dy = dy.contiguous()
-        dxz = torch.empty_like(xz)
         drg, dxc, dlam, dgate_b, dh0 = kernels.gate_scan_bwd(
-            rg, xc, z, lam, carries, dy, dxz[..., H:], dh0_rows=ctx.h0_rows, gate_b=gate_b,
-            seq=seq, last_only=ctx.last_only, batch_row=ctx.batch_row)
+            rg, xc, z, lam, carries, dy, dz, dh0_rows=ctx.h0_rows, gate_b=gate_b,
+            seq=seq, last_only=ctx.last_only, batch_row=ctx.batch_row, z_last=z_last)
         drg2 = drg.view(rows, H2)
         gflops = 2 * rows * H * H2
         # dL/dxc through the gates GEMM: the conv backward reads it as its second
@@ -212,11 +230,10 @@ class BDLRUCore(torch.autograd.Function):
                              xmax=ctx.r_xc)
         dconv_w = dconv_b = None
         if ctx.use_conv:
-            dw, dconv_b = kernels.conv_silu_bwd(x, conv_w, conv_b, dxc, dxc_g, dxz[..., :H],
-                                                seq=seq)
+            dw, dconv_b = kernels.conv_silu_bwd(x, conv_w, conv_b, dxc, dxc_g, dx, seq=seq)
             dconv_w = dw.view_as(conv_w)
         else:
-            torch.add(dxc, dxc_g, out=dxz[..., :H])
+            torch.add(dxc, dxc_g, out=dx)
         if dgate_w is None:
             dgate_w = _timed("gemm", gflops, wgrad, drg2, xc.reshape(rows, H), ymax=r_drg,
                              xmax=ctx.r_xc)
@@ -224,7 +241,8 @@ class BDLRUCore(torch.autograd.Function):
             kernels.pad_prefix_bwd(conv_b, gate_w, gate_b, lam, ctx.pad_len, dh0.float(),
                                    into=(dconv_b, dgate_w, dgate_b, dlam))
         return (dxz, dconv_w, dconv_b, dgate_w, dgate_b, dlam,
-                dh0 if ctx.has_h0 else None, None, None, None, None, None, None)
+                dh0 if ctx.has_h0 else None, None, None, None, None, None, None,
+                dz if ctx.sparse_z else None)
 
     @staticmethod
     def _backward_fused(ctx, dy):
@@ -233,7 +251,7 @@ class BDLRUCore(torch.autograd.Function):
         drg, dxc = drg W_g and the conv backward in the same launch.  Left
         outside: dW_g = drg^T xc (rb_gemm_tn_h on the 32-row maxima the kernel
         writes) and the column sums of the per-workgroup partials."""
-        xz, _, _, tile_carries, conv_w, conv_b, gate_w, gate_b, lam = ctx.saved_tensors
+        xz, _, _, tile_carries, conv_w, conv_b, gate_w, gate_b, lam, _ = ctx.saved_tensors
         seq = ctx.seq
         H = xz.shape[-1] // 2
         rows = xz.shape[0]
@@ -250,7 +268,7 @@ class BDLRUCore(torch.autograd.Function):
             kernels.pad_prefix_bwd(conv_b, gate_w, gate_b, lam, ctx.pad_len, dh0,
                                    into=(dconv_b, dgate_w, dgate_b, dlam))
         return (dxz, dconv_w, dconv_b, dgate_w, dgate_b, dlam,
-                dh0 if ctx.has_h0 else None, None, None, None, None, None, None)
+                dh0 if ctx.has_h0 else None, None, None, None, None, None, None, None)
 
 
 def row_pad_lens(lengths: torch.Tensor) -> torch.Tensor:
@@ -263,7 +281,7 @@ def row_pad_lens(lengths: torch.Tensor) -> torch.Tensor:
 
 
 def bd_lru(xz, conv_w, conv_b, gate_w, gate_b, lam, use_conv=True, pad=None, seq=None,
-           last_only=False, observe=None, capture=None):
+           last_only=False, observe=None, capture=None, z_last=None):
     """Everything between the in- and out-projections of RecBLR.py:170-207.
 
     pad=None: the reference's pad prefix pow2(L) - L for the batch's L.
@@ -278,7 +296,8 @@ def bd_lru(xz, conv_w, conv_b, gate_w, gate_b, lam, use_conv=True, pad=None, seq
     observe: optional callable (x, xc, rg) run in the forward (module hooks).
     capture: optional callable (x, xc, rg, carries) run in the forward with the
     scan's inputs and its tile carries [B, ceil(L / RB_TILE), H] (session.py's
-    prefill by one forward); selects the three-launch path, as observe does."""
+    prefill by one forward); selects the three-launch path, as observe does.
+    z_last: sparse z (see BDLRUCore) — xz is then x [ntok, H] alone."""
     if pad is None:
         P = pow2_pad_len(seq.L if seq is not None else xz.shape[1])
         pad_len = P if (P and use_conv) else None
@@ -287,6 +306,6 @@ def bd_lru(xz, conv_w, conv_b, gate_w, gate_b, lam, use_conv=True, pad=None, seq
     if not _FOLD_PAD and pad_len is not None:   # A/B: separate autograd node
         h0 = PadPrefix.apply(conv_b, gate_w, gate_b, lam, pad_len)
         return BDLRUCore.apply(xz, conv_w, conv_b, gate_w, gate_b, lam, h0, use_conv, seq,
-                               last_only, None, observe, capture)
+                               last_only, None, observe, capture, z_last)
     return BDLRUCore.apply(xz, conv_w, conv_b, gate_w, gate_b, lam, None, use_conv, seq,
-                           last_only, pad_len, observe, capture)
+                           last_only, pad_len, observe, capture, z_last)

@@ -77,7 +77,7 @@ typedef uint16_t rb_bf16;
 #define RB_TILE 16
 
 /* ABI version; bumped on any signature change.  rb_version() returns it. */
-#define RB_ABI_VERSION 54
+#define RB_ABI_VERSION 55
 int rb_version(void);
 
 /* Human-readable description of the last error on the calling thread. */
@@ -172,18 +172,27 @@ int rb_gate_scan_bwd(const float* rg, int64_t rg_rs, const float* xc,
  * batch_row (int64 [B], a permutation of 0..B-1, or NULL): sequence b's row
  * of y_last / dy_last is batch_row[b] instead of b — packed sequences run
  * longest first, so the last layer's output lands in batch order without a
- * gather (and its gradient is read without a scatter). */
+ * gather (and its gradient is read without a scatter).
+ * Sparse z (ABI 55): y_last reads z, and dz is non-zero, only at each
+ * sequence's last position.  With z_last [B, H] contiguous (rows as y_last's:
+ * sequence b's at batch_row[b]) instead of z (z NULL, z_rs ignored) the
+ * forward loads no row of z; the backward likewise takes z_last and writes
+ * dz_last [B, H] (rows as dy_last's) instead of dz (dz NULL, dz_rs ignored),
+ * loading no row of z and storing no row of dz.  drg, dxc, part and dh0_part
+ * are the same operations in the same order either way.  z and z_last (dz and
+ * dz_last) exclude each other; the backward needs z_last and dz_last together. */
 int rb_gate_scan_fwd_last(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
-                          const float* z, int64_t z_rs, const float* lam, const float* gate_b,
-                          const float* h0, int64_t h0_bs, float* y_last, float* carries,
-                          int64_t B, int64_t L, int64_t H, const int64_t* seq_offsets,
-                          const int64_t* batch_row, void* stream);
-int rb_gate_scan_bwd_last(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
-                          const float* z, int64_t z_rs, const float* lam, const float* gate_b,
-                          const float* carries, const float* dy_last, float* drg,
-                          int64_t drg_rs, float* dxc, int64_t dxc_rs, float* dz, int64_t dz_rs,
-                          float* part, float* dh0_part, int64_t B, int64_t L, int64_t H,
+                          const float* z, int64_t z_rs, const float* z_last, const float* lam,
+                          const float* gate_b, const float* h0, int64_t h0_bs, float* y_last,
+                          float* carries, int64_t B, int64_t L, int64_t H,
                           const int64_t* seq_offsets, const int64_t* batch_row, void* stream);
+int rb_gate_scan_bwd_last(const float* rg, int64_t rg_rs, const float* xc, int64_t xc_rs,
+                          const float* z, int64_t z_rs, const float* z_last, const float* lam,
+                          const float* gate_b, const float* carries, const float* dy_last,
+                          float* drg, int64_t drg_rs, float* dxc, int64_t dxc_rs, float* dz,
+                          int64_t dz_rs, float* dz_last, float* part, float* dh0_part, int64_t B,
+                          int64_t L, int64_t H, const int64_t* seq_offsets,
+                          const int64_t* batch_row, void* stream);
 
 /* The state the power-of-two left padding leaves in the recurrence
  * (RecBLR.py:176-179: F.pad of x by P zero steps before conv + scan), without
