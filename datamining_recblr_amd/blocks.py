@@ -332,6 +332,22 @@ class _FeedForward(torch.autograd.Function):
                 None, None, None)
 
 
+def _two_pass_layer_norm(x, ln: torch.nn.LayerNorm):
+    """ln(x) for a row size the row kernels do not take, in torch ops with
+    their arithmetic (rownorm.hip): the mean first, then the variance of the
+    centred row, in fp32.  torch's own LayerNorm on the GPU is several times
+    further off than that where a row's mean dwarfs its spread (an embedding
+    row of 300 +- 0.06: 4.3 times the error of plain two-pass fp32, measured
+    through session.prefill(method="forward") at d = 48).  A LayerNorm that
+    carries forward hooks is called as the module it is."""
+    if has_hooks(ln):
+        return ln(x)
+    c = x.float()
+    c = c - c.mean(-1, keepdim=True)
+    rs = torch.rsqrt((c * c).mean(-1, keepdim=True) + ln.eps)
+    return (c * rs * ln.weight.float() + ln.bias.float()).to(x.dtype)
+
+
 def add_dropout_layer_norm(a, residual, dropout: torch.nn.Dropout, ln: torch.nn.LayerNorm,
                            training: bool, slot: ResidualGrad | None = None,
                            addend: ResidualGrad | None = None):
@@ -340,7 +356,7 @@ def add_dropout_layer_norm(a, residual, dropout: torch.nn.Dropout, ln: torch.nn.
     of the output that its consumer hands back (see ResidualGrad)."""
     _require_gpu(a)
     if a.shape[-1] not in kernels.ROW_SIZES:
-        return ln(dropout(a) + residual)
+        return _two_pass_layer_norm(dropout(a) + residual, ln)
     p, seed = _drop(dropout, training)
     return _AddDropoutLN.apply(a, residual, ln.weight, ln.bias, None, seed, p, ln.eps, slot,
                                addend)
@@ -370,7 +386,7 @@ def embed_dropout_layer_norm(idx, emb: torch.nn.Embedding, dropout: torch.nn.Dro
     """ln(dropout(emb(idx))) — RecBLR.py:76-78 (`addend`: see ResidualGrad)."""
     _require_gpu(emb.weight)
     if emb.weight.shape[1] not in kernels.ROW_SIZES:
-        return ln(dropout(emb(idx)))
+        return _two_pass_layer_norm(dropout(emb(idx)), ln)
     p, seed = _drop(dropout, training)
     return _EmbedDropoutLN.apply(emb.weight, idx, ln.weight, ln.bias, None, seed, p, ln.eps,
                                  emb.padding_idx, addend)
