@@ -24,10 +24,9 @@ MI355X, rounded up (up to 32 is expected with the f16x3 GEMMs in between):
     5e-6 or less, every max|ref64| 3e-4 or more.
 """
 import pytest
-import torch
 
-from oracle import recblr_oracle as orc
-from test_gpu_session import V, _model
+import model_grad_reference as R
+from test_gpu_session import V
 
 pytestmark = pytest.mark.gpu
 
@@ -39,41 +38,14 @@ VARIANTS = [dict(), dict(loss_type="BPR"), dict(disable_conv1d=True), dict(disab
             dict(bd_lru_only=True)]
 
 
-def _oracle_grads(state, cfg, seq, lens, pos, neg, dtype):
-    p = {k: v.detach().cpu().to(dtype).clone().requires_grad_() for k, v in state.items()}
-    orc.calculate_loss(p, cfg, seq, lens, pos, neg).backward()
-    return {k: v.grad for k, v in p.items()}
-
-
 def run_variant(dev, flags):
     """{parameter: (error, e32, ratio, max|ref64|)}; parameters the variant
-    does not use (no oracle gradient) must have none on the GPU either."""
-    model, cfg = _model(dev, 64, 4, L, 2, **flags)
-    g = torch.Generator().manual_seed(5)
-    lens = torch.tensor(LENGTHS)
-    B = len(LENGTHS)
-    seq = torch.randint(1, V, (B, L), generator=g) * (torch.arange(L)[None] < lens[:, None])
-    pos = torch.randint(1, V, (B,), generator=g)
-    neg = torch.randint(1, V, (B,), generator=g)
-    inter = {"item_id_list": seq.to(dev), "item_length": lens.to(dev), "item_id": pos.to(dev),
-             "neg_item_id": neg.to(dev)}
-    model.calculate_loss(inter).backward()
-    torch.cuda.synchronize()
-    state = model.state_dict()
-    g64 = _oracle_grads(state, cfg, seq, lens, pos, neg, torch.float64)
-    g32 = _oracle_grads(state, cfg, seq, lens, pos, neg, torch.float32)
-    out = {}
-    for name, p in model.named_parameters():
-        ref = g64[name]
-        if ref is None:
-            assert p.grad is None or p.grad.abs().max() == 0, name
-            continue
-        assert p.grad is not None, f"{name} has no gradient"
-        scale = ref.abs().max().item()
-        err = (p.grad.detach().cpu().double() - ref).abs().max().item() / scale
-        e32 = (g32[name].double() - ref).abs().max().item() / scale
-        out[name] = (err, e32, err / max(e32, FLOOR), scale)
-    return out
+    does not use (no oracle gradient) must have none on the GPU either
+    (model_grad_reference.judge)."""
+    flags = dict(flags)
+    loss_type = flags.pop("loss_type", "CE")
+    case = R.make_case(flags, 64, V, L, LENGTHS, loss_type)
+    return R.run_case(case, dev, floor=FLOOR)[0]
 
 
 @pytest.mark.parametrize("flags", VARIANTS, ids=["CE", "BPR", "disable_conv1d", "disable_ffn", "bd_lru_only"])

@@ -10,8 +10,7 @@ import pytest
 import torch
 
 from datamining_recblr_amd import _lib, session
-from datamining_recblr_amd.model import RecBLR
-from datamining_recblr_amd.recbole_compat import SyntheticDataset
+from model_grad_reference import build_model
 from oracle import recblr_oracle as orc
 from test_gpu_e2e import close
 
@@ -21,19 +20,8 @@ V = 200
 
 
 def _model(dev, d=64, K=4, L=20, layers=2, **flags):
-    cfg = dict(hidden_size=d, loss_type="CE", num_layers=layers, dropout_prob=0.0, expand=2,
-               d_conv=K, bd_lru_only=False, disable_conv1d=False, disable_ffn=False,
-               MAX_ITEM_LIST_LENGTH=L)
-    cfg.update(flags)
-    torch.manual_seed(0)
-    model = RecBLR(cfg, SyntheticDataset(V)).eval()
-    g = torch.Generator().manual_seed(1)
-    with torch.no_grad():   # off the init's zeros / ones / N(0, 0.02): every term matters
-        for name, p in model.named_parameters():
-            if name.endswith("bias") or "layer_norm" in name:
-                p.add_(0.1 * torch.randn(p.shape, generator=g))
-            elif "Lambda" not in name and "conv1d" not in name:
-                p.mul_(3.0)
+    # off the init's zeros / ones / N(0, 0.02): every term matters
+    model, cfg = build_model(V, d, K, L, layers, **flags)
     return model.to(dev), cfg
 
 
