@@ -512,16 +512,56 @@ int check_allow(const char* fn, const int32_t* allow, int64_t F, int64_t words, 
   if (words != (V + 31) / 32) return fail(fn, "words must be ceil(V / 32)");
   return 0;
 }
+
+// Every rb_item_rank* after its own required-argument rule: the shared checks,
+// then each option that is present (allow, prior: non-null) checked and packed.
+int item_rank(const char* fn, const float* seq, const float* items, const int64_t* target,
+              int64_t B, int64_t V, int64_t d, int64_t first_item, int64_t* n_greater,
+              int64_t* n_equal, void* workspace, int64_t workspace_bytes, void* stream,
+              const int32_t* allow, int64_t F, int64_t words, const int64_t* allow_rows,
+              const float* prior, int64_t P, const int64_t* prior_rows,
+              const float* prior_weight) {
+  if (int rc = check_item_rank(fn, seq, items, target, B, V, d, first_item, n_greater, workspace))
+    return rc;
+  if (allow)
+    if (int rc = check_allow(fn, allow, F, words, V)) return rc;
+  const AllowArgs al{allow, F, words, allow_rows};
+  const PriorArgs pa{prior, P, V, prior_rows, prior_weight};
+  return launch_item_rank(fn, seq, items, target, B, V, d, first_item, n_greater, n_equal,
+                          workspace, workspace_bytes, allow ? &al : nullptr,
+                          prior ? &pa : nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ... and every rb_item_topk* (groups non-null: the cap)
+int item_topk(const char* fn, const float* seq, const float* items, int64_t B, int64_t V,
+              int64_t d, int64_t k, int64_t first_item, const int64_t* exclude, int64_t E,
+              int64_t* ids, float* scores, void* workspace, int64_t workspace_bytes, void* stream,
+              const int32_t* allow, int64_t F, int64_t words, const int64_t* allow_rows,
+              const int32_t* groups, int64_t max_per_group, const float* prior, int64_t P,
+              const int64_t* prior_rows, const float* prior_weight) {
+  if (int rc = check_item_topk(fn, seq, items, B, V, d, k, first_item, exclude, E, ids, scores,
+                               workspace))
+    return rc;
+  if (allow)
+    if (int rc = check_allow(fn, allow, F, words, V)) return rc;
+  if (groups && max_per_group < 1) return fail(fn, "max_per_group must be >= 1");
+  const AllowArgs al{allow, F, words, allow_rows};
+  // a cap of k or more never binds: clamp it into the kernel's int
+  const GroupArgs gr{groups, (int)std::min<int64_t>(max_per_group, k)};
+  const PriorArgs pa{prior, P, V, prior_rows, prior_weight};
+  return launch_item_topk(fn, seq, items, B, V, d, k, first_item, E > 0 ? exclude : nullptr, E,
+                          ids, scores, workspace, workspace_bytes, allow ? &al : nullptr,
+                          groups ? &gr : nullptr, prior ? &pa : nullptr,
+                          reinterpret_cast<hipStream_t>(stream));
+}
 }  // namespace
 
 int rb_item_rank(const float* seq, const float* items, const int64_t* target, int64_t B,
                  int64_t V, int64_t d, int64_t first_item, int64_t* n_greater, int64_t* n_equal,
                  void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = check_item_rank("rb_item_rank", seq, items, target, B, V, d, first_item,
-                               n_greater, workspace))
-    return rc;
-  return launch_item_rank(seq, items, target, B, V, d, first_item, n_greater, n_equal, workspace,
-                          workspace_bytes, reinterpret_cast<hipStream_t>(stream));
+  return item_rank("rb_item_rank", seq, items, target, B, V, d, first_item, n_greater, n_equal,
+                   workspace, workspace_bytes, stream, /*filter*/ nullptr, 0, 0, nullptr,
+                   /*prior*/ nullptr, 0, nullptr, nullptr);
 }
 
 int rb_item_rank_allowed(const float* seq, const float* items, const int64_t* target, int64_t B,
@@ -530,12 +570,10 @@ int rb_item_rank_allowed(const float* seq, const float* items, const int64_t* ta
                          void* stream, const int32_t* allow, int64_t F, int64_t words,
                          const int64_t* allow_rows) {
   const char* fn = "rb_item_rank_allowed";
-  if (int rc = check_item_rank(fn, seq, items, target, B, V, d, first_item, n_greater, workspace))
-    return rc;
-  if (int rc = check_allow(fn, allow, F, words, V)) return rc;
-  return launch_item_rank_allowed(seq, items, target, B, V, d, first_item, n_greater, n_equal,
-                                  workspace, workspace_bytes, allow, F, words, allow_rows,
-                                  reinterpret_cast<hipStream_t>(stream));
+  if (!allow) return fail(fn, "null pointer (allow)");
+  return item_rank(fn, seq, items, target, B, V, d, first_item, n_greater, n_equal, workspace,
+                   workspace_bytes, stream, allow, F, words, allow_rows,
+                   /*prior*/ nullptr, 0, nullptr, nullptr);
 }
 
 int64_t rb_item_topk_workspace(int64_t B, int64_t V, int64_t d, int64_t k) {
@@ -546,12 +584,9 @@ int64_t rb_item_topk_workspace(int64_t B, int64_t V, int64_t d, int64_t k) {
 int rb_item_topk(const float* seq, const float* items, int64_t B, int64_t V, int64_t d, int64_t k,
                  int64_t first_item, const int64_t* exclude, int64_t E, int64_t* ids,
                  float* scores, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = check_item_topk("rb_item_topk", seq, items, B, V, d, k, first_item, exclude, E, ids,
-                               scores, workspace))
-    return rc;
-  return launch_item_topk(seq, items, B, V, d, k, first_item, E > 0 ? exclude : nullptr, E, ids,
-                          scores, workspace, workspace_bytes,
-                          reinterpret_cast<hipStream_t>(stream));
+  return item_topk("rb_item_topk", seq, items, B, V, d, k, first_item, exclude, E, ids, scores,
+                   workspace, workspace_bytes, stream, /*filter*/ nullptr, 0, 0, nullptr,
+                   /*cap*/ nullptr, 0, /*prior*/ nullptr, 0, nullptr, nullptr);
 }
 
 int rb_item_topk_allowed(const float* seq, const float* items, int64_t B, int64_t V, int64_t d,
@@ -560,14 +595,10 @@ int rb_item_topk_allowed(const float* seq, const float* items, int64_t B, int64_
                          void* stream, const int32_t* allow, int64_t F, int64_t words,
                          const int64_t* allow_rows) {
   const char* fn = "rb_item_topk_allowed";
-  if (int rc = check_item_topk(fn, seq, items, B, V, d, k, first_item, exclude, E, ids, scores,
-                               workspace))
-    return rc;
-  if (int rc = check_allow(fn, allow, F, words, V)) return rc;
-  return launch_item_topk_allowed(seq, items, B, V, d, k, first_item,
-                                  E > 0 ? exclude : nullptr, E, ids, scores, workspace,
-                                  workspace_bytes, allow, F, words, allow_rows,
-                                  reinterpret_cast<hipStream_t>(stream));
+  if (!allow) return fail(fn, "null pointer (allow)");
+  return item_topk(fn, seq, items, B, V, d, k, first_item, exclude, E, ids, scores, workspace,
+                   workspace_bytes, stream, allow, F, words, allow_rows, /*cap*/ nullptr, 0,
+                   /*prior*/ nullptr, 0, nullptr, nullptr);
 }
 
 int64_t rb_item_topk_grouped_workspace(int64_t B, int64_t V, int64_t d, int64_t k) {
@@ -582,17 +613,10 @@ int rb_item_topk_grouped(const float* seq, const float* items, int64_t B, int64_
                          const int64_t* allow_rows, const int32_t* groups,
                          int64_t max_per_group) {
   const char* fn = "rb_item_topk_grouped";
-  if (int rc = check_item_topk(fn, seq, items, B, V, d, k, first_item, exclude, E, ids, scores,
-                               workspace))
-    return rc;
-  if (allow)
-    if (int rc = check_allow(fn, allow, F, words, V)) return rc;
   if (!groups) return fail(fn, "null pointer (groups)");
-  if (max_per_group < 1) return fail(fn, "max_per_group must be >= 1");
-  return launch_item_topk_grouped(seq, items, B, V, d, k, first_item,
-                                  E > 0 ? exclude : nullptr, E, ids, scores, workspace,
-                                  workspace_bytes, allow, F, words, allow ? allow_rows : nullptr,
-                                  groups, max_per_group, reinterpret_cast<hipStream_t>(stream));
+  return item_topk(fn, seq, items, B, V, d, k, first_item, exclude, E, ids, scores, workspace,
+                   workspace_bytes, stream, allow, F, words, allow_rows, groups, max_per_group,
+                   /*prior*/ nullptr, 0, nullptr, nullptr);
 }
 
 int64_t rb_item_topk_prior_workspace(int64_t B, int64_t V, int64_t d, int64_t k) {
@@ -608,19 +632,11 @@ int rb_item_topk_prior(const float* seq, const float* items, int64_t B, int64_t 
                        const float* prior, int64_t P, const int64_t* prior_rows,
                        const float* prior_weight) {
   const char* fn = "rb_item_topk_prior";
-  if (int rc = check_item_topk(fn, seq, items, B, V, d, k, first_item, exclude, E, ids, scores,
-                               workspace))
-    return rc;
-  if (allow)
-    if (int rc = check_allow(fn, allow, F, words, V)) return rc;
-  if (groups && max_per_group < 1) return fail(fn, "max_per_group must be >= 1");
   if (!prior) return fail(fn, "null pointer (prior)");
   if (P < 1) return fail(fn, "P must be >= 1");
-  return launch_item_topk_prior(seq, items, B, V, d, k, first_item, E > 0 ? exclude : nullptr, E,
-                                ids, scores, workspace, workspace_bytes, allow, F, words,
-                                allow ? allow_rows : nullptr, groups, groups ? max_per_group : 1,
-                                prior, P, prior_rows, prior_weight,
-                                reinterpret_cast<hipStream_t>(stream));
+  return item_topk(fn, seq, items, B, V, d, k, first_item, exclude, E, ids, scores, workspace,
+                   workspace_bytes, stream, allow, F, words, allow_rows, groups, max_per_group,
+                   prior, P, prior_rows, prior_weight);
 }
 
 int rb_item_rank_prior(const float* seq, const float* items, const int64_t* target, int64_t B,
@@ -630,16 +646,11 @@ int rb_item_rank_prior(const float* seq, const float* items, const int64_t* targ
                        const float* prior, int64_t P, const int64_t* prior_rows,
                        const float* prior_weight) {
   const char* fn = "rb_item_rank_prior";
-  if (int rc = check_item_rank(fn, seq, items, target, B, V, d, first_item, n_greater, workspace))
-    return rc;
-  if (allow)
-    if (int rc = check_allow(fn, allow, F, words, V)) return rc;
   if (!prior) return fail(fn, "null pointer (prior)");
   if (P < 1) return fail(fn, "P must be >= 1");
-  return launch_item_rank_prior(seq, items, target, B, V, d, first_item, n_greater, n_equal,
-                                workspace, workspace_bytes, allow, F, words,
-                                allow ? allow_rows : nullptr, prior, P, prior_rows, prior_weight,
-                                reinterpret_cast<hipStream_t>(stream));
+  return item_rank(fn, seq, items, target, B, V, d, first_item, n_greater, n_equal, workspace,
+                   workspace_bytes, stream, allow, F, words, allow_rows, prior, P, prior_rows,
+                   prior_weight);
 }
 
 int rb_item_ce_probs(const float* seq, const float* items, const int64_t* target,

@@ -559,47 +559,42 @@ int launch_item_ce_fwd(const float* E, const float* W, const int64_t* tgt, int64
 int launch_item_ce_bwd(const float* E, const float* W, const int64_t* tgt, const float* lse,
                        const float* dloss, int64_t B, int64_t V, int64_t D, float* dE, float* dW,
                        void* ws, int64_t ws_bytes, hipStream_t st);
-int launch_item_rank(const float* E, const float* W, const int64_t* tgt, int64_t B, int64_t V,
-                     int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq, void* ws,
-                     int64_t ws_bytes, hipStream_t st);
+// The options of the fused top-k and ranks, as the kernels take them.  A launch
+// function takes each by pointer, null where the option is off.
+// Allow-bitmaps (include/recblr_filters.h): words [F, W] int32 (bit i of word w
+// of filter f: item 32 w + i is allowed), rows [B] int64 or null: the filter
+// each row selects.
+struct AllowArgs {
+  const int* words;
+  int64_t F, W;
+  const int64_t* rows;
+};
+// Diversity caps (include/recblr_groups.h): at most m items of a group per list.
+struct GroupArgs {
+  const int* ids;   // [V], -1 (uncapped) or a group in [0, RB_GROUP_ID_MAX]
+  int m;
+};
+// Score priors (include/recblr_priors.h): values [P, V] fp32, rows [B] int64 or
+// null (the prior each row takes), weight [B] fp32 or null (1 for every row).
+struct PriorArgs {
+  const float* values;
+  int64_t P, V;
+  const int64_t* rows;
+  const float* weight;
+};
+// fn: the C entry point's name, for the messages.  The top-k workspace is the
+// grouped one's with gr, the plain one's without.
+int launch_item_rank(const char* fn, const float* E, const float* W, const int64_t* tgt,
+                     int64_t B, int64_t V, int64_t D, int64_t first, int64_t* n_gt,
+                     int64_t* n_eq, void* ws, int64_t ws_bytes, const AllowArgs* al,
+                     const PriorArgs* pa, hipStream_t st);
 int64_t item_topk_workspace_bytes(int64_t B, int64_t V, int64_t k);
-int launch_item_topk(const float* E, const float* W, int64_t B, int64_t V, int64_t D, int64_t k,
-                     int64_t first, const int64_t* ex, int64_t NE, int64_t* ids, float* scores,
-                     void* ws, int64_t ws_bytes, hipStream_t st);
-// the two above under per-row allow-bitmaps (include/recblr_filters.h); same workspaces
-int launch_item_rank_allowed(const float* E, const float* W, const int64_t* tgt, int64_t B,
-                             int64_t V, int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq,
-                             void* ws, int64_t ws_bytes, const int* allow, int64_t F,
-                             int64_t words, const int64_t* allow_rows, hipStream_t st);
-int launch_item_topk_allowed(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
-                             int64_t k, int64_t first, const int64_t* ex, int64_t NE,
-                             int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
-                             const int* allow, int64_t F, int64_t words,
-                             const int64_t* allow_rows, hipStream_t st);
-// launch_item_topk with at most m items of a group per list (include/recblr_groups.h);
-// allow null: no filter
 int64_t item_topk_grouped_workspace_bytes(int64_t B, int64_t V, int64_t k);
-int launch_item_topk_grouped(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
-                             int64_t k, int64_t first, const int64_t* ex, int64_t NE,
-                             int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
-                             const int* allow, int64_t F, int64_t words,
-                             const int64_t* allow_rows, const int* groups, int64_t m,
-                             hipStream_t st);
-// launch_item_topk / launch_item_rank over scores adjusted by a per-item prior
-// (include/recblr_priors.h); allow null: no filter, groups null: no cap; the
-// top-k workspace is the grouped one's with groups, the plain one's without
-int launch_item_topk_prior(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
-                           int64_t k, int64_t first, const int64_t* ex, int64_t NE, int64_t* ids,
-                           float* scores, void* ws, int64_t ws_bytes, const int* allow, int64_t F,
-                           int64_t words, const int64_t* allow_rows, const int* groups, int64_t m,
-                           const float* prior, int64_t P, const int64_t* prior_rows,
-                           const float* prior_weight, hipStream_t st);
-int launch_item_rank_prior(const float* E, const float* W, const int64_t* tgt, int64_t B,
-                           int64_t V, int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq,
-                           void* ws, int64_t ws_bytes, const int* allow, int64_t F, int64_t words,
-                           const int64_t* allow_rows, const float* prior, int64_t P,
-                           const int64_t* prior_rows, const float* prior_weight,
-                           hipStream_t st);
+int launch_item_topk(const char* fn, const float* E, const float* W, int64_t B, int64_t V,
+                     int64_t D, int64_t k, int64_t first, const int64_t* ex, int64_t NE,
+                     int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
+                     const AllowArgs* al, const GroupArgs* gr, const PriorArgs* pa,
+                     hipStream_t st);
 int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, const float* lse,
                          const float* dloss, int64_t B, int64_t V, int64_t D, int64_t v_off,
                          float* out, int64_t ld, hipStream_t st);

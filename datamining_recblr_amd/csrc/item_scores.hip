@@ -218,14 +218,8 @@ __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2
 }
 
 // ---- allow-bitmaps: a filter is one 32-bit word per 32-item tile --------------------
-// words [F, W] int32 (bit i of word w of filter f: item 32 w + i is allowed),
-// rows [B] int64 or null: the filter each row selects.
-struct AllowArgs {
-  const int* words;
-  int64_t F, W;
-  const int64_t* rows;
-};
-
+// AllowArgs (common.h): words [F, W] int32, rows [B] int64 or null.
+//
 // One row's view of its filter.  rows null: filter 0.  f == -1: every item is
 // allowed; f outside [-1, F): none is.  The filter and word indices are
 // clamped for the load and the loaded word masked, so nothing is ever read out
@@ -266,15 +260,9 @@ __device__ __forceinline__ unsigned lane_bits(unsigned a, int h) {
 }
 
 // ---- score priors: a per-item term, weighted per row (include/recblr_priors.h) -----
-// values [P, V] fp32, rows [B] int64 or null (the prior each row takes), weight
-// [B] fp32 or null (1 for every row).
-struct PriorArgs {
-  const float* values;
-  int64_t P, V;
-  const int64_t* rows;
-  const float* weight;
-};
-
+// PriorArgs (common.h): values [P, V] fp32, rows [B] int64 or null, weight [B]
+// fp32 or null.
+//
 // One row's view of its prior.  rows null: prior 0.  f == -1: the row takes no
 // prior (its scores stay as they are, bit for bit); f outside [-1, P): the row
 // selects nothing.  The prior and item indices are clamped for the load and the
@@ -885,12 +873,8 @@ __device__ __forceinline__ bool beats(float s, int id, float s2, int id2) {
 // is (the newcomer beats an entry that the worst does not beat), so only a
 // replaced worst is followed by the rescan.  A tile's 32 group ids are read
 // one per lane, one tile ahead, and a candidate's id is fetched by shuffle.
+// GroupArgs: common.h.
 constexpr int kNoGroup = 0xffff;
-
-struct GroupArgs {
-  const int* ids;   // [V], -1 (uncapped) or a group in [0, RB_GROUP_ID_MAX]
-  int m;
-};
 
 //
 // kPrior (include/recblr_priors.h): a tile's scores become the adjusted scores
@@ -1839,13 +1823,13 @@ int launch_item_ce_bwd(const float* E, const float* W, const int64_t* tgt, const
   return launch_status("rb_item_ce_bwd");
 }
 
-namespace {
-// rb_item_rank (al null) and rb_item_rank_allowed: one workspace, one plan
-// ... and rb_item_rank_prior (pa given, al or not): kernels of its own
-int item_rank_launch(const char* fn, const float* E, const float* W, const int64_t* tgt,
+// rb_item_rank, _allowed and _prior (fn names the caller for the messages; al,
+// pa: null where the option is off): one workspace, one plan; a prior, with a
+// filter or not, has kernels of its own
+int launch_item_rank(const char* fn, const float* E, const float* W, const int64_t* tgt,
                      int64_t B, int64_t V, int64_t D, int64_t first, int64_t* n_gt,
                      int64_t* n_eq, void* ws, int64_t ws_bytes, const AllowArgs* al,
-                     hipStream_t st, const PriorArgs* pa = nullptr) {
+                     const PriorArgs* pa, hipStream_t st) {
   const RankWs L = rank_layout(B, V);
   if (ws_bytes < (int64_t)L.total) return fail((std::string(fn) + ": workspace too small").c_str());
   char* w = static_cast<char*>(ws);
@@ -1877,35 +1861,6 @@ int item_rank_launch(const char* fn, const float* E, const float* W, const int64
   hipLaunchKernelGGL(k_rank_rows, rows, dim3(256), 0, st, gt, eq, g.splits, ts, B, n_gt, n_eq);
   return launch_status(fn);
 }
-}  // namespace
-
-int launch_item_rank(const float* E, const float* W, const int64_t* tgt, int64_t B, int64_t V,
-                     int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq, void* ws,
-                     int64_t ws_bytes, hipStream_t st) {
-  return item_rank_launch("rb_item_rank", E, W, tgt, B, V, D, first, n_gt, n_eq, ws, ws_bytes,
-                          nullptr, st);
-}
-
-int launch_item_rank_allowed(const float* E, const float* W, const int64_t* tgt, int64_t B,
-                             int64_t V, int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq,
-                             void* ws, int64_t ws_bytes, const int* allow, int64_t F,
-                             int64_t words, const int64_t* allow_rows, hipStream_t st) {
-  const AllowArgs al{allow, F, words, allow_rows};
-  return item_rank_launch("rb_item_rank_allowed", E, W, tgt, B, V, D, first, n_gt, n_eq, ws,
-                          ws_bytes, &al, st);
-}
-
-int launch_item_rank_prior(const float* E, const float* W, const int64_t* tgt, int64_t B,
-                           int64_t V, int64_t D, int64_t first, int64_t* n_gt, int64_t* n_eq,
-                           void* ws, int64_t ws_bytes, const int* allow, int64_t F, int64_t words,
-                           const int64_t* allow_rows, const float* prior, int64_t P,
-                           const int64_t* prior_rows, const float* prior_weight,
-                           hipStream_t st) {
-  const AllowArgs al{allow, F, words, allow_rows};
-  const PriorArgs pa{prior, P, V, prior_rows, prior_weight};
-  return item_rank_launch("rb_item_rank_prior", E, W, tgt, B, V, D, first, n_gt, n_eq, ws,
-                          ws_bytes, allow ? &al : nullptr, st, &pa);
-}
 
 int64_t item_topk_workspace_bytes(int64_t B, int64_t V, int64_t k) {
   return (int64_t)topk_layout(B, V, k).total;
@@ -1915,24 +1870,27 @@ int64_t item_topk_grouped_workspace_bytes(int64_t B, int64_t V, int64_t k) {
   return (int64_t)topk_layout(B, V, k, true).total;
 }
 
-namespace {
-// rb_item_topk (al null), rb_item_topk_allowed and rb_item_topk_grouped (gr
-// given, al or not): one plan, and one workspace but for the grouped third array
-int item_topk_launch(const char* fn, const float* E, const float* W, int64_t B, int64_t V,
+// rb_item_topk, _allowed, _grouped and _prior (fn names the caller for the
+// messages; al, gr, pa: null where the option is off): one plan, one workspace
+// but for the cap's third array, one selection launch and one merge launch
+int launch_item_topk(const char* fn, const float* E, const float* W, int64_t B, int64_t V,
                      int64_t D, int64_t k, int64_t first, const int64_t* ex, int64_t NE,
                      int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
-                     const AllowArgs* al, hipStream_t st, const GroupArgs* gr = nullptr,
-                     const PriorArgs* pa = nullptr) {
+                     const AllowArgs* al, const GroupArgs* gr, const PriorArgs* pa,
+                     hipStream_t st) {
   const TopkWs L = topk_layout(B, V, k, gr != nullptr);
   if (ws_bytes < (int64_t)L.total) return fail((std::string(fn) + ": workspace too small").c_str());
   char* w = static_cast<char*>(ws);
   float* sc = reinterpret_cast<float*>(w + L.sc);
   int* id = reinterpret_cast<int*>(w + L.id);
+  int* cg = gr ? reinterpret_cast<int*>(w + L.g) : nullptr;
   const Grid2 g = plan(B, ntiles(V));
-  if (pa) {
-    // rb_item_topk_prior: the same plan, workspace and merge kernels
-    int* cg = gr ? reinterpret_cast<int*>(w + L.g) : nullptr;
-    if (int rc = for_item_dim(D, [&](auto dc) {
+  const AllowArgs a = al ? *al : AllowArgs{};
+  if (int rc = for_item_dim(D, [&](auto dc) {
+        // the kernel of the option set, at the candidate list's LDS capacity per
+        // (row, split): 32 or 64
+        const dim3 grid(g.wgs()), block(256);
+        if (pa) {
           const auto kernel =
               gr ? (k <= 32 ? k_item_topk_prior<dc, 32, true, true>
                             : k_item_topk_prior<dc, 64, true, true>)
@@ -1940,95 +1898,34 @@ int item_topk_launch(const char* fn, const float* E, const float* W, int64_t B, 
                               : k_item_topk_prior<dc, 64, true, false>)
                    : (k <= 32 ? k_item_topk_prior<dc, 32, false, false>
                               : k_item_topk_prior<dc, 64, false, false>);
-          hipLaunchKernelGGL(kernel, dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, (int)k,
-                             ex, NE, g.per, g.blocks, g.splits, sc, id, cg,
-                             al ? *al : AllowArgs{}, gr ? *gr : GroupArgs{}, *pa);
-        }))
-      return rc;
-    if (gr)
-      hipLaunchKernelGGL(k_topk_rows_grouped, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, sc,
-                         id, cg, g.splits, B, (int)k, gr->m, ids, scores);
-    else
-      hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, sc, id,
-                         g.splits, B, (int)k, ids, scores);
-    return launch_status(fn);
-  }
-  if (gr) {
-    int* cg = reinterpret_cast<int*>(w + L.g);
-    if (int rc = for_item_dim(D, [&](auto dc) {
+          hipLaunchKernelGGL(kernel, grid, block, 0, st, E, W, B, V, first, (int)k, ex, NE, g.per,
+                             g.blocks, g.splits, sc, id, cg, a, gr ? *gr : GroupArgs{}, *pa);
+        } else if (gr) {
           const auto kernel =
               al ? (k <= 32 ? k_item_topk_grouped<dc, 32, true> : k_item_topk_grouped<dc, 64, true>)
                  : (k <= 32 ? k_item_topk_grouped<dc, 32, false>
                             : k_item_topk_grouped<dc, 64, false>);
-          hipLaunchKernelGGL(kernel, dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, (int)k,
-                             ex, NE, g.per, g.blocks, g.splits, sc, id, cg,
-                             al ? *al : AllowArgs{}, *gr);
-        }))
-      return rc;
-    hipLaunchKernelGGL(k_topk_rows_grouped, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, sc,
-                       id, cg, g.splits, B, (int)k, gr->m, ids, scores);
-    return launch_status(fn);
-  }
-  if (int rc = for_item_dim(D, [&](auto dc) {
-        // the candidate list's LDS capacity per (row, split)
-        if (al) {
+          hipLaunchKernelGGL(kernel, grid, block, 0, st, E, W, B, V, first, (int)k, ex, NE, g.per,
+                             g.blocks, g.splits, sc, id, cg, a, *gr);
+        } else if (al) {
           const auto kernel = k <= 32 ? k_item_topk_allowed<dc, 32> : k_item_topk_allowed<dc, 64>;
-          hipLaunchKernelGGL(kernel, dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, (int)k,
-                             ex, NE, g.per, g.blocks, g.splits, sc, id, *al);
+          hipLaunchKernelGGL(kernel, grid, block, 0, st, E, W, B, V, first, (int)k, ex, NE, g.per,
+                             g.blocks, g.splits, sc, id, a);
         } else {
           const auto kernel = k <= 32 ? k_item_topk<dc, 32> : k_item_topk<dc, 64>;
-          hipLaunchKernelGGL(kernel, dim3(g.wgs()), dim3(256), 0, st, E, W, B, V, first, (int)k,
-                             ex, NE, g.per, g.blocks, g.splits, sc, id);
+          hipLaunchKernelGGL(kernel, grid, block, 0, st, E, W, B, V, first, (int)k, ex, NE, g.per,
+                             g.blocks, g.splits, sc, id);
         }
       }))
     return rc;
-  hipLaunchKernelGGL(k_topk_rows, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, sc, id,
-                     g.splits, B, (int)k, ids, scores);
+  const dim3 rows((unsigned)((B + 3) / 4));
+  if (gr)
+    hipLaunchKernelGGL(k_topk_rows_grouped, rows, dim3(256), 0, st, sc, id, cg, g.splits, B,
+                       (int)k, gr->m, ids, scores);
+  else
+    hipLaunchKernelGGL(k_topk_rows, rows, dim3(256), 0, st, sc, id, g.splits, B, (int)k, ids,
+                       scores);
   return launch_status(fn);
-}
-}  // namespace
-
-int launch_item_topk(const float* E, const float* W, int64_t B, int64_t V, int64_t D, int64_t k,
-                     int64_t first, const int64_t* ex, int64_t NE, int64_t* ids, float* scores,
-                     void* ws, int64_t ws_bytes, hipStream_t st) {
-  return item_topk_launch("rb_item_topk", E, W, B, V, D, k, first, ex, NE, ids, scores, ws,
-                          ws_bytes, nullptr, st);
-}
-
-int launch_item_topk_allowed(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
-                             int64_t k, int64_t first, const int64_t* ex, int64_t NE,
-                             int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
-                             const int* allow, int64_t F, int64_t words,
-                             const int64_t* allow_rows, hipStream_t st) {
-  const AllowArgs al{allow, F, words, allow_rows};
-  return item_topk_launch("rb_item_topk_allowed", E, W, B, V, D, k, first, ex, NE, ids, scores,
-                          ws, ws_bytes, &al, st);
-}
-
-int launch_item_topk_grouped(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
-                             int64_t k, int64_t first, const int64_t* ex, int64_t NE,
-                             int64_t* ids, float* scores, void* ws, int64_t ws_bytes,
-                             const int* allow, int64_t F, int64_t words,
-                             const int64_t* allow_rows, const int* groups, int64_t m,
-                             hipStream_t st) {
-  const AllowArgs al{allow, F, words, allow_rows};
-  // a cap of k or more never binds: clamp it into the kernel's int
-  const GroupArgs gr{groups, (int)std::min<int64_t>(m, k)};
-  return item_topk_launch("rb_item_topk_grouped", E, W, B, V, D, k, first, ex, NE, ids, scores,
-                          ws, ws_bytes, allow ? &al : nullptr, st, &gr);
-}
-
-int launch_item_topk_prior(const float* E, const float* W, int64_t B, int64_t V, int64_t D,
-                           int64_t k, int64_t first, const int64_t* ex, int64_t NE, int64_t* ids,
-                           float* scores, void* ws, int64_t ws_bytes, const int* allow, int64_t F,
-                           int64_t words, const int64_t* allow_rows, const int* groups, int64_t m,
-                           const float* prior, int64_t P, const int64_t* prior_rows,
-                           const float* prior_weight, hipStream_t st) {
-  const AllowArgs al{allow, F, words, allow_rows};
-  const GroupArgs gr{groups, (int)std::min<int64_t>(m, k)};
-  const PriorArgs pa{prior, P, V, prior_rows, prior_weight};
-  return item_topk_launch("rb_item_topk_prior", E, W, B, V, D, k, first, ex, NE, ids, scores, ws,
-                          ws_bytes, allow ? &al : nullptr, st, groups ? &gr : nullptr, &pa);
 }
 
 int launch_item_ce_probs(const float* E, const float* W, const int64_t* tgt, const float* lse,

@@ -910,15 +910,12 @@ def target_ranks(seq: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
     allow, allow_rows = _check_allow(allow, allow_rows, seq.shape[0], table.shape[0], seq.device)
     prior, prior_rows, prior_weight = _check_prior(prior, prior_rows, prior_weight, seq.shape[0],
                                                    table.shape[0], seq.device)
-    if prior is not None:
-        return kernels.item_rank(seq.detach(), table.detach(), target, first_item=first_item,
-                                 allow=allow.words if allow is not None else None,
-                                 allow_rows=allow_rows, prior=prior.values,
-                                 prior_rows=prior_rows, prior_weight=prior_weight)
-    if allow is None:
-        return kernels.item_rank(seq.detach(), table.detach(), target, first_item=first_item)
+    opts = dict(allow=allow.words if allow is not None else None, allow_rows=allow_rows,
+                prior=prior.values if prior is not None else None, prior_rows=prior_rows,
+                prior_weight=prior_weight)
+    # an absent option stays out of the call (item_rank picks the entry point from the rest)
     return kernels.item_rank(seq.detach(), table.detach(), target, first_item=first_item,
-                             allow=allow.words, allow_rows=allow_rows)
+                             **{name: v for name, v in opts.items() if v is not None})
 
 
 def _top_items_torch(seq, table, k, first_item, exclude, allow=None, allow_rows=None,
@@ -1052,24 +1049,14 @@ def top_items(seq: torch.Tensor, table: torch.Tensor, k: int, first_item: int = 
             groups is None or groups.n_groups <= kernels.ITEM_GROUP_ID_MAX + 1):
         if exclude is not None:
             exclude = exclude.to(device=seq.device, dtype=torch.int64)
-        if prior is not None:
-            return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
-                                     exclude=exclude,
-                                     allow=allow.words if allow is not None else None,
-                                     allow_rows=allow_rows,
-                                     groups=groups.ids if groups is not None else None,
-                                     max_per_group=m, prior=prior.values, prior_rows=prior_rows,
-                                     prior_weight=prior_weight)
-        if groups is not None:
-            return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
-                                     exclude=exclude,
-                                     allow=allow.words if allow is not None else None,
-                                     allow_rows=allow_rows, groups=groups.ids, max_per_group=m)
-        if allow is None:
-            return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
-                                     exclude=exclude)
+        opts = dict(allow=allow.words if allow is not None else None, allow_rows=allow_rows,
+                    groups=groups.ids if groups is not None else None, max_per_group=m,
+                    prior=prior.values if prior is not None else None, prior_rows=prior_rows,
+                    prior_weight=prior_weight)
+        # an absent option stays out of the call (item_topk picks the entry point from the rest)
         return kernels.item_topk(seq.detach(), table.detach(), k, first_item=first_item,
-                                 exclude=exclude, allow=allow.words, allow_rows=allow_rows)
+                                 exclude=exclude,
+                                 **{name: v for name, v in opts.items() if v is not None})
     return _top_items_torch(seq.detach(), table.detach(), k, first_item, exclude, allow,
                             allow_rows, groups, m, prior, prior_rows, prior_weight)
 

@@ -14,7 +14,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(1, 1, 16), (5, 7, 32), (33, 64, 64), (130, 97, 64), (37, 515, 256), (64, 1000, 128),
-          (300, 10544, 128)]
+          (300, 10544, 128), (5, 300, 16)]
 KS = (1, 10, 20, 64)
 
 
@@ -71,11 +71,18 @@ def _case(B, V, d, cuda, seed=0):
 
 @pytest.mark.parametrize("first_item", [0, 1])
 @pytest.mark.parametrize("B,V,d", SHAPES)
-def test_topk_exact_against_scores(cuda, B, V, d, first_item):
+def test_topk_exact_against_scores(cuda, monkeypatch, B, V, d, first_item):
     from datamining_recblr_amd import kernels
 
     seq, W, S = _case(B, V, d, cuda)
     ref_ids, ref_sc = _reference(S, max(KS), first_item)
+    launches, real_launch = [], kernels._launch
+
+    def spy_launch(name, *a, **kw):
+        launches.append(name)
+        return real_launch(name, *a, **kw)
+
+    monkeypatch.setattr(kernels, "_launch", spy_launch)
     for k in KS:
         got = kernels.item_topk(seq, W, k, first_item=first_item)
         _same(got, (ref_ids[:, :k], ref_sc[:, :k]), f"k={k}")
@@ -84,6 +91,7 @@ def test_topk_exact_against_scores(cuda, B, V, d, first_item):
             assert (got[0][:, n_ok:] == -1).all()
             assert (got[1][:, n_ok:] == float("-inf")).all()
             assert (got[0][:, :n_ok] >= first_item).all()
+    assert launches == ["rb_item_topk"] * len(KS)      # the plain entry, at both list capacities
 
 
 def _group_rank(S, item, first_item=1):
